@@ -1,11 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X: 16 kHz PCM -> HIP fbank -> ResNetBigger fwd/bwd -> clip + Adam.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path over one batch of `--batch` synthetic 1 s clips per GPU that are already
 resident in HBM (BASELINE.json configs[2]; for N > 1 configs[3]: data-parallel, one RCCL all-reduce of the flat
-gradient per step, weak scaling).  Rank 0 prints ONE JSON line (contract in the task statement) carrying
+gradient per step, weak scaling).  Rank 0 prints ONE JSON line: metric, value (segments/s), unit, higher_is_better,
+dtype, ms_per_step and the configuration.  A plain run does nothing else: set-up, W warm-up steps, K timed steps, the
+outputs (--dump-outputs), the line.
+
+--dump-outputs DIR  rank 0 writes what the timed step computed in its last step, as a caller of the step receives it, to
+               DIR/<name>.npy (float32, < 64 MB in all): `features` (fbank output), `probs`, `metrics` (the head's
+               counters), `grad_norm`, `params` (flat parameters after Adam), `bn_running_stats`.  The inputs are seeded:
+               two runs with the same arguments compute from the same data.
+
+--full adds what takes runs of its own; its keys are null in a plain line:
   roofline     the dominant kernel (conv_b3<64,64,9>: the eight 64->64 3x3 convolution launches of block1, forward and
                data gradient, on the bf16 matrix cores with three-way split operands): algorithmic FLOPs per launch /
                mean launch duration from HIP events recorded on the launch stream inside the timed region, against the
@@ -14,11 +23,13 @@ gradient per step, weak scaling).  Rank 0 prints ONE JSON line (contract in the 
   cpu_baseline the CPU oracle (oracle/, a port) timed on this host by the protocol of SURVEY.md section 8(d) /
                BASELINE.md section 3 (C1: 256 clips at batch 32, eval and train, all cores and one thread, median of 3);
   side         (N = 1 only) BASELINE configs[1] (HIP fbank, 1024 clips) and configs[4] (fp16 sliding-window inference
-               over a 60 min channel) as sub-records with their own rooflines: < 2 s of GPU time.
+               over a 60 min channel) as sub-records with their own rooflines: < 2 s of GPU time; the same step on
+               non-degenerate weights (train_realistic) and on the two exact arithmetics (train_exact);
+  allreduce_ms_per_step  (N > 1, or one rank under a launcher) HIP events around every all-reduce.
 
-Timing.  After W warm-up steps the run times three blocks of exactly K steps each, every block bracketed by barrier +
-synchronize on both sides and max-reduced over the ranks; `ms_per_step` and `value` are the MEDIAN block, the three
-block times and their spread are in the line (a 0.3 s region is otherwise a single sample; boxes differ by 2-3 %).
+Timing.  After W warm-up steps the run times one block of exactly K steps (`--blocks B`: B blocks of K steps), every block
+bracketed by barrier + synchronize on both sides and max-reduced over the ranks; `ms_per_step` and `value` are the MEDIAN
+block, the block times and their spread are in the line.
 
 Ranks.  With `--gpus N > 1` the N ranks come from an outer launcher (`python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N`, which exports RANK / WORLD_SIZE) or, when no launcher environment is present, from this script
@@ -188,6 +199,31 @@ def _make_model(dropout, dev, degenerate_ok):
                 b.copy_(torch.randn(b.shape, generator=g) * 0.2)
     model.engine.notify_weights_changed()
     return model
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: under 64 MB in all, headers included
+
+
+def dump_outputs(out_dir, model, feats, met):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files in out_dir.  The per-segment arrays (features,
+    probs) keep every segment while they fit the budget; past it, a fixed seeded sample of segments (the same rows in both)."""
+    import numpy as np
+    eng = model.engine
+    plan = eng._last_train_plan
+    torch.cuda.synchronize()
+    whole = {"metrics": met, "grad_norm": eng._norm_out, "params": eng.flat_param(),
+             "bn_running_stats": torch.cat([b.detach().reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()])}
+    whole = {k: v.detach().float().cpu().numpy() for k, v in whole.items()}
+    B = feats.shape[0]
+    per_seg = feats[0].numel() * 4 + 4
+    keep = max(1, (DUMP_BUDGET_BYTES - sum(v.nbytes for v in whole.values())) // per_seg)
+    rows = None if B <= keep else torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, keep, replace=False))).to(feats.device)
+    per = {"features": feats, "probs": plan["probs"][:B]}
+    for k, v in per.items():
+        whole[k] = (v if rows is None else v.index_select(0, rows)).detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in whole.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def _pmc_traffic(name):
@@ -498,12 +534,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps each; the line reports the median block")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps each; the line reports the median block")
     ap.add_argument("--batch", type=int, default=512, help="segments per GPU per step")
     ap.add_argument("--dropout", type=float, default=0.5, help="train.py default")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the roofline (per-kernel events), the all-reduce time, the side "
+                    "records and the CPU baseline; a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: time budget of the CPU baseline (0 = skip)")
     ap.add_argument("--cpu-clips", type=int, default=256, help="clips in the CPU baseline's C1 workload (256 = the protocol; tests shrink it)")
-    ap.add_argument("--no-side", action="store_true", help="skip the configs[1] / configs[4] sub-records")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the configs[1] / configs[4] sub-records")
     ap.add_argument("--dump-params", default=None, help="rank 0 saves its flat parameter buffer here after the timed steps (tests: "
                                                         "the data-parallel result against a single-process emulation)")
     ap.add_argument("--no-kernel-events", action="store_true")
@@ -548,6 +587,8 @@ def main():
         # parent launcher: this process has made no GPU call; it starts the ranks as fresh children and waits
         raise SystemExit(parallel.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:], timeout=parallel.SPAWN_TIMEOUT_S))
     if args.workload != "train":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: train workload only")
         return side_workload(args)
 
     rank, world, local = parallel.init_from_env()
@@ -599,7 +640,7 @@ def main():
     for _ in range(args.warmup):
         met = step()
     torch.cuda.synchronize()
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         model.engine.kernel_events = {dominant: []}
         reducer.events = []
     calls0 = reducer.calls
@@ -632,6 +673,8 @@ def main():
     model.engine.kernel_events = None
     if args.dump_params and rank == 0:
         torch.save(model.engine.flat_param().detach().cpu(), args.dump_params)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, feats, met)
     loss = metrics_from_counters(met.cpu().numpy())[0]
     allreduce_ms = allreduce_ranks = None
     if reducer.events:
@@ -721,7 +764,7 @@ def main():
                                      "avg_launch_ms includes that (`--no-overlap-small`: 0.5524 ms, frac 0.3616, step +0.07 ms)")
         seg_s = world * B * args.steps / dt
         side = None
-        if world == 1 and not args.no_side:
+        if args.full and world == 1 and not args.no_side:
             side = {"fbank_1024": fbank_record(extractor, dev, 50, 10),
                     "infer_60min_fp16": infer_record(extractor, dev, 60.0, "fp16")}
             side["infer_60min_fp16"]["predicted_8gpu_rtf"] = infer_record(extractor, dev, 60.0, "fp16", emulate_world=8)
@@ -729,7 +772,7 @@ def main():
             if not (args.no_b3 or args.no_h2):
                 side["train_exact"] = exact_legs(args, extractor, dev, reducer, pcm, labels)
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             cpu = cpu_baseline(args.cpu_seconds, clips_c1=args.cpu_clips)
         which = "configs[2]" if world == 1 else "configs[3]"
         out = {

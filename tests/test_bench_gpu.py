@@ -22,7 +22,7 @@ def _run(*args, env=None):
 
 
 def test_train_line_has_the_contract_fields():
-    d = _run("--gpus", "1", "--steps", "3", "--warmup", "2", "--cpu-seconds", "4", "--cpu-clips", "64")
+    d = _run("--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--blocks", "3", "--cpu-seconds", "4", "--cpu-clips", "64")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "side", "rccl_ranks"):
         assert k in d, k
@@ -55,7 +55,7 @@ def test_train_line_has_the_contract_fields():
         assert cpu[k] > 0
     assert cpu["value"] == cpu["train_all_threads"] and cpu["repetitions"] == 3 and cpu["cpu_model"]
     assert cpu["eval_all_threads"] > cpu["train_all_threads"]
-    # the sub-records of configs[1] and configs[4] ride on the default line
+    # the sub-records of configs[1] and configs[4] ride on the --full line
     fb, inf = d["side"]["fbank_1024"], d["side"]["infer_60min_fp16"]
     assert fb["roofline"]["bound"] == "hbm" and 0 < fb["roofline"]["frac"] < 1 and "configs[1]" in fb["config"]["workload"]
     assert inf["config"]["windows"] == 360000 and inf["higher_is_better"] is False and inf["dtype"] == "f16"
@@ -77,6 +77,33 @@ def test_train_line_has_the_contract_fields():
     assert real["value"] > 0 and "non-degenerate" in real["state"] and 0.5 * d["value"] < real["value"] < 1.5 * d["value"]
 
 
+def test_plain_line_times_exactly_the_steps_asked_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (one block of exactly --steps steps; no roofline, side records or
+    CPU baseline), and --dump-outputs writes the last timed step's outputs: float32, < 64 MB, from the same seeded inputs
+    in every run."""
+    import numpy as np
+    B, runs = 64, []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--dump-outputs", str(out))
+        assert d["steps"] == 3 and d["warmup"] == 1 and len(d["timed_blocks"]["ms_per_step"]) == 1
+        assert d["ms_per_step"] == d["timed_blocks"]["ms_per_step"][0]
+        assert d["value"] == pytest.approx(B / (d["ms_per_step"] * 1e-3), rel=0.02) and d["higher_is_better"] is True
+        assert d["unit"] == "segments/s" and d["dtype"].startswith("f32") and "segments/sec" in d["metric"]
+        assert d["roofline"] is None and d["side"] is None and d["cpu_baseline"] is None and d["allreduce_ms_per_step"] is None
+        files = {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}
+        assert set(files) == {"features", "probs", "metrics", "grad_norm", "params", "bn_running_stats"}
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) < 64e6
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in files.values())
+        assert files["features"].shape == (B, 100, 44) and files["probs"].shape == (B,) and files["metrics"][5] == B
+        assert ((files["probs"] > 0) & (files["probs"] < 1)).all() and files["grad_norm"][0] > 0
+        runs.append(files)
+    a, b = runs
+    assert np.array_equal(a["features"], b["features"])
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, err_msg=k)
+
+
 def test_one_rank_under_a_launcher_goes_through_rccl():
     """RANK / WORLD_SIZE = 0 / 1 as torchrun exports them: the `nccl` (= RCCL) group is initialised and every step's
     flat gradient goes through dist.all_reduce -- the code path of N > 1, observable on a one-GPU box."""
@@ -86,7 +113,7 @@ def test_one_rank_under_a_launcher_goes_through_rccl():
         port = s.getsockname()[1]
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    d = _run("--gpus", "1", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0", "--no-side", env=env)
+    d = _run("--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--cpu-seconds", "0", "--no-side", env=env)
     assert d["rccl_ranks"] == 1 and d["config"]["backend"] == "nccl" and d["n_gpus"] == 1
     assert d["allreduce_calls"] == 4 and d["allreduce_ms_per_step"] > 0
     assert d["value"] > 0 and d["cpu_baseline"] is None and d["side"] is None
@@ -104,7 +131,8 @@ def test_ranks_rehearsed_on_one_gpu(world, batch):
     env = dict(os.environ, LAD_REHEARSE_ON_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    d = _run("--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", str(batch), "--cpu-seconds", "0", "--no-side", env=env)
+    d = _run("--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", str(batch), "--full", "--cpu-seconds", "0", "--no-side",
+             env=env)
     assert d["n_gpus"] == world and d["rccl_ranks"] == world and d["config"]["backend"] == "gloo"
     assert "configs[3]" in d["config"]["workload"] and d["config"]["parallelism"] == f"dp{world}" and d["config"]["global_batch"] == world * batch
     assert d["allreduce_calls"] == 3 and d["scaling"] == "weak"
@@ -130,7 +158,7 @@ def test_two_ranks_give_the_parameters_of_the_single_process_emulation(tmp_path)
     dump = str(tmp_path / "rank0_params.pt")
     steps, warmup, B = 2, 1, 64
     d = _run("--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--blocks", "1", "--batch", str(B), "--dropout", "0",
-             "--cpu-seconds", "0", "--no-side", "--dump-params", dump, env=env)
+             "--full", "--cpu-seconds", "0", "--no-side", "--dump-params", dump, env=env)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["allreduce_calls"] == steps and d["scaling"] == "weak"
     assert d["config"]["backend"] == ("nccl" if two else "gloo")
     r = d["allreduce_ms_per_step_over_ranks"]
@@ -187,7 +215,7 @@ def test_other_workloads_print_one_line():
 
 def test_ab_switches_of_the_train_workload_run():
     """The A/B switches bench.py offers for the round-4 fusions and schedules: each runs and reports itself in `config`."""
-    base = ("--steps", "2", "--warmup", "1", "--no-side", "--cpu-seconds", "0", "--blocks", "1", "--batch", "32")
+    base = ("--steps", "2", "--warmup", "1", "--full", "--no-side", "--cpu-seconds", "0", "--blocks", "1", "--batch", "32")
     a = _run(*base)
     b = _run(*base, "--no-fuse-bnbwd-wgrad")
     c = _run(*base, "--overlap-small")

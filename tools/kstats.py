@@ -1,4 +1,4 @@
-"""Per-step table of a rocprofv3 kernel_stats.csv of `bench.py --steps K --warmup W` (3 timed blocks: 3K + W steps in all).
+"""Per-step table of a rocprofv3 kernel_stats.csv of `bench.py --steps K --warmup W [--blocks B]` (B timed blocks: BK + W steps in all).
    python tools/kstats.py profiles/r04a_bench_bs512_kernel_stats.csv --steps 33 [--top 40]"""
 import argparse, csv
 ap = argparse.ArgumentParser()
