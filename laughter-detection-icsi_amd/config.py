@@ -24,9 +24,11 @@ MODEL_MAP['resnet_base'] = {
     'filter_sizes': [64, 32, 16, 16],
 }
 
-# Kept for name compatibility.  As in the reference this preset cannot run on (100,44) features
-# (flattened size 96 != linear_layer_size 128 -> RuntimeError); the HIP kernels are
-# instantiated for the resnet_base widths only.
+# The reference's default for segment_laughter.py.  It runs on the reference's original features, FEAT['num_samples'] = 128
+# (128 x 44 windows: block4 leaves 32 channels x 16 x 6, AvgPool2d(4) -> 32 x 4 x 1 = 128 = linear_layer_size; config.py:14-15 of
+# the reference).  On (100, 44) features it fails exactly as the reference does (flattened size 96 != 128 -> RuntimeError,
+# SURVEY.md section 0).  These widths run on the exact-f32 kernels only (engine.ResNetEngine.base_widths): no split-operand or
+# fp16 paths.
 MODEL_MAP['resnet_with_augmentation'] = {
     'batch_size': 32,
     'model': models.ResNetBigger,

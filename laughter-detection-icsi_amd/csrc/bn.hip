@@ -657,7 +657,7 @@ int bn_bwd_impl(const float *dy, const float *y, const unsigned long long *bits,
     LAD_REQUIRE(mode >= 0 && mode <= 2, "lad_bn_bwd: bad mode");
     LAD_REQUIRE(mode == 0 || aux, "lad_bn_bwd: mode needs aux");
     LAD_REQUIRE(mode != 2 || (xs && scoef && sgamma && dsgamma && dsbeta), "lad_bn_bwd: mode 2 needs the shortcut tensors");
-    LAD_REQUIRE(channels == 16 || channels == 32 || channels == 64, "lad_bn_bwd: channels must be 16, 32 or 64");
+    LAD_REQUIRE(channels == 16 || channels == 32 || channels == 64 || channels == 128, "lad_bn_bwd: channels must be 16, 32, 64 or 128");
     LAD_REQUIRE(batch >= 0 && H >= 1 && W >= 1, "lad_bn_bwd: bad geometry");
     if (batch == 0) return LAD_OK;
     const RowGeom rg = make_row_geom(batch, H, W);
@@ -683,7 +683,7 @@ int bn_bwd_impl(const float *dy, const float *y, const unsigned long long *bits,
             hipLaunchKernelGGL((bn_bwd_reduce_kernel<CC, false>), dim3(groups), dim3(THREADS), 0, st, (const float4 *)dy, \
                                (const float4 *)y, (const float4 *)x, coef, nullptr, nullptr, workspace, rows, relu, bits); \
     }
-    LAD_RED(16) LAD_RED(32) LAD_RED(64)
+    LAD_RED(16) LAD_RED(32) LAD_RED(64) LAD_RED(128)   // (128: block1 of resnet_with_augmentation)
 #undef LAD_RED
     }
     int rc = check_launch("bn_bwd_reduce_kernel");

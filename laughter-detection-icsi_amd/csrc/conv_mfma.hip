@@ -393,7 +393,7 @@ __device__ __forceinline__ void s1_epilogue(f32x16 (&acc)[NTiles<COUT>::NT], con
 }
 
 template <int CIN, int COUT, int TAPS, int EPI, int RB>
-__global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_s1_kernel(const float *__restrict__ in,
+__global__ __launch_bounds__(THREADS, (RB == 1 && COUT <= 64) ? 3 : 2) void conv_s1_kernel(const float *__restrict__ in,
                                                              const float *__restrict__ wt,
                                                              const float *__restrict__ bias,
                                                              const float *__restrict__ addend,
@@ -560,6 +560,17 @@ __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_s1_kernel(const
     LAD_STAMP_AT(3)
 }
 
+// Fragments of one tap that the stride-2 kernels request before their MFMAs: all of them (G groups of 8 channels x (1 + NT)
+// float4) where that is at most 24 float4, as at the resnet_base widths; otherwise (128 input channels, 64 or 128 output
+// channels) GC groups at a time, GC the largest power of two that keeps to 24 -- the whole tap held 192 registers there.
+// The MFMAs run in the same order either way.
+template <int G, int NT>
+struct S2Chunk {
+    static constexpr int cap(int g) { return (g > 1 && g * (1 + NT) > 24) ? cap(g / 2) : g; }
+    static constexpr int GC = cap(G);
+    static_assert(G % GC == 0, "chunks of whole 8-channel groups");
+};
+
 // SC (3x3 only): the block's 1x1 stride-2 shortcut convolution (no bias) reads exactly the rows the 3x3's centre tap
 // gathers, so its product rides on that tap's A fragments into a second accumulator and leaves through a second
 // epilogue (out_sc, partials_sc) -- one launch and one pass over the input instead of two.
@@ -597,7 +608,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv_s2_kernel(const float *__rest
     }
     if (gk == 0) mask_s[wave * 32 + i] = inter ? 1.0f : 0.0f;
 
-    f32x16 acc[NT], acc_sc[SC ? NT : 1];
+    f32x16 acc[NT], acc_sc[NT];   // (acc_sc: dead without SC)
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -612,28 +623,32 @@ __global__ __launch_bounds__(THREADS, 2) void conv_s2_kernel(const float *__rest
     // Lanes of non-interior output rows gather from the first image (base_row = 0: in-bounds); their accumulators are
     // discarded by the row mask in the epilogue, so the loop carries no predicate.
     constexpr int G = CIN / 8;
+    constexpr int GC = S2Chunk<G, NT>::GC;   // 8-channel groups whose fragments are in flight together
 #pragma unroll 1
     for (int tap = 0; tap < TAPS; ++tap) {
         const int ky = (TAPS == 9) ? tap / 3 : 1, kx = (TAPS == 9) ? tap % 3 : 1;
         const float *ap = in + (base_row + (int64_t)ky * gi.Wp + kx) * CIN + 4 * gk;
         const float *wp = w_base + tap * (C4 * COUTP * 4);
-        float4 av[G], bv[G][NT];  // the whole tap's fragments requested together, then its MFMAs
+        float4 av[G], bv[G][NT];  // the tap's fragments requested together (GC groups at a time), then their MFMAs
 #pragma unroll
-        for (int c8 = 0; c8 < G; ++c8) {
-            av[c8] = *reinterpret_cast<const float4 *>(ap + c8 * 8);
+        for (int g0 = 0; g0 < G; g0 += GC) {
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bv[c8][n] = *reinterpret_cast<const float4 *>(wp + (c8 * 2 * COUTP + n * 32) * 4);
-        }
+            for (int c8 = g0; c8 < g0 + GC; ++c8) {
+                av[c8] = *reinterpret_cast<const float4 *>(ap + c8 * 8);
 #pragma unroll
-        for (int c8 = 0; c8 < G; ++c8) {
+                for (int n = 0; n < NT; ++n) bv[c8][n] = *reinterpret_cast<const float4 *>(wp + (c8 * 2 * COUTP + n * 32) * 4);
+            }
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].x, bv[c8][n].x, acc[n]);
+            for (int c8 = g0; c8 < g0 + GC; ++c8) {
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].y, bv[c8][n].y, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].x, bv[c8][n].x, acc[n]);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].z, bv[c8][n].z, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].y, bv[c8][n].y, acc[n]);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].w, bv[c8][n].w, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].z, bv[c8][n].z, acc[n]);
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].w, bv[c8][n].w, acc[n]);
+            }
         }
         if (SC && tap == 4) {   // centre tap: the 1x1 shortcut on the same A fragments (1x1 image = one tap slot)
             const float *wp2 = wt_sc + (gk * COUTP + i) * 4;
@@ -656,7 +671,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv_s2_kernel(const float *__rest
     }
     __syncthreads();
     conv_epilogue<COUT>(acc, bias, nullptr, out, partials, mask_s, out_s, red_s, q0, go.rows, scale, relu);
-    if (SC) {
+    if constexpr (SC) {
         __syncthreads();   // the first epilogue's use of out_s / red_s is over
         conv_epilogue<COUT>(acc_sc, nullptr, nullptr, out_sc, partials_sc, mask_s, out_s, red_s, q0, go.rows, nullptr, 0);
     }
@@ -859,6 +874,13 @@ extern "C" int lad_conv_fwd(const float *in, const float *wt, const float *bias,
     LAD_S1_CASE(32, 64, 1)
     LAD_S1_CASE(16, 32, 1)
     LAD_S1_CASE(16, 16, 1)
+    // resnet_with_augmentation widths (block1: 64 -> 128 with a stride-1 1x1 projection shortcut, 128 -> 128); the data
+    // gradients of those layers swap the channel counts
+    LAD_S1_CASE(128, 128, 9)
+    LAD_S1_CASE(64, 128, 9)
+    LAD_S1_CASE(128, 64, 9)
+    LAD_S1_CASE(64, 128, 1)
+    LAD_S1_CASE(128, 64, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_fwd: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 
@@ -892,6 +914,10 @@ extern "C" int lad_conv_s2_fwd(const float *in, const float *wt, const float *bi
     LAD_S2_CASE(64, 32, 1)
     LAD_S2_CASE(32, 16, 1)
     LAD_S2_CASE(16, 16, 1)
+    LAD_S2_CASE(128, 64, 9)   // resnet_with_augmentation: block2.0 and block4.0
+    LAD_S2_CASE(128, 64, 1)
+    LAD_S2_CASE(32, 32, 9)
+    LAD_S2_CASE(32, 32, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_s2_fwd: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 
@@ -952,6 +978,9 @@ extern "C" int lad_conv_fwd_eval(const float *in, const float *wt, const float *
     LAD_S1E_CASE(64, 64, 9)
     LAD_S1E_CASE(32, 32, 9)
     LAD_S1E_CASE(16, 16, 9)
+    LAD_S1E_CASE(128, 128, 9)   // resnet_with_augmentation: block1
+    LAD_S1E_CASE(64, 128, 9)
+    LAD_S1E_CASE(64, 128, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_fwd_eval: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 
@@ -974,6 +1003,10 @@ extern "C" int lad_conv_s2_fwd_eval(const float *in, const float *wt, const floa
     LAD_S2E_CASE(64, 32, 1)
     LAD_S2E_CASE(32, 16, 1)
     LAD_S2E_CASE(16, 16, 1)
+    LAD_S2E_CASE(128, 64, 9)    // resnet_with_augmentation: block2.0 and block4.0
+    LAD_S2E_CASE(128, 64, 1)
+    LAD_S2E_CASE(32, 32, 9)
+    LAD_S2E_CASE(32, 32, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_s2_fwd_eval: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 

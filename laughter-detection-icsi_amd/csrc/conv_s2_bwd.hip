@@ -50,6 +50,16 @@ __device__ __forceinline__ uint32_t udiv_f64(uint32_t n, uint32_t d, double inv,
     return qt;
 }
 
+// Fragments of one tap requested before their MFMAs: all of them where that is at most 24 float4 (every resnet_base layer), else
+// GC groups of 8 channels at a time (GC the largest power of two within 24 float4): the data gradient into 128 channels held
+// 160 registers of fragments otherwise.  The MFMAs run in the same order either way.
+template <int G, int NT>
+struct S2Chunk {
+    static constexpr int cap(int g) { return (g > 1 && g * (1 + NT) > 24) ? cap(g / 2) : g; }
+    static constexpr int GC = cap(G);
+    static_assert(G % GC == 0, "chunks of whole 8-channel groups");
+};
+
 // KC = channels of dout (the conv's cout), NC = channels of dx (the conv's cin)
 // SC (3x3 only): the 1x1 stride-2 shortcut's data gradient dx[2yo, 2xo] += dout_sc[yo, xo] * W_sc lands exactly on parity
 // class (0, 0), whose positions take ONE tap of the 3x3 from the same low-resolution position: one more tap for that class
@@ -77,6 +87,7 @@ __global__ __launch_bounds__(THREADS, 2) void dgrad_s2_kernel(const float *__res
     constexpr int NP = NTl<NC>::NP;
     constexpr int K4 = KC / 4;
     constexpr int G = KC / 8;
+    constexpr int GC = S2Chunk<G, NT>::GC;
     constexpr int LDO = NC + 4;
     __shared__ __attribute__((aligned(16))) float out_s[TM * LDO];
     __shared__ int qrow_s[TM];  // full-resolution row of each of the tile's outputs, -1 past the end of the class
@@ -129,23 +140,26 @@ __global__ __launch_bounds__(THREADS, 2) void dgrad_s2_kernel(const float *__res
         // mode-1 image: tap slot t' holds w[.., taps-1-t'], so the unflipped tap (ky,kx) sits at slot 8 - (3 ky + kx)
         const int slot = (TAPS == 9) ? 8 - (3 * ky + kx) : 0;
         const float *wp = sc_tap ? wt_sc + (gk * NP + i) * 4 : w_base + slot * (K4 * NP * 4);
-        float4 av[G], bv[G][NT];  // the whole tap's fragments requested together, then its MFMAs
+        float4 av[G], bv[G][NT];  // the tap's fragments requested together (GC groups at a time), then their MFMAs
 #pragma unroll
-        for (int c8 = 0; c8 < G; ++c8) {
-            av[c8] = *reinterpret_cast<const float4 *>(ap + c8 * 8);
+        for (int g0 = 0; g0 < G; g0 += GC) {
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bv[c8][n] = *reinterpret_cast<const float4 *>(wp + (c8 * 2 * NP + n * 32) * 4);
-        }
+            for (int c8 = g0; c8 < g0 + GC; ++c8) {
+                av[c8] = *reinterpret_cast<const float4 *>(ap + c8 * 8);
 #pragma unroll
-        for (int c8 = 0; c8 < G; ++c8) {
+                for (int n = 0; n < NT; ++n) bv[c8][n] = *reinterpret_cast<const float4 *>(wp + (c8 * 2 * NP + n * 32) * 4);
+            }
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].x, bv[c8][n].x, acc[n]);
+            for (int c8 = g0; c8 < g0 + GC; ++c8) {
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].y, bv[c8][n].y, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].x, bv[c8][n].x, acc[n]);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].z, bv[c8][n].z, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].y, bv[c8][n].y, acc[n]);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].w, bv[c8][n].w, acc[n]);
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].z, bv[c8][n].z, acc[n]);
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[n] = mfma32(av[c8].w, bv[c8][n].w, acc[n]);
+            }
         }
     }
     // ---- transpose through LDS (wave-private region), then whole rows of dx ----------------------------------------
@@ -222,9 +236,14 @@ __global__ __launch_bounds__(THREADS, 2) void dgrad_s2_kernel(const float *__res
 constexpr int MAX_GROUPS = 768;   // persistent workgroups (38 KB of LDS at 64 channels x 46 columns: 3 per CU)
 constexpr int W2_PRE = 10;        // float4 registers per thread for the next tile's input span (3*Wp_hi*CIN/4 <= 2560)
 
+// 128 input channels (resnet_with_augmentation, block2.0): the input span of a tile does not fit the staging registers, so a
+// workgroup takes a slice of CS = 32 input channels (blockIdx.y = slice) and every slice writes its own rows of the workgroup's
+// slab: the slab sums stay the fixed-order sums.  (Two such workgroups per CU: at three, the slice addressing spills.)
 template <int CIN, int COUT, int TAPS>
 struct W2Cfg {
-    static constexpr int MT = (CIN + 31) / 32, NT = (COUT + 31) / 32, MN = MT * NT;
+    static constexpr int CS = CIN > 64 ? 32 : CIN;   // input channels per slice
+    static constexpr int NSLICE = CIN / CS;
+    static constexpr int MT = (CS + 31) / 32, NT = (COUT + 31) / 32, MN = MT * NT;
     static constexpr int TSTRIDE = (MN >= 4) ? 1 : 4 / MN;
     static constexpr int TPW = (TAPS + TSTRIDE - 1) / TSTRIDE;
 };
@@ -235,23 +254,28 @@ struct W2Cfg {
 // the odd taps has a free accumulator slot (9 taps over 2 or 4 tap-owners).  On its own that gradient was a launch that
 // staged three image rows per tile to use one (173 us at 64 -> 32, batch 512, for 1/9 of the 3x3's arithmetic).
 template <int CIN, int COUT, int TAPS, bool SC = false>
-__global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__restrict__ in, const float *__restrict__ dout,
+__global__ __launch_bounds__(THREADS, (W2Cfg<CIN, COUT, TAPS>::NSLICE > 1 ? 2 : 3)) void wgrad_s2_kernel(const float *__restrict__ in, const float *__restrict__ dout,
                                                               float *__restrict__ slabs, float *__restrict__ bias_slabs, Geom ghi,
                                                               Geom glo, int64_t n_tiles, int Ho,
                                                               const float *__restrict__ dout_sc = nullptr,
                                                               float *__restrict__ slabs_sc = nullptr) {
     static_assert(!SC || TAPS == 9, "the shortcut rides with the 3x3 convolution");
     using C = W2Cfg<CIN, COUT, TAPS>;
-    constexpr int CI4 = CIN / 4, CO4 = COUT / 4;
+    static_assert(!SC || C::NSLICE == 1, "the fused shortcut is for unsliced layers");
+    constexpr int CS = C::CS;
+    constexpr int CI4 = CS / 4, CO4 = COUT / 4;
+    static_assert(THREADS % CI4 == 0, "a staging register covers whole rows of the slice");
     constexpr int BPARTS = THREADS / COUT;
     extern __shared__ float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, gk = lane >> 5;
+    const int ci0 = (C::NSLICE == 1) ? 0 : (int)blockIdx.y * CS;   // this workgroup's input channels ci0 .. ci0 + CS
+    if (ci0 != 0) bias_slabs = nullptr;                              // (summed by the first slice)
     const int KR = (glo.Wp + 1) & ~1;                 // k rows per tile (even); row Wp_lo, if present, is a zero row
     const int span = 3 * ghi.Wp + 1;                  // 3 image rows + the border position that follows them (shared borders)
     const int nin = span * CI4;                       // float4 of the input span
-    float *in_s = smem;                               // [span][CIN]
-    float *do_s = in_s + span * CIN;                  // [KR][COUT] (+32 slack for the padded MFMA columns)
+    float *in_s = smem;                               // [span][CS]
+    float *do_s = in_s + span * CS;                   // [KR][COUT] (+32 slack for the padded MFMA columns)
     float *bred_s = do_s + KR * COUT + 32;            // [BPARTS][COUT]
     float *do2_s = bred_s + THREADS;                  // SC: [KR][COUT] (+32 slack)
     const int mn = wave % C::MN;
@@ -268,14 +292,18 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__res
     for (int j = 0; j < C::TPW; ++j) {
         const int tap = tap0 + j * C::TSTRIDE;
         // 3x3 pad 1: padded input (2yo + ky, 2xo + kx);  1x1 pad 0: padded input (2yo + 1, 2xo + 1)
-        toff[j] = ((TAPS == 9 && tap < TAPS) ? (tap / 3) * ghi.Wp + (tap % 3) : ghi.Wp + 1) * CIN;
+        toff[j] = ((TAPS == 9 && tap < TAPS) ? (tap / 3) * ghi.Wp + (tap % 3) : ghi.Wp + 1) * CS;
     }
     float bsum = 0.0f;
     const int bco = tid % COUT, bpart = tid / COUT;
 
     // the wave whose last slot is "tap 9": it owns the shortcut (toff of a slot past the 3x3 taps is the centre tap's)
     const bool sc_wave = SC && (tap0 + (C::TPW - 1) * C::TSTRIDE == TAPS);
-    float4 pin[W2_PRE], pdo, pdo2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // dout rows of a tile: KR x COUT / 4 float4, one register per thread up to 32 channels; at 64 channels (block2.0 of
+    // resnet_with_augmentation: 23 low-resolution columns) two
+    constexpr int NPDO = COUT >= 64 ? 2 : 1;
+    static_assert(!SC || NPDO == 1, "the fused shortcut is for layers of at most 32 output channels");
+    float4 pin[W2_PRE], pdo[NPDO], pdo2 = make_float4(0.f, 0.f, 0.f, 0.f);
     auto fetch = [&](int64_t tile) {
         const int64_t b = tile / Ho;
         const int yo = (int)(tile - b * Ho);
@@ -284,11 +312,18 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__res
         for (int u = 0; u < W2_PRE; ++u) {
             const int f = u * THREADS + tid;
             pin[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (f < nin) pin[u] = src[f];
+            if constexpr (C::NSLICE == 1) {
+                if (f < nin) pin[u] = src[f];
+            } else {   // float4 f of the slice: row f / CI4, channels ci0 + 4 (f % CI4) ..
+                if (f < nin) pin[u] = src[ci0 / 4 + (u * (THREADS / CI4) + tid / CI4) * (CIN / 4) + tid % CI4];
+            }
         }
         const float4 *dsrc = reinterpret_cast<const float4 *>(dout + ((b * glo.Hp + yo + 1) * (int64_t)glo.Wp) * COUT);
-        pdo = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tid < glo.Wp * CO4) pdo = dsrc[tid];
+#pragma unroll
+        for (int u = 0; u < NPDO; ++u) {
+            pdo[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u * THREADS + tid < glo.Wp * CO4) pdo[u] = dsrc[u * THREADS + tid];
+        }
         if (SC) {
             const float4 *dsrc2 = reinterpret_cast<const float4 *>(dout_sc + ((b * glo.Hp + yo + 1) * (int64_t)glo.Wp) * COUT);
             pdo2 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -308,7 +343,7 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__res
             const float b = b_base[xpo * COUT];
             // column 2*xo of the input row; clamped for the (zero) border / padding k rows so the read stays inside the span
             const int c0 = min(max(2 * (xpo - 1), 0), ghi.Wp - 2);
-            const float *arow = a_base + c0 * CIN;
+            const float *arow = a_base + c0 * CS;
 #pragma unroll
             for (int j = 0; j < NTAPS; ++j) acc[j] = mfma32(arow[toff[j]], b, acc[j]);
             if constexpr (WITH_SC) acc[NTAPS] = mfma32(arow[toff[NTAPS]], b2_base[xpo * COUT], acc[NTAPS]);
@@ -323,7 +358,9 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__res
             const int f = u * THREADS + tid;
             if (f < nin) reinterpret_cast<float4 *>(in_s)[f] = pin[u];
         }
-        if (tid < KR * CO4) reinterpret_cast<float4 *>(do_s)[tid] = pdo;  // rows >= Wp_lo were fetched as zero
+#pragma unroll
+        for (int u = 0; u < NPDO; ++u)   // rows >= Wp_lo were fetched as zero
+            if (u * THREADS + tid < KR * CO4) reinterpret_cast<float4 *>(do_s)[u * THREADS + tid] = pdo[u];
         if (SC && tid < KR * CO4) reinterpret_cast<float4 *>(do2_s)[tid] = pdo2;
         __syncthreads();
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);
@@ -346,7 +383,7 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad_s2_kernel(const float *__res
             for (int r = 0; r < 16; ++r) {
                 const int ci = mt * 32 + acc_row(r, lane);
                 const int co = nt * 32 + i;
-                if (ci < CIN && co < COUT) slab[(tap * CIN + ci) * COUT + co] = acc[j][r];
+                if (ci < CS && co < COUT) slab[(tap * CIN + ci0 + ci) * COUT + co] = acc[j][r];
             }
         }
     }
@@ -391,11 +428,12 @@ int launch_wgrad(const float *in, const float *dout, float *ws, float *dw, float
     const Geom ghi = mk(batch, H, W), glo = mk(batch, (H + 1) / 2, (W + 1) / 2);
     const int Ho = (H + 1) / 2;
     const int64_t n_tiles = batch * Ho;
-    const int groups = (int)std::min<int64_t>(MAX_GROUPS, n_tiles);
+    using C = W2Cfg<CIN, COUT, TAPS>;
+    const int groups = (int)std::max<int64_t>(1, std::min<int64_t>(MAX_GROUPS / C::NSLICE, n_tiles));
     const int KR = (glo.Wp + 1) & ~1;
-    if ((3 * ghi.Wp + 1) * (CIN / 4) > W2_PRE * THREADS || KR * (COUT / 4) > THREADS)
+    if ((3 * ghi.Wp + 1) * (C::CS / 4) > W2_PRE * THREADS || KR * (COUT / 4) > (COUT >= 64 ? 2 : 1) * THREADS)
         return lad::fail(LAD_ERR_INVALID, "wgrad_s2: image too wide for the tile (W = %d)", W);
-    const size_t lds = ((size_t)(3 * ghi.Wp + 1) * CIN + (size_t)KR * COUT + 32 + THREADS + (SC ? (size_t)KR * COUT + 32 : 0)) * sizeof(float);
+    const size_t lds = ((size_t)(3 * ghi.Wp + 1) * C::CS + (size_t)KR * COUT + 32 + THREADS + (SC ? (size_t)KR * COUT + 32 : 0)) * sizeof(float);
     static lad::DeviceOnce attr_set;
     if (!attr_set) {
         LAD_HIP_CHECK(hipFuncSetAttribute((const void *)wgrad_s2_kernel<CIN, COUT, TAPS, SC>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -404,7 +442,7 @@ int launch_wgrad(const float *in, const float *dout, float *ws, float *dw, float
     }
     float *bias_slabs = ws + (int64_t)MAX_GROUPS * TAPS * CIN * COUT;
     float *slabs_sc = bias_slabs + (int64_t)MAX_GROUPS * COUT;   // SC: [groups][CIN][COUT]
-    hipLaunchKernelGGL((wgrad_s2_kernel<CIN, COUT, TAPS, SC>), dim3(groups), dim3(THREADS), lds, st, in, dout, ws,
+    hipLaunchKernelGGL((wgrad_s2_kernel<CIN, COUT, TAPS, SC>), dim3(groups, C::NSLICE), dim3(THREADS), lds, st, in, dout, ws,
                        dbias ? bias_slabs : nullptr, ghi, glo, n_tiles, Ho, dout_sc, slabs_sc);
     int rc = lad::check_launch("wgrad_s2_kernel");
     if (rc) return rc;
@@ -432,6 +470,10 @@ extern "C" int lad_conv_s2_dgrad(const float *dout, const float *wt, float *dx, 
     LAD_DG_CASE(64, 32, 1)
     LAD_DG_CASE(32, 16, 1)
     LAD_DG_CASE(16, 16, 1)
+    LAD_DG_CASE(128, 64, 9)   // resnet_with_augmentation: block2.0 (into 128 channels) and block4.0
+    LAD_DG_CASE(128, 64, 1)
+    LAD_DG_CASE(32, 32, 9)
+    LAD_DG_CASE(32, 32, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_s2_dgrad: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 
@@ -455,6 +497,10 @@ extern "C" int lad_conv_s2_wgrad(const float *in, const float *dout, float *work
     LAD_WG2_CASE(64, 32, 1)
     LAD_WG2_CASE(32, 16, 1)
     LAD_WG2_CASE(16, 16, 1)
+    LAD_WG2_CASE(128, 64, 9)   // resnet_with_augmentation: block2.0 (sliced, see W2Cfg) and block4.0
+    LAD_WG2_CASE(128, 64, 1)
+    LAD_WG2_CASE(32, 32, 9)
+    LAD_WG2_CASE(32, 32, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_s2_wgrad: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }
 

@@ -665,8 +665,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(HeadArgs a, Head
 
 int check_head(const HeadArgs &a) {
     using namespace lad;
-    LAD_REQUIRE(a.B >= 1 && a.F >= 1 && a.F <= MAX_F && a.F * HID <= 2 * HEAD_THREADS, "head: F must be 1..%d (got %d), B >= 1",
-                HEAD_THREADS * 2 / HID, a.F);
+    // (F = 128: resnet_with_augmentation on 128 x 44 windows.  The round-2 bound F * HID <= 2 * HEAD_THREADS came from a dW1 loop with two
+    // outputs per thread; the tiled dW1 stage that replaced it sizes its classes KS from F and the LDS meeting place.)
+    LAD_REQUIRE(a.B >= 1 && a.F >= 1 && a.F <= MAX_F, "head: F must be 1..%d (got %d), B >= 1", MAX_F, a.F);
     LAD_REQUIRE(a.g2 && a.b2 && a.rm2 && a.rv2 && a.W1 && a.bias1 && a.g3 && a.b3 && a.rm3 && a.rv3 && a.W2 && a.bias2,
                 "head: null parameter pointer");
     return LAD_OK;

@@ -27,10 +27,20 @@ constexpr int NWAVES = THREADS / 64;
 constexpr int TMW = 64;          // rows per tile
 constexpr int MAX_GROUPS = 512;  // persistent workgroups (2 per CU)
 
+// Channels past 64 (the resnet_with_augmentation widths: 64 -> 128, 128 -> 128) are sliced: a workgroup owns CS = 64 input
+// channels x COS = 32 output channels of the weight gradient (blockIdx.y = slice) -- the shape of the 64 -> 32 layer: two (ci tile,
+// co tile) pairs, each shared by two wavefronts that split the taps (five accumulators each, 48 KB of LDS, three workgroups per
+// CU) -- and stages those channels of the input and dout rows.  The unsliced 128-channel tile would hold 16 pairs over 4 wavefronts
+// in ~112 KB of LDS; 64 x 64 slices (nine accumulators per wavefront) spill.  Every slice writes its own part of the workgroup's
+// slab, so the slab sums (slab_reduce.hip) are the same fixed-order sums.
 template <int CIN, int COUT, int TAPS>
 struct WgCfg {
-    static constexpr int MT = (CIN + 31) / 32;
-    static constexpr int NT = (COUT + 31) / 32;
+    static constexpr int CS = CIN > 64 ? 64 : CIN;       // input channels per slice
+    static constexpr int COS = COUT > 64 ? 32 : COUT;    // output channels per slice
+    static constexpr int NCI = CIN / CS, NCO = COUT / COS;
+    static constexpr int NSLICE = NCI * NCO;
+    static constexpr int MT = (CS + 31) / 32;
+    static constexpr int NT = (COS + 31) / 32;
     static constexpr int MN = MT * NT;          // 1, 2 or 4 distinct (mt, nt) pairs
     static constexpr int TSTRIDE = NWAVES / MN; // wavefronts that share one (mt, nt) split the taps
     static constexpr int TPW = (TAPS + TSTRIDE - 1) / TSTRIDE;  // accumulator tiles per wavefront
@@ -50,17 +60,23 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
                                                            float *__restrict__ slabs, float *__restrict__ bias_slabs,
                                                            Geom g, int64_t n_tiles) {
     using C = WgCfg<CIN, COUT, TAPS>;
-    constexpr int CI4 = CIN / 4, CO4 = COUT / 4;
-    constexpr int BPARTS = THREADS / COUT;
+    // this workgroup's slice: input channels ci0 .. ci0 + CS, output channels co0 .. co0 + COS (the whole layer below 128 channels)
+    constexpr int CS = C::CS, COS = C::COS;
+    constexpr int CI4 = CS / 4, CO4 = COS / 4;
+    constexpr int BPARTS = THREADS / COS;
     constexpr int NPD = (TMW * CO4 + THREADS - 1) / THREADS;
+    static_assert(THREADS % CI4 == 0 && THREADS % CO4 == 0, "a staging register covers whole rows of the slice");
     extern __shared__ float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, gk = lane >> 5;
+    const int ci0 = (C::NSLICE == 1) ? 0 : (int)(blockIdx.y / C::NCO) * CS;
+    const int co0 = (C::NSLICE == 1) ? 0 : (int)(blockIdx.y % C::NCO) * COS;
+    if (ci0 != 0) bias_slabs = nullptr;   // (the bias gradient of a column slice is summed by its first row slice)
     const int halo = (TAPS == 9) ? g.Wp + 1 : 0;
     const int nrows = TMW + 2 * halo;
-    float *in_s = smem;                                  // [nrows][CIN] (+32 slack)
-    float *do_s = in_s + nrows * CIN + 32;               // [TMW][COUT]  (+32 slack)
-    float *bred_s = do_s + TMW * COUT + 32;              // [BPARTS][COUT]
+    float *in_s = smem;                                  // [nrows][CS] (+32 slack)
+    float *do_s = in_s + nrows * CS + 32;                // [TMW][COS]  (+32 slack)
+    float *bred_s = do_s + TMW * COS + 32;               // [BPARTS][COS]
 
     const int mn = wave % C::MN;
     const int mt = mn / C::NT, nt = mn % C::NT;
@@ -76,11 +92,11 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
     for (int j = 0; j < C::TPW; ++j) {
         const int tap = tap0 + j * C::TSTRIDE;
         const int sh = (TAPS == 9 && tap < TAPS) ? ((tap / 3 - 1) * g.Wp + (tap % 3 - 1)) : 0;
-        aoff[j] = (gk + halo + sh) * CIN + mt * 32 + i;
+        aoff[j] = (gk + halo + sh) * CS + mt * 32 + i;
     }
-    const int boff = gk * COUT + nt * 32 + i;
+    const int boff = gk * COS + nt * 32 + i;
     float bsum = 0.0f;
-    const int bco = tid % COUT, bpart = tid / COUT;
+    const int bco = tid % COS, bpart = tid / COS;
     const int nfi = nrows * CI4;
 
     // Software pipeline over this workgroup's tiles: the rows of tile t+1 travel HBM -> registers while the MFMAs of
@@ -94,12 +110,25 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
         const int64_t qb = q0 - halo;  // tensor row of staged row 0 (negative in the first tiles)
         const int64_t first = qb < 0 ? 0 : qb;
         const int skip = (int)(first - qb) * (CIN * 4);
-        const __amdgpu_buffer_rsrc_t in_r = make_rsrc(in + first * CIN, (g.rows - first) * (CIN * 4));
+        if constexpr (C::NSLICE == 1) {
+            const __amdgpu_buffer_rsrc_t in_r = make_rsrc(in + first * CIN, (g.rows - first) * (CIN * 4));
 #pragma unroll
-        for (int u = 0; u < WG_PRE_IN; ++u) pin[u] = buf_load16(in_r, (u * THREADS + tid) * 16 - skip);
-        const __amdgpu_buffer_rsrc_t do_r = make_rsrc(dout + q0 * COUT, (g.rows - q0) * (COUT * 4));
+            for (int u = 0; u < WG_PRE_IN; ++u) pin[u] = buf_load16(in_r, (u * THREADS + tid) * 16 - skip);
+            const __amdgpu_buffer_rsrc_t do_r = make_rsrc(dout + q0 * COUT, (g.rows - q0) * (COUT * 4));
 #pragma unroll
-        for (int u = 0; u < NPD; ++u) pdo[u] = buf_load16(do_r, (u * THREADS + tid) * 16);
+            for (int u = 0; u < NPD; ++u) pdo[u] = buf_load16(do_r, (u * THREADS + tid) * 16);
+        } else {
+            // a slice: the resources start at its first channel; float4 u * THREADS + tid is row (u * THREADS + tid) / CI4 of it
+            // (THREADS is a multiple of CI4), channels 4 (tid % CI4) ..
+            const __amdgpu_buffer_rsrc_t in_r = make_rsrc(in + first * CIN + ci0, (g.rows - first) * (CIN * 4) - ci0 * 4);
+            const int in_lane = (tid / CI4) * (CIN * 4) + (tid % CI4) * 16 - skip;
+#pragma unroll
+            for (int u = 0; u < WG_PRE_IN; ++u) pin[u] = buf_load16(in_r, in_lane + u * (THREADS / CI4) * (CIN * 4));
+            const __amdgpu_buffer_rsrc_t do_r = make_rsrc(dout + q0 * COUT + co0, (g.rows - q0) * (COUT * 4) - co0 * 4);
+            const int do_lane = (tid / CO4) * (COUT * 4) + (tid % CO4) * 16;
+#pragma unroll
+            for (int u = 0; u < NPD; ++u) pdo[u] = buf_load16(do_r, do_lane + u * (THREADS / CO4) * (COUT * 4));
+        }
     };
     int64_t tile = blockIdx.x;
     if (tile < n_tiles) fetch(tile);
@@ -127,15 +156,15 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
         WG_T(t4)
         if (bias_slabs != nullptr) {
 #pragma unroll 4
-            for (int r = bpart; r < TMW; r += BPARTS) bsum += do_s[r * COUT + bco];
+            for (int r = bpart; r < TMW; r += BPARTS) bsum += do_s[r * COS + bco];
         }
 #pragma unroll
         for (int k = 0; k < TMW; k += 2) {  // fully unrolled: every LDS address is a per-kernel base + an immediate
-            const float b = do_s[k * COUT + boff];
+            const float b = do_s[k * COS + boff];
 #pragma unroll
             for (int j = 0; j < C::TPW; ++j) {
                 if (C::TSTRIDE == 1 || tap0 + j * C::TSTRIDE < TAPS) {
-                    const float a = in_s[k * CIN + aoff[j]];
+                    const float a = in_s[k * CS + aoff[j]];
                     acc[j] = mfma32(a, b, acc[j]);
                 }
             }
@@ -162,18 +191,18 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
             for (int r = 0; r < 16; ++r) {
                 const int ci = mt * 32 + acc_row(r, lane);
                 const int co = nt * 32 + i;
-                if (ci < CIN && co < COUT) slab[(tap * CIN + ci) * COUT + co] = acc[j][r];
+                if (ci < CS && co < COS) slab[(tap * CIN + ci0 + ci) * COUT + co0 + co] = acc[j][r];
             }
         }
     }
     if (bias_slabs != nullptr) {
         __syncthreads();
-        bred_s[bpart * COUT + bco] = bsum;
+        bred_s[bpart * COS + bco] = bsum;
         __syncthreads();
-        if (tid < COUT) {
+        if (tid < COS) {
             float s = 0.0f;
-            for (int p = 0; p < BPARTS; ++p) s += bred_s[p * COUT + tid];
-            bias_slabs[(int64_t)blockIdx.x * COUT + tid] = s;
+            for (int p = 0; p < BPARTS; ++p) s += bred_s[p * COS + tid];
+            bias_slabs[(int64_t)blockIdx.x * COUT + co0 + tid] = s;
         }
     }
 }
@@ -1107,12 +1136,14 @@ int launch_wgrad_b3(const float *in, const float *in_coef, const float *dout, fl
 
 template <int CIN, int COUT, int TAPS>
 int launch_wgrad(const float *in, const float *dout, float *ws, float *dw, float *dbias, const Geom &g, hipStream_t st) {
+    using C = WgCfg<CIN, COUT, TAPS>;
     const int64_t n_tiles = lad::ceil_div(g.rows, TMW);
-    const int groups = groups_for(n_tiles);
+    // sliced layers: the slices of one slab share MAX_GROUPS / NSLICE persistent rows of workgroups (as many resident in all)
+    const int groups = (int)std::max<int64_t>(1, std::min<int64_t>(MAX_GROUPS / C::NSLICE, n_tiles));
     const int halo = (TAPS == 9) ? g.Wp + 1 : 0;
     const int nrows = TMW + 2 * halo;
-    const size_t lds = ((size_t)nrows * CIN + 32 + TMW * COUT + 32 + THREADS) * sizeof(float);
-    if (lds > 160 * 1024 || (int64_t)nrows * (CIN / 4) > (int64_t)WG_PRE_IN * THREADS)
+    const size_t lds = ((size_t)nrows * C::CS + 32 + TMW * C::COS + 32 + THREADS) * sizeof(float);
+    if (lds > 160 * 1024 || (int64_t)nrows * (C::CS / 4) > (int64_t)WG_PRE_IN * THREADS)
         return lad::fail(LAD_ERR_INVALID, "wgrad: image too wide for the tile (W = %d)", g.Wp - 1);
     static lad::DeviceOnce attr_set;
     if (!attr_set) {
@@ -1122,7 +1153,7 @@ int launch_wgrad(const float *in, const float *dout, float *ws, float *dw, float
     }
     float *slabs = ws;
     float *bias_slabs = ws + (int64_t)MAX_GROUPS * TAPS * CIN * COUT;
-    hipLaunchKernelGGL((wgrad_kernel<CIN, COUT, TAPS>), dim3(groups), dim3(THREADS), lds, st, in, dout, slabs,
+    hipLaunchKernelGGL((wgrad_kernel<CIN, COUT, TAPS>), dim3(groups, C::NSLICE), dim3(THREADS), lds, st, in, dout, slabs,
                        dbias ? bias_slabs : nullptr, g, n_tiles);
     int rc = lad::check_launch("wgrad_kernel");
     if (rc) return rc;
@@ -1244,5 +1275,8 @@ extern "C" int lad_conv_wgrad(const float *in, const float *dout, float *workspa
     LAD_WG_CASE(64, 32, 1)
     LAD_WG_CASE(32, 16, 1)
     LAD_WG_CASE(16, 16, 1)
+    LAD_WG_CASE(128, 128, 9)   // resnet_with_augmentation: block1 (sliced, see WgCfg)
+    LAD_WG_CASE(64, 128, 9)
+    LAD_WG_CASE(64, 128, 1)
     return fail(LAD_ERR_INVALID, "lad_conv_wgrad: unsupported (cin=%d, cout=%d, taps=%d)", cin, cout, taps);
 }

@@ -99,10 +99,11 @@ class LadDataset(torch.utils.data.Dataset):
 class InferenceDataset(torch.utils.data.Dataset):
     """Stride-one-frame windows over the features of a whole file (datasets.py:72-93)."""
 
-    def __init__(self, feats, n_frames=cfg.FEAT['num_samples']) -> None:
+    def __init__(self, feats, n_frames=None) -> None:
         super().__init__()
         self.feats = feats
-        self.n_frames = n_frames
+        # (read when the dataset is made, not when this module is imported: a caller may set FEAT['num_samples'] = 128 first)
+        self.n_frames = cfg.FEAT['num_samples'] if n_frames is None else n_frames
 
     def __len__(self):
         return len(self.feats)

@@ -27,6 +27,9 @@ _VP = ctypes.c_void_p
 # launches, and 8192 windows amortise them better than 2048 did (2.03 -> 2.28 M windows/s on the 60 min channel); f32 keeps
 # every window's level-1 activation (1.2 MB), so its groups stay at 2048
 PREDICT_CHUNK = {"fp16": 8192, "fp32": 2048}
+# the stage widths every kernel and fusion of the library is instantiated for (config.MODEL_MAP['resnet_base']); other widths run on the
+# exact-f32 kernels (ResNetEngine.base_widths)
+BASE_WIDTHS = (64, 32, 16, 16)
 # fp16: windows whose level-1 / level-2 frame streams are computed in one go (engine.stream_super): five tensors of 5.8 KB per frame at
 # level 1 -- 10 GB for a 60-minute channel's 360,000 windows, 30 GB at this cap
 STREAM_SUPER_MAX = 1 << 20
@@ -160,6 +163,14 @@ class ResNetEngine:
         self._side_pending = False
         self.debug_capture = None  # tools/: dict that receives clones of the backward intermediates per block
         self.kernel_events = None  # bench.py: {kernel label: [(start_event, end_event), ...]} when profiling is on
+        # Stage widths other than resnet_base's (resnet_with_augmentation: [128, 64, 32, 32] on 128 x 44 windows) run on the exact-f32
+        # MFMA kernels only: every split-operand path, sign-bit path and fusion above was validated on the resnet_base layer graph
+        # alone and is switched off (the layer flags b3 / s2b3 in _build_specs follow), and so is fp16 inference (no half-precision
+        # kernels at 128 channels: predict_windows raises).
+        self.base_widths = list(model.filter_sizes) == list(BASE_WIDTHS)
+        if not self.base_widths:
+            for k in self.KERNEL_OPTIONS:
+                setattr(self, k, False)
 
     # ------------------------------------------------------------------------------------ flat storage
     def lib(self):
@@ -258,7 +269,7 @@ class ResNetEngine:
             s.wt_d = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(cout, cin, taps, 1)), device=dev)
             # b3: forward and data gradient on the split-operand kernel (64 or 32 channels); b3_full: 64 channels, where the
             # weight gradient, the sign bits and the virtual activation exist as well
-            s.b3 = cin == cout and cin in (64, 32) and taps == 9 and stride == 1 and w <= 46
+            s.b3 = cin == cout and cin in (64, 32) and taps == 9 and stride == 1 and w <= 46 and self.base_widths
             s.b3_full = s.b3 and cin == 64
             s.b3_wgrad = s.b3 and (cin == 64 or w <= 30)   # the 32-channel weight-gradient window holds 64 rows + 2 (W + 2)
             if s.b3:  # split (bf16 x 3) weight images, forward and data gradient
@@ -269,7 +280,7 @@ class ResNetEngine:
                 s.wt2_f = torch.zeros(nb2, device=dev, dtype=torch.uint8)
                 s.wt2_d = torch.zeros(nb2, device=dev, dtype=torch.uint8)
             # the 64 -> 32 stride-2 transition with its shortcut: one split image per direction (3x3 + 1x1 together)
-            s.s2b3 = cin == 64 and cout == 32 and taps == 9 and stride == 2 and (w + 1) // 2 <= 45
+            s.s2b3 = cin == 64 and cout == 32 and taps == 9 and stride == 2 and (w + 1) // 2 <= 45 and self.base_widths
             if s.s2b3:
                 s.wt3_s2f = torch.zeros(int(self.lib().lad_conv_s2b3_packed_weight_bytes()), device=dev, dtype=torch.uint8)
                 s.wt3_s2d = torch.zeros(int(self.lib().lad_conv_s2b3_dgrad_packed_weight_bytes()), device=dev, dtype=torch.uint8)
@@ -370,7 +381,8 @@ class ResNetEngine:
         for b in blocks:   # the stride-2 data gradient on the split-operand path writes its BatchNorm sums per parity class
             if getattr(b.conv1, "s2b3", False):
                 max_tiles = max(max_tiles, int(lib.lad_conv_s2b3_dgrad_partials(B, b.conv1.h_in, b.conv1.w_in)))
-        p["partials"] = torch.zeros(max_tiles * 2 * 64, device=dev)
+        cmax = max([64] + [b.conv1.cout for b in blocks])   # (128 at the resnet_with_augmentation widths)
+        p["partials"] = torch.zeros(max_tiles * 2 * cmax, device=dev)
         p["partials_sc"] = torch.zeros(max(int(lib.lad_conv_num_tiles(B, b.conv1.h_out, b.conv1.w_out)) * 2 * b.conv1.cout
                                            for b in blocks if b.sc_conv is not None) if any(b.sc_conv is not None for b in blocks) else 0,
                                        device=dev)
@@ -429,8 +441,8 @@ class ResNetEngine:
                             n = int(lib.lad_conv_s2_wgrad_fused_workspace_floats(cs.cin, cs.cout)) if cs.taps == 9 else \
                                 int(lib.lad_conv_s2_wgrad_workspace_floats(cs.cin, cs.cout, cs.taps))
                         p["wgrad_ws_of"][cs.name] = torch.zeros(n, device=dev)
-            p["bn_ws"] = torch.zeros(int(lib.lad_bn_bwd_workspace_floats(64)), device=dev)
-            p["bcoef"] = torch.zeros(8 * 64, device=dev)
+            p["bn_ws"] = torch.zeros(int(lib.lad_bn_bwd_workspace_floats(cmax)), device=dev)
+            p["bcoef"] = torch.zeros(8 * cmax, device=dev)
         self._plans[key] = p
         return p
 
@@ -956,10 +968,17 @@ class ResNetEngine:
                    "lad_head_fwd_eval")
         return probs
 
+    def _require_half(self):
+        if not self.base_widths:
+            raise ValueError(f"precision 'fp16' runs the stage widths {list(BASE_WIDTHS)} (resnet_base) only; this model has "
+                             f"{list(self.model.filter_sizes)}: use precision 'fp32'")
+
     def _forward_eval_any(self, half, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats=0):
         """Eval-mode forward of B images taken from a (frames, W) feature matrix (see lad_stem_fwd_eval): every BatchNorm is
         folded into the epilogue of the convolution in front of it, so the whole model is stem + 19 convolution launches +
         pool + head.  half: activations / weights in fp16 on the 16-bit matrix cores (csrc/conv_f16.hip), f32 in and out."""
+        if half:
+            self._require_half()
         p = self._plan_eval(B, H, W, torch.float16 if half else torch.float32)
         blocks = p["blocks"]
         self._eval_prepare(blocks, half)
@@ -1346,6 +1365,8 @@ class ResNetEngine:
         if precision not in ("fp32", "fp16"):
             raise ValueError("precision must be 'fp32' or 'fp16'")
         half = precision == "fp16"
+        if half:
+            self._require_half()
         chunk = PREDICT_CHUNK[precision] if chunk is None else chunk
         self.ensure_flat()
         _hip.require_cuda(feats, "feats", torch.float32)
@@ -1599,6 +1620,14 @@ class ResNetEngine:
                 if not fuse1:
                     self._wgrad(p, c1s, a["x"], dc1, B, hi, wi)
                 dx = dy  # dy is dead after the first bn_bwd; never aliases dc1 / aux
+                if b.sc_conv is not None:
+                    # a stride-1 projection shortcut (resnet_with_augmentation's block1.0, 64 -> 128): aux is the gradient into its
+                    # BatchNorm's input; the 1x1 convolution's data gradient (into da1, dead since bn1's backward) becomes the
+                    # addend of conv1's data gradient below, its weight gradient reads aux
+                    sc = b.sc_conv
+                    self._wgrad(p, sc, a["x"], aux, B, hi, wi)
+                    self._dgrad_raw(sc, aux, None, da1, B, hi, wi)
+                    aux = da1
                 # who consumes dx: the bn2 of the block below (identity shortcut only: its sums need y and c2), or the stem bn
                 if bi == 0:
                     stat = None  # the stem's convolution output is not kept: its BatchNorm sums come from lad_stem_bn_bwd_sums

@@ -205,7 +205,7 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
 
 
 class InferenceLoader:
-    """Batches of <= batch_size stride-one-frame windows, (n, 100, F) GPU float32 (DataLoader(batch_size=32))."""
+    """Batches of <= batch_size stride-one-frame windows, (n, FEAT['num_samples'], F) GPU float32 (DataLoader(batch_size=32))."""
 
     def __init__(self, dataset, batch_size=32):
         self.dataset, self.batch_size = dataset, batch_size

@@ -60,7 +60,8 @@ def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32
     feats = loader.dataset.feats
     T = feats.shape[0]
     sh = parallel.shard_indices(T, rank, world)
-    local = model.engine.predict_windows(feats, chunk=chunk, start=sh.start, stop=sh.stop, precision=precision)
+    local = model.engine.predict_windows(feats, n_frames=loader.dataset.n_frames, chunk=chunk, start=sh.start, stop=sh.stop,
+                                         precision=precision)
     probs = parallel.gather_probs(local, T, rank, world)
     file_length = audio_utils.get_audio_length(audio_path)  # seconds; fps = T / file_length (segment_laughter.py:103-104)
     return probs.cpu().numpy(), file_length

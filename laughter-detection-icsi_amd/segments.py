@@ -11,17 +11,33 @@ Everything here is integer bookkeeping on the host (bit-exact by construction, t
 themselves are gathered on the GPU (csrc/gather.hip).
 """
 import csv
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
-FRAME_SHIFT = 0.01
+FRAME_SHIFT = 0.01        # the frame shift at the default FEAT['num_samples'] = 100 (configured_frame_shift() reads the configured one)
 MIN_SEG_DURATION = 1.0
 
 
-def seconds_to_frame(t, frame_shift=FRAME_SHIFT):
+def configured_frame_shift():
+    """Frame shift of the configured features, 1 / FEAT['num_samples'] (utils/utils.py:15 of the reference), read at call time:
+    0.01 at the default 100 frames per second, 1/128 s at the reference's original 128."""
+    import config
+    return 1.0 / config.FEAT['num_samples']
+
+
+def frames_per_segment():
+    """Frames of one MIN_SEG_DURATION segment at the configured frame shift (100, or 128 at FEAT['num_samples'] = 128)."""
+    return int(round(MIN_SEG_DURATION / configured_frame_shift()))
+
+
+def seconds_to_frame(t, frame_shift=None):
     """Frame index of a time stamp: round-half-even of t / frame_shift on the 2-decimal values of the data frames
-    (create_data_df.py:182 rounds every time to 2 decimals, so t / 0.01 is an integer up to float noise)."""
+    (create_data_df.py:182 rounds every time to 2 decimals, so t / 0.01 is an integer up to float noise).  frame_shift None: the
+    configured one (configured_frame_shift()).  At other frame shifts (1/128 s) the same rule applies; Lhotse's own time -> frame rounding of
+    such cuts is a restatement like the rest of this module, parity unpinned."""
+    if frame_shift is None:
+        frame_shift = configured_frame_shift()
     return int(round(round(float(t), 2) / frame_shift))
 
 
@@ -32,7 +48,7 @@ class SegmentTable:
     n_frames: np.ndarray     # int32 (N,)  <= frames_per_segment; the rest is padding
     label: np.ndarray        # int32 (N,)
     channels: list           # channel keys, e.g. "Bmr021/chan3.sph"
-    frames_per_segment: int = 100
+    frames_per_segment: int = field(default_factory=frames_per_segment)
 
     def __len__(self):
         return len(self.label)
@@ -50,8 +66,11 @@ class SegmentTable:
                             self.frames_per_segment)
 
 
-def table_from_rows(rows, min_seg_duration=MIN_SEG_DURATION, frame_shift=FRAME_SHIFT):
-    """rows: iterable of dicts with the data-frame columns -> SegmentTable (one segment per row, row order kept)."""
+def table_from_rows(rows, min_seg_duration=MIN_SEG_DURATION, frame_shift=None):
+    """rows: iterable of dicts with the data-frame columns -> SegmentTable (one segment per row, row order kept).
+    frame_shift None: 1 / FEAT['num_samples'] (configured_frame_shift())."""
+    if frame_shift is None:
+        frame_shift = configured_frame_shift()
     fps = int(round(min_seg_duration / frame_shift))
     chans, chan_idx = [], {}
     channel, first, count, label = [], [], [], []
@@ -80,11 +99,13 @@ def table_from_csv(path, **kw):
 
 
 def whole_track_table(n_frames_total, channel_key, laugh_intervals_ms=(), min_seg_duration=MIN_SEG_DURATION,
-                      frame_shift=FRAME_SHIFT):
+                      frame_shift=None):
     """Consecutive windows over one channel (compute_features.py:228-243): window w = [w, w+1) s; the last partial
     window is dropped; label 1 iff the open-closed interval (start_ms, end_ms] overlaps a laugh interval of the
     channel's participant.  laugh_intervals_ms: iterable of (lo_ms, hi_ms] integer pairs (the `portion` index of
     analysis/preprocess.py, in 1 ms frames)."""
+    if frame_shift is None:
+        frame_shift = configured_frame_shift()
     fps = int(round(min_seg_duration / frame_shift))
     n_win = n_frames_total // fps
     first = np.arange(n_win, dtype=np.int64) * fps
