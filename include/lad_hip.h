@@ -560,6 +560,37 @@ int lad_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, 
                   double beta2, double eps, int64_t step, const int64_t *step_counter, int32_t zero_grad,
                   float *norm_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Threshold sweep of a probability track on the device: run tables for K thresholds in one pass.
+ * Replaces the per-frame loop of get_laughter_instances (laugh_segmenter.py:74-111, with fix_over_underflow :57-71) up to
+ * the integer run table: p > 1 -> 1, p <= 0 -> 1e-7, else p (NaN included); frame i is on for threshold k iff
+ * (double)p[i] > thresholds[k], compared in float64 whatever the track's type; a table row is one maximal run
+ * (first_frame, last_frame), rows in ascending frame order.  first / fps, last / fps and the min_length filter stay with the
+ * caller.  Two steps, four launches whatever K and channels are, no atomics (identical bytes on every call):
+ *   lad_runs_count  -> workspace: int32 counts[channels * K] at its start (runs of channel c, threshold k at c * K + k);
+ *                      the caller copies them to the host to size the table
+ *   lad_runs_fill   -> table: int32[total][2], the (c, k) tables back to back in c * K + k order
+ * probs: float32 or float64 [channels][frames], contiguous.  thresholds: HOST double[n_thresholds].
+ * ---------------------------------------------------------------------------------------------- */
+enum lad_runs_dtype { LAD_RUNS_F32 = 0, LAD_RUNS_F64 = 1 };
+/* frames one wave handles (laugh_segmenter.py:74-111 has no such notion: the tests place their edge cases from it) */
+int32_t lad_runs_tile_frames(void);
+/* largest n_thresholds of one call (64; the evaluation sweep of laugh_segmenter.py:74-111 uses 29) */
+int32_t lad_runs_max_thresholds(void);
+/* bytes of workspace for lad_runs_count / lad_runs_fill (laugh_segmenter.py:74-111); needs no GPU.  -1 and lad_last_error() for
+ * channels outside 1..65535, frames outside 1..2^30 or n_thresholds outside 1..lad_runs_max_thresholds(). */
+int64_t lad_runs_workspace_bytes(int64_t channels, int64_t frames, int32_t n_thresholds);
+/* counting pass of laugh_segmenter.py:74-111 (three launches on `stream`); dtype: lad_runs_dtype */
+int lad_runs_count(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *thresholds,
+                   int32_t n_thresholds, void *workspace, void *stream);
+/* the run tables of laugh_segmenter.py:74-111 (one launch): same probs / thresholds / workspace as the lad_runs_count before it.
+ * counts_host: HOST int32[channels * n_thresholds], the counts the caller read back.  capacity_runs: rows `table` holds; if the
+ * counts sum to more, LAD_ERR_INVALID with lad_last_error() set and nothing is launched.  The kernel never writes a row at or
+ * beyond capacity_runs, whatever the workspace holds. */
+int lad_runs_fill(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *thresholds,
+                  int32_t n_thresholds, const void *workspace, const int32_t *counts_host, int32_t *table,
+                  int64_t capacity_runs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

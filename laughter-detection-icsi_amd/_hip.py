@@ -150,6 +150,13 @@ SIGNATURES = {
     "lad_grad_sumsq": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
     "lad_grad_accumulate": (c_int, [c_void_p, c_void_p, c_i64, c_double, c_void_p]),
     "lad_adam_step": (c_int, [c_void_p] * 4 + [c_i64, c_void_p] + [c_double] * 6 + [c_i64, c_void_p, c_i32, c_void_p, c_void_p]),
+    # threshold sweep of the probability track (csrc/runs.hip)
+    "lad_runs_tile_frames": (c_i32, []),
+    "lad_runs_max_thresholds": (c_i32, []),
+    "lad_runs_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "lad_runs_count": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p]),
+    "lad_runs_fill": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p,
+                              ctypes.POINTER(c_i32), c_void_p, c_i64, c_void_p]),
 }
 
 _lib = None

@@ -7,7 +7,13 @@ the evaluation sweeps, cluster_scripts/gen_eval_exp.py:30-36) is replaced by one
 threshold.  Integer run boundaries are bit-exact with the reference (tests/test_host_logic.py against vectors produced
 by the reference itself); this is host-side integer bookkeeping on a (T,) vector, not part of the GPU arithmetic.
 The Gillick-era MFCC code below laugh_segmenter.py:115 is dead in the reference and is not reproduced.
+
+`get_laughter_instances_device` / `get_laughter_frame_spans_device` are the opt-in device form of the same sweep for a track that
+is already in GPU memory (csrc/runs.hip: the run tables of all thresholds, and of several channels, in four launches): only the
+compact tables cross to the host, and the dictionary is the host function's bit for bit.  They have no CPU fallback.
 """
+import ctypes
+
 import numpy as np
 
 
@@ -92,3 +98,76 @@ def format_outputs(instances, wav_paths=None):
 def get_laughter_frame_spans(probs, threshold):
     """Integer (first_frame, last_frame) runs for one threshold: the bit-exact core of get_laughter_instances."""
     return run_spans(fix_probs(probs) > threshold)
+
+
+def _device_run_tables(probs, thresholds):
+    """probs: (C, T) float32 / float64 GPU tensor, T >= 1.  Returns (counts (C, K) int64, table (total, 2) int32 numpy): the
+    (c, k) tables back to back in c * K + k order (include/lad_hip.h: lad_runs_count, lad_runs_fill)."""
+    import torch
+
+    import _hip
+    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
+        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    _hip.require_cuda(probs, "probs")
+    lib = _hip.lib()
+    C, T = probs.shape
+    K = len(thresholds)
+    thr = (ctypes.c_double * max(K, 1))(*[float(t) for t in thresholds])
+    dtype = 0 if probs.dtype == torch.float32 else 1     # lad_runs_dtype
+    ws_bytes = lib.lad_runs_workspace_bytes(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_runs_workspace_bytes")
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
+        _hip.check(lib.lad_runs_count(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), stream), "lad_runs_count")
+        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
+        total = int(counts.sum(dtype=np.int64))
+        table = torch.empty((total, 2), dtype=torch.int32, device=probs.device)
+        _hip.check(lib.lad_runs_fill(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws),
+                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _hip.ptr(table), total, stream),
+                   "lad_runs_fill")
+        return counts.astype(np.int64).reshape(C, K), table.cpu().numpy()
+
+
+def _split_tables(counts, table):
+    """[[ (n, 2) int64 array per threshold ] per channel] from the back-to-back tables."""
+    edges = np.concatenate([[0], np.cumsum(counts.reshape(-1))])
+    C, K = counts.shape
+    return [[table[edges[c * K + k]:edges[c * K + k + 1]].astype(np.int64) for k in range(K)] for c in range(C)]
+
+
+def get_laughter_frame_spans_device(probs, thresholds):
+    """Device form of get_laughter_frame_spans for a list of thresholds.  probs: (T,) GPU tensor (float32 / float64, contiguous) ->
+    [int64 (n, 2) array of (first_frame, last_frame) per threshold], each equal to get_laughter_frame_spans(probs.cpu(), thr);
+    (C, T) -> one such list per channel, from the same four launches."""
+    import _hip
+    thresholds = list(thresholds)
+    single = getattr(probs, "ndim", None) == 1
+    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
+    if getattr(p2, "ndim", None) != 2:
+        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device sweep has no CPU fallback)")
+    C, T = p2.shape
+    if T == 0 or C == 0 or not thresholds:
+        _hip.require_cuda(p2, "probs")
+        out = [[np.zeros((0, 2), np.int64) for _ in thresholds] for _ in range(C)]
+    else:
+        out = _split_tables(*_device_run_tables(p2, thresholds))
+    return out[0] if single else out
+
+
+def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+    """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats).
+    The run tables come from the device; first / fps, last / fps and end - start > min_length are evaluated on them in float64
+    (the arithmetic of the reference's Python floats)."""
+    import _hip
+    if getattr(probs, "ndim", None) != 1:
+        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
+    thresholds = list(thresholds)
+    instance_dict = {}
+    for thr, spans in zip(thresholds, get_laughter_frame_spans_device(probs, thresholds)):
+        starts, ends = spans[:, 0] / fps, spans[:, 1] / fps
+        length = ends - starts
+        for min_l in min_lengths:
+            keep = length > min_l
+            instance_dict[(thr, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
+    return {(thr, min_l): instance_dict[(thr, min_l)] for thr in thresholds for min_l in min_lengths}

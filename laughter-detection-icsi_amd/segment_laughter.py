@@ -16,6 +16,10 @@ tolerance in tests/test_resnet_gpu.py) -- the invocation behind the published re
 The script prints the real-time factor of everything it does (file read, featurisation, windows, threshold sweep,
 TextGrid / wav output).  With torchrun (one process per GPU) the window range is sharded over ranks and the
 probabilities are all-gathered.
+
+`--segmenter device` (default `host`) keeps the gathered track on the GPU and cuts it there (csrc/runs.hip through
+`laugh_segmenter.get_laughter_instances_device`: the run tables of every threshold in four launches); only the compact tables
+cross to the host, and the track itself only when `--save_probs` asks for it.  Same TextGrids and wav files, byte for byte.
 """
 import argparse
 import os
@@ -53,8 +57,8 @@ def build_model(config_name, model_path, device):
     return model
 
 
-def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32"):
-    """probs (T,) float32 numpy for the stride-one-frame windows of the file + its duration in seconds.
+def predict_file_device(model, audio_path, chunk=None, rank=0, world=1, precision="fp32"):
+    """probs (T,) float32 GPU tensor for the stride-one-frame windows of the file + its duration in seconds.
     chunk=None: the engine's own chunk size for the precision (engine.PREDICT_CHUNK)."""
     loader = load_data.create_inference_dataloader(audio_path)
     feats = loader.dataset.feats
@@ -64,6 +68,12 @@ def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32
                                          precision=precision)
     probs = parallel.gather_probs(local, T, rank, world)
     file_length = audio_utils.get_audio_length(audio_path)  # seconds; fps = T / file_length (segment_laughter.py:103-104)
+    return probs, file_length
+
+
+def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32"):
+    """predict_file_device with the track copied to the host: probs (T,) float32 numpy + the duration in seconds."""
+    probs, file_length = predict_file_device(model, audio_path, chunk=chunk, rank=rank, world=world, precision=precision)
     return probs.cpu().numpy(), file_length
 
 
@@ -85,17 +95,29 @@ def save_audio_instances(instances, audio_path, output_dir):
 
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
-                  precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None):
-    """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]})."""
+                  precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host"):
+    """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
+    segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary)."""
+    if segmenter not in ("host", "device"):
+        raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if save_to_audio_files and output_dir is None:
         raise Exception("Need to specify an output directory to save audio files")   # segment_laughter.py:138-140
     start_time = time.time()
-    probs, file_length = predict_file(model, audio_path, rank=rank, world=world, precision=precision)
+    predict = predict_file_device if segmenter == "device" else predict_file
+    probs, file_length = predict(model, audio_path, rank=rank, world=world, precision=precision)
+    if segmenter == "device":
+        torch.cuda.synchronize(probs.device)   # (the host path's copy waits for the model pass: the same split of the two legs)
     predict_time = time.time() - start_time
     if save_probs and rank == 0:
-        np.save(save_probs, probs)   # (not in the reference: the per-frame track, e.g. to compare a sharded run with a single-rank one)
+        # (not in the reference: the per-frame track, e.g. to compare a sharded run with a single-rank one)
+        np.save(save_probs, probs.cpu().numpy() if segmenter == "device" else probs)
     fps = len(probs) / float(file_length)
-    instance_dict = laugh_segmenter.get_laughter_instances(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
+    if segmenter == "host":
+        instance_dict = laugh_segmenter.get_laughter_instances(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
+    elif rank == 0:
+        instance_dict = laugh_segmenter.get_laughter_instances_device(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
+    else:
+        instance_dict = {}
     sweep_time = time.time() - start_time - predict_time
     if rank == 0:
         for setting, instances in instance_dict.items():
@@ -119,7 +141,7 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     return time_taken, instance_dict
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--model_path', type=str, default='checkpoints/in_use/resnet_with_augmentation')
     parser.add_argument('--config', type=str, default='resnet_base')
@@ -135,7 +157,14 @@ def main(argv=None):
     parser.add_argument('--gpus', type=int, default=None,
                         help='ranks that share the window range; > 1 without a launcher environment starts the ranks itself')
     parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'fp16'], help='matrix-core precision')
-    args = parser.parse_args(argv)
+    parser.add_argument('--segmenter', type=str, default='host', choices=['host', 'device'],
+                        help="(not in the reference) where the probability track is cut into instances: 'host' copies it to the host "
+                             "(numpy, one pass per threshold); 'device' cuts it on the GPU, all thresholds in one pass -- same output")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.gpus is not None and args.gpus > 1 and not parallel.under_launcher():
         raise SystemExit(parallel.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:] if argv is None else list(argv),
                                               timeout=None))
@@ -152,7 +181,8 @@ def main(argv=None):
     truthy = ('true', '1', 'yes')
     load_and_pred(model, args.input_audio_file, thresholds, min_lengths, args.output_dir,
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
-                  precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs)
+                  precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
+                  segmenter=args.segmenter)
 
 
 if __name__ == '__main__':
