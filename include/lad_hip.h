@@ -591,6 +591,44 @@ int lad_runs_fill(const void *probs, int32_t dtype, int64_t channels, int64_t fr
                   int32_t n_thresholds, const void *workspace, const int32_t *counts_host, int32_t *table,
                   int64_t capacity_runs, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scores of the sweep against transcript intervals, from the run tables above while they are still on the device.
+ * Replaces analysis/analyse.py: eval_preds :152-225 and laugh_match :120-149 up to the per-channel integers (and the TextGrid
+ * files that textgrid_to_df :49-61 reads back), on the index of analysis/preprocess.py:27-46, 49-120, 133-167, time base
+ * analysis/utils.py:8-37 (milliseconds, Python's round).  A run (first, last) of channel c is start = first / fps[c],
+ * end = last / fps[c] in float64, kept for min_length l iff end - start > l (laugh_segmenter.py:74-111), and the interval
+ * (a, b] = (rint(start * 1000), rint(end * 1000)].  scores[c][k][l] = { n_pred, n_valid, pred_ms, corr_ms, fp_speech_ms,
+ * fp_noise_ms, fp_silence_ms } (enum lad_score_field) summed over the kept runs: n_valid counts runs with (a, b] \ INVALID
+ * non-empty, or every run if the channel has no invalid interval (analyse.py:185-187); pred_ms = |(a, b] \ INVALID|; the other
+ * four are |(a, b] n class|.
+ * Index (CSR): int32 bounds[n_intervals][2] = (lo, hi], int32 offsets[channels * 5 + 1], segment c * 5 + class with the
+ * classes of enum lad_score_class; within a segment intervals are non-empty, sorted and disjoint, 0 <= lo < hi; LAUGH, SPEECH,
+ * NOISE and SILENCE come with INVALID already subtracted (laugh_match :129-131 subtracts it from the prediction instead).
+ * Integer sums accumulated with vector global atomics on int64: identical bytes on every call.
+ * ---------------------------------------------------------------------------------------------- */
+enum lad_score_class { LAD_SCORE_INVALID = 0, LAD_SCORE_LAUGH = 1, LAD_SCORE_SPEECH = 2, LAD_SCORE_NOISE = 3, LAD_SCORE_SILENCE = 4 };
+enum lad_score_field { LAD_SCORE_N_PRED = 0, LAD_SCORE_N_VALID = 1, LAD_SCORE_PRED_MS = 2, LAD_SCORE_CORR_MS = 3,
+                       LAD_SCORE_FP_SPEECH_MS = 4, LAD_SCORE_FP_NOISE_MS = 5, LAD_SCORE_FP_SILENCE_MS = 6, LAD_SCORE_FIELDS = 7 };
+/* largest n_min_lengths of one call (8; the evaluation sweep of cluster_scripts/gen_eval_exp.py:30-36 uses 3) */
+int32_t lad_score_max_min_lengths(void);
+/* bytes of workspace for lad_score_runs (analyse.py:152-225); needs no GPU.  -1 and lad_last_error() for channels outside
+ * 1..65535, n_intervals outside 0..2^30, n_thresholds outside 1..lad_runs_max_thresholds() or n_min_lengths outside
+ * 1..lad_score_max_min_lengths(). */
+int64_t lad_score_workspace_bytes(int64_t channels, int64_t n_intervals, int32_t n_thresholds, int32_t n_min_lengths);
+/* eval_preds / laugh_match of analyse.py:120-225 for every (channel, threshold, min_length) at once: a memset and two launches on
+ * `stream`.  runs_workspace, table, counts_host, channels, frames, n_thresholds: as given to / left by lad_runs_count and
+ * lad_runs_fill (only the counts at the start of runs_workspace are read).  bounds, offsets, fps: DEVICE; bounds_host,
+ * offsets_host, fps_host: HOST copies of the same values, checked before anything is launched; min_lengths: HOST
+ * double[n_min_lengths].  scores: DEVICE int64[channels][n_thresholds][n_min_lengths][7].
+ * LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for sizes out of range, an index whose offsets
+ * do not ascend from 0 to n_intervals or whose intervals are empty, unsorted or overlapping, an fps that is not positive and
+ * finite, or millisecond overflow: to_frames(frames / fps[c]) (utils.py:8-15) must stay below 2^31 for every channel. */
+int lad_score_runs(const void *runs_workspace, const int32_t *table, const int32_t *counts_host, int64_t channels,
+                   int64_t frames, int32_t n_thresholds, const int32_t *bounds, const int32_t *offsets,
+                   const int32_t *bounds_host, const int32_t *offsets_host, int64_t n_intervals, const double *fps,
+                   const double *fps_host, const double *min_lengths, int32_t n_min_lengths, void *workspace,
+                   int64_t *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,12 @@ SIGNATURES = {
     "lad_runs_count": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p]),
     "lad_runs_fill": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p,
                               ctypes.POINTER(c_i32), c_void_p, c_i64, c_void_p]),
+    # scores of the sweep against transcript intervals (csrc/score.hip)
+    "lad_score_max_min_lengths": (c_i32, []),
+    "lad_score_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "lad_score_runs": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_void_p,
+                               ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
+                               ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Precision and recall of the threshold sweep against the transcript, from saved probability tracks.
+
+Counterpart of the reference's evaluation (analysis/analyse.py: create_evaluation_df :227-266, eval_preds :152-225,
+calc_sum_stats :269-298, on the indices of analysis/preprocess.py).  The reference gets there through one TextGrid file per
+(channel, threshold, min_length) that segment_laughter.py writes and analyse.py reads back; here the tracks
+`segment_laughter.py --save_probs` wrote are swept and scored directly:
+
+    python evaluate_sweep.py --probs_dir <dir with <meeting>/<chan>.npy> --transcripts rows.csv --channels channels.csv \\
+        --thresholds 0,0.05,...,1 --min_lengths 0,0.1,0.2 --out_dir <out>
+
+--transcripts: CSV with the columns of the reference's parse.py DataFrames (meeting_id, part_id, chan, start, end, length, type,
+laugh_type; type in laugh / speech / noise / invalid).  --channels: CSV meeting_id, part_id, chan, length (seconds; an empty part_id
+for a channel that belongs to no participant -- it is not evaluated, analyse.py:27-28).  The frame rate of a channel is its frame
+count over its length (segment_laughter.py:103-104) unless --fps is given.
+
+Writes `eval_df_per_meeting.csv` (the 14 columns of analyse.py:255-257) and `sum_stats.csv` (config.py:38-39 of the reference).
+`--scorer device` (default `host`) uploads all tracks as one NaN-padded (C, T) tensor and scores the whole sweep on the GPU
+(csrc/runs.hip + csrc/score.hip through sweep_eval.score_sweep_device); both scorers write the same bytes.
+"""
+import argparse
+import csv
+import os
+import sys
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.join(_PKG, "utils"), _PKG):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np  # noqa: E402
+
+import sweep_eval  # noqa: E402
+
+
+def read_csv(path, columns, numeric):
+    with open(path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    for r in rows:
+        missing = [c for c in columns if c not in r]
+        if missing:
+            raise ValueError(f"{path} lacks the columns {missing}")
+        for c in numeric:
+            r[c] = float(r[c])
+    return rows
+
+
+def load_tracks(probs_dir, index):
+    """[(meeting_id, chan)], [track] for every <meeting>/<chan>.npy whose channel the channel table lists, in sorted order."""
+    known = set(index.channels())
+    channels, tracks = [], []
+    for meeting in sorted(os.listdir(probs_dir)):
+        mdir = os.path.join(probs_dir, meeting)
+        if not os.path.isdir(mdir):
+            continue
+        for name in sorted(os.listdir(mdir)):
+            if name.endswith(".npy") and (meeting, name[:-4]) in known:
+                channels.append((meeting, name[:-4]))
+                tracks.append(np.load(os.path.join(mdir, name)).reshape(-1))
+    if not channels:
+        raise ValueError(f"no <meeting>/<chan>.npy under {probs_dir} matches the channel table")
+    return channels, tracks
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index):
+    import torch
+    dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
+    padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
+    for c, t in enumerate(tracks):
+        padded[c, :len(t)] = t
+    return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index)
+
+
+def write_csv(path, columns, rows):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(columns)
+        for r in rows:
+            w.writerow([repr(v) if isinstance(v, float) else v for v in r])
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--probs_dir', required=True, type=str, help='<meeting>/<chan>.npy, as segment_laughter.py --save_probs writes')
+    parser.add_argument('--transcripts', required=True, type=str, help='CSV: meeting_id,part_id,chan,start,end,length,type,laugh_type')
+    parser.add_argument('--channels', required=True, type=str, help='CSV: meeting_id,part_id,chan,length')
+    parser.add_argument('--thresholds', type=str, default='0.5', help='Single value or comma-separated list of thresholds to evaluate')
+    parser.add_argument('--min_lengths', type=str, default='0.2', help='Single value or comma-separated list of min_lengths to evaluate')
+    parser.add_argument('--fps', type=float, default=None, help='frames per second of every track (default: frames / channel length)')
+    parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
+                        help='host: laugh_segmenter.get_laughter_instances + sweep_eval.score_instances per channel; '
+                             'device: the sweep and its scores on the GPU (csrc/runs.hip, csrc/score.hip)')
+    parser.add_argument('--out_dir', required=True, type=str)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    thresholds = [float(t) for t in args.thresholds.split(',')]
+    min_lengths = [float(t) for t in args.min_lengths.split(',')]
+    rows = read_csv(args.transcripts, sweep_eval.ROW_COLUMNS, ("start", "end", "length"))
+    chans = read_csv(args.channels, sweep_eval.CHANNEL_COLUMNS, ("length",))
+    index = sweep_eval.TranscriptIndex(rows, chans)
+    channels, tracks = load_tracks(args.probs_dir, index)
+    length = {(c["meeting_id"], c["chan"]): c["length"] for c in chans}
+    fps = [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
+    if args.scorer == "device":
+        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index)
+    else:
+        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index)
+    per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index)
+    os.makedirs(args.out_dir, exist_ok=True)
+    write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"), sweep_eval.EVAL_COLUMNS, per_meeting)
+    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), sweep_eval.SUM_COLUMNS, sweep_eval.calc_sum_stats(per_meeting))
+    print(f"{len(channels)} channels, {len(thresholds) * len(min_lengths)} settings ({args.scorer} scorer): "
+          f"{len(per_meeting)} rows -> {args.out_dir}")
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,395 @@
+"""Scores of the threshold sweep against the transcript: what the reference's analysis/ computes from 87 TextGrid files per channel.
+
+Reference: analysis/utils.py:8-37 (to_frames, to_sec, p_len: a time base of integer milliseconds, Python's round), analysis/
+preprocess.py:13-24 (seg_invalid), :27-46 (append_to_index), :49-120 (the laugh / invalid / speech / noise indices), :133-167 (the
+silence index), analysis/analyse.py:120-149 (laugh_match), :152-225 (eval_preds), :255-257 (the 14 columns), :269-298
+(calc_sum_stats).  The reference keeps every set as a `portion` interval union and measures it by iterating its milliseconds;
+here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a difference of two coverage values.
+
+    TranscriptIndex        the five interval sets per channel (INVALID, LAUGH, SPEECH, NOISE, SILENCE) and the per-meeting totals
+    score_instances        host scorer of one channel's get_laughter_instances dictionary -> {(thr, min_l): 7 ints}
+    score_sweep_host       the host sweep + score_instances for several tracks -> int64 (C, K, L, 7)
+    score_sweep_device     the same array for tracks in GPU memory (csrc/runs.hip + csrc/score.hip): besides the C x K run counts
+                           only the scores cross to the host.  No CPU fallback.
+    eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
+    calc_sum_stats         threshold, min_len, precision, recall over all meetings
+
+Everything is integer arithmetic plus a few IEEE float64 operations, so host and device agree exactly.
+"""
+import ctypes
+
+import numpy as np
+
+CLASSES = ("invalid", "laugh", "speech", "noise", "silence")          # include/lad_hip.h: enum lad_score_class
+FIELDS = ("n_pred", "n_valid", "pred_ms", "corr_ms", "fp_speech_ms", "fp_noise_ms", "fp_silence_ms")   # enum lad_score_field
+EVAL_COLUMNS = ["meeting", "threshold", "min_len", "precision", "recall", "corr_pred_time", "tot_pred_time", "tot_transc_laugh_time",
+                "num_of_pred_laughs", "valid_pred_laughs", "num_of_transc_laughs", "tot_fp_speech_time", "tot_fp_noise_time",
+                "tot_fp_silence_time"]                                # analyse.py:255-257
+SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.py:290
+ROW_COLUMNS = ("meeting_id", "part_id", "chan", "start", "end", "length", "type", "laugh_type")
+CHANNEL_COLUMNS = ("meeting_id", "part_id", "chan", "length")
+FACTOR = 1000.0                # utils.py:14: 1000 / frame_duration, frame_duration = 1 ms (config.py:46-52)
+MIN_LAUGH_LENGTH = 0.2         # preprocess.py:22: cfg["model"]["min_length"]
+_EMPTY = np.zeros((0, 2), np.int64)
+
+
+def to_frames(t):
+    """utils.py:8-15: round(t * factor), Python's round on a float (half to even); numpy.rint is the same function."""
+    return np.rint(np.asarray(t, dtype=np.float64) * FACTOR).astype(np.int64)
+
+
+def to_sec(n):
+    """utils.py:18-25"""
+    return n / FACTOR
+
+
+# ---- interval sets: int64 (n, 2) arrays of (lo, hi], sorted, disjoint, non-empty, not touching -----------------------------------
+def normalise(iv):
+    """Union of arbitrary (lo, hi] rows: empty ones (hi <= lo) dropped, the part below 0 cut off (no prediction reaches it),
+    overlapping and adjacent ones merged."""
+    iv = np.asarray(iv, dtype=np.int64).reshape(-1, 2)
+    iv = np.stack([np.maximum(iv[:, 0], 0), iv[:, 1]], axis=1)
+    iv = iv[iv[:, 1] > iv[:, 0]]
+    if len(iv) == 0:
+        return _EMPTY
+    iv = iv[np.argsort(iv[:, 0], kind="stable")]
+    reach = np.maximum.accumulate(iv[:, 1])
+    first = np.concatenate([[True], iv[1:, 0] > reach[:-1]])           # a row that starts beyond everything before it
+    starts = np.flatnonzero(first)
+    ends = np.concatenate([starts[1:], [len(iv)]]) - 1
+    return np.stack([iv[starts, 0], reach[ends]], axis=1)
+
+
+def _member(iv, x):
+    """x in the set, element-wise."""
+    if len(iv) == 0:
+        return np.zeros(len(x), bool)
+    i = np.searchsorted(iv[:, 0], x, side="left") - 1                  # the last interval with lo < x
+    return (i >= 0) & (x <= iv[np.maximum(i, 0), 1])
+
+
+def subtract(a, b):
+    """a minus b for two normalised sets."""
+    if len(a) == 0 or len(b) == 0:
+        return a
+    pts = np.unique(np.concatenate([a.ravel(), b.ravel()]))
+    right = pts[1:]                                                     # (pts[i], pts[i + 1]] lies wholly inside or outside each set
+    keep = _member(a, right) & ~_member(b, right)
+    return normalise(np.stack([pts[:-1][keep], right[keep]], axis=1))
+
+
+def _cum(iv):
+    return np.concatenate([[0], np.cumsum(iv[:, 1] - iv[:, 0])])[:-1] if len(iv) else np.zeros(0, np.int64)
+
+
+def coverage(iv, x):
+    """F(x) = milliseconds of the set in (0, x], element-wise (csrc/score.hip evaluates the same expression)."""
+    x = np.asarray(x, dtype=np.int64)
+    if len(iv) == 0:
+        return np.zeros(x.shape, np.int64)
+    i = np.searchsorted(iv[:, 0], x, side="left") - 1
+    j = np.maximum(i, 0)
+    return np.where(i >= 0, _cum(iv)[j] + np.minimum(x, iv[j, 1]) - iv[j, 0], 0)
+
+
+def _records(table, columns):
+    """Rows as dictionaries: a pandas DataFrame, an iterable of mappings, or an iterable of tuples in column order."""
+    if hasattr(table, "to_dict") and hasattr(table, "columns"):
+        table = table.to_dict("records")
+    out = []
+    for r in table:
+        out.append(dict(r) if hasattr(r, "keys") else dict(zip(columns, r)))
+        missing = [c for c in columns if c not in out[-1]]
+        if missing:
+            raise ValueError(f"row {len(out) - 1} lacks {missing}")
+    return out
+
+
+class DeviceIndex:
+    """The CSR form csrc/score.hip reads, for a list of channels: bounds int32 (n, 2), offsets int32 (C * 5 + 1) on the device, and
+    the host copies lad_score_runs checks before it launches anything."""
+
+    def __init__(self, channels, bounds_host, offsets_host, device):
+        import torch
+        self.channels = list(channels)
+        self.bounds_host = np.ascontiguousarray(bounds_host, dtype=np.int32).reshape(-1, 2)
+        self.offsets_host = np.ascontiguousarray(offsets_host, dtype=np.int32)
+        self.bounds = torch.from_numpy(self.bounds_host if len(self.bounds_host) else np.zeros((1, 2), np.int32)).to(device)
+        self.offsets = torch.from_numpy(self.offsets_host).to(device)
+        self.device = self.bounds.device                                           # ("cuda" -> the device it resolved to)
+
+    @property
+    def n_intervals(self):
+        return len(self.bounds_host)
+
+
+class TranscriptIndex:
+    """preprocess.py's five indices from the transcript rows (columns of parse.py's DataFrames: meeting_id, part_id, chan, start,
+    end, length, type, laugh_type; type in laugh / speech / noise / invalid) and the channel table (meeting_id, part_id, chan,
+    length; part_id None or '' for a channel that is mapped to no participant: analyse.py:27-28 does not evaluate it).
+    Built once per corpus, pure numpy."""
+
+    def __init__(self, rows, channels):
+        rows = _records(rows, ROW_COLUMNS)
+        chans = _records(channels, CHANNEL_COLUMNS)
+        self._part = {}                     # (meeting, chan) -> part_id or None
+        self._length = {}                   # (meeting, part) -> channel length in seconds
+        for c in chans:
+            part = c["part_id"] if c["part_id"] not in (None, "") else None
+            key = (c["meeting_id"], c["chan"])
+            if key in self._part:
+                raise ValueError(f"channel {key} is listed twice")
+            self._part[key] = part
+            if part is not None:
+                if (c["meeting_id"], part) in self._length:
+                    raise ValueError(f"participant {part} of {c['meeting_id']} has two channels")
+                self._length[(c["meeting_id"], part)] = float(c["length"])
+        for r in rows:
+            if r["type"] not in CLASSES[:4]:
+                raise ValueError(f"row type {r['type']!r}: one of {CLASSES[:4]}")
+        self.meetings = sorted({c["meeting_id"] for c in chans} | {r["meeting_id"] for r in rows})
+        self._raw = {}                      # (meeting, part) -> {class: [(lo, hi), ...]}
+        self._tot = {m: {k: [0, 0] for k in CLASSES[:4]} for m in self.meetings}      # class -> [tot_len, tot_events]
+        self._laugh_rows = {m: 0 for m in self.meetings}
+        # preprocess.py:193-196: the invalid rows first, then the laugh rows (which add to the invalid index), speech, noise;
+        # each by meeting, participants ascending, rows by start (:66-86, :108-118)
+        for kind in ("invalid", "laugh", "speech", "noise"):
+            sel = [r for r in rows if r["type"] == kind]
+            sel.sort(key=lambda r: float(r["start"]))                              # (stable)
+            sel.sort(key=lambda r: (r["meeting_id"], r["part_id"]))
+            for r in sel:
+                m = r["meeting_id"]
+                target = kind
+                if kind == "laugh":
+                    self._laugh_rows[m] += 1
+                    if float(r["length"]) < MIN_LAUGH_LENGTH or r["laugh_type"] == "breath-laugh":      # seg_invalid :13-24
+                        target = "invalid"
+                lo, hi = int(to_frames(float(r["start"]))), int(to_frames(float(r["end"])))
+                if hi >= 2 ** 31:
+                    raise ValueError(f"row ends at {hi} ms: millisecond values are int32")
+                self._raw.setdefault((m, r["part_id"]), {k: [] for k in CLASSES[:4]})[target].append((lo, hi))
+                self._tot[m][target][0] += to_sec(max(hi - lo, 0))                 # append_to_index :42-45 (p_len of one interval)
+                self._tot[m][target][1] += 1
+        self._sets = {}
+        self._device = {}
+
+    # ---- per meeting -------------------------------------------------------------------------------------------------------------
+    def tot_len(self, meeting_id, kind="laugh"):
+        """Sum of the rows' lengths in seconds (not the length of their union): index[meeting]['tot_len']."""
+        return self._tot[meeting_id][kind][0]
+
+    def tot_events(self, meeting_id, kind="laugh"):
+        return self._tot[meeting_id][kind][1]
+
+    def num_laugh_rows(self, meeting_id):
+        """Rows of type laugh in the input table (parse.laugh_only_df of the meeting: analyse.py:163-164)."""
+        return self._laugh_rows[meeting_id]
+
+    # ---- per channel -------------------------------------------------------------------------------------------------------------
+    def channels(self, meeting_id=None):
+        return [k for k in self._part if meeting_id is None or k[0] == meeting_id]
+
+    def participant(self, meeting_id, chan):
+        return self._part[(meeting_id, chan)]
+
+    def intervals(self, meeting_id, chan):
+        """{class: int64 (n, 2) array of (lo, hi]} as preprocess.py holds them (each class the union of its own rows, SILENCE the
+        rest of (0, to_frames(length)]); None for a channel without a participant."""
+        part = self._part[(meeting_id, chan)]
+        if part is None:
+            return None
+        key = (meeting_id, part)
+        if key not in self._sets:
+            raw = self._raw.get(key, {})
+            sets = {k: normalise(raw.get(k, [])) for k in CLASSES[:4]}
+            full = normalise([(0, int(to_frames(self._length[key])))])
+            if len(full) and full[0, 1] >= 2 ** 31:
+                raise ValueError(f"channel {chan} of {meeting_id} ends at {full[0, 1]} ms: millisecond values are int32")
+            silence = full
+            for k in ("laugh", "invalid", "speech", "noise"):                      # preprocess.py:157-163
+                silence = subtract(silence, sets[k])
+            sets["silence"] = silence
+            self._sets[key] = sets
+        return self._sets[key]
+
+    def scoring_sets(self, meeting_id, chan):
+        """The five sets in class order as the scorers use them: INVALID, and the other four minus INVALID (laugh_match :129-131
+        subtracts INVALID from the prediction; subtracting it from the classes once gives the same overlaps).  Five empty sets for
+        a channel without a participant."""
+        sets = self.intervals(meeting_id, chan)
+        if sets is None:
+            return [_EMPTY] * len(CLASSES)
+        return [sets["invalid"]] + [subtract(sets[k], sets["invalid"]) for k in CLASSES[1:]]
+
+    def to_device(self, channels, device="cuda"):
+        """DeviceIndex of a list of (meeting_id, chan) (kept: a second call with the same list returns the same tensors)."""
+        import torch
+        key = (tuple(channels), str(torch.device(device)))
+        if key not in self._device:
+            parts = [s for mc in channels for s in self.scoring_sets(*mc)]
+            offsets = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
+            if offsets[-1] >= 2 ** 30:
+                raise ValueError("the index holds more than 2^30 intervals")
+            bounds = np.concatenate(parts) if parts else _EMPTY
+            self._device[key] = DeviceIndex(channels, bounds, offsets, device)
+        return self._device[key]
+
+
+def _score_spans(a, b, sets):
+    """The seven integers for predictions (a, b] (int64 arrays) against the five scoring sets."""
+    cover = [coverage(s, b) - coverage(s, a) for s in sets]
+    pred = (b - a) - cover[0]
+    valid = pred > 0 if len(sets[0]) else np.ones(len(a), bool)                    # analyse.py:185-187
+    return (len(a), int(np.count_nonzero(valid)), int(pred.sum()), int(cover[1].sum()), int(cover[2].sum()), int(cover[3].sum()),
+            int(cover[4].sum()))
+
+
+def score_instances(instances, index, meeting_id, chan):
+    """Host scorer of one channel: instances as get_laughter_instances returns them -> {(thr, min_l): (n_pred, n_valid, pred_ms,
+    corr_ms, fp_speech_ms, fp_noise_ms, fp_silence_ms)}, each prediction (start_s, end_s) being the millisecond interval
+    (to_frames(start), to_frames(end)] (analyse.py:179-181)."""
+    sets = index.scoring_sets(meeting_id, chan)
+    out = {}
+    for key, spans in instances.items():
+        s = np.asarray(spans, dtype=np.float64).reshape(-1, 2)
+        out[key] = _score_spans(to_frames(s[:, 0]), to_frames(s[:, 1]), sets)
+    return out
+
+
+def _fps_list(fps, C):
+    f = [float(fps)] * C if np.ndim(fps) == 0 else [float(x) for x in fps]
+    if len(f) != C:
+        raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
+    return f
+
+
+def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index):
+    """laugh_segmenter.get_laughter_instances + score_instances per track -> int64 (C, K, L, 7).  tracks: C arrays (lengths may
+    differ); channels: C (meeting_id, chan); fps: a float or C floats."""
+    import laugh_segmenter as ls
+    thresholds, min_lengths = list(thresholds), list(min_lengths)
+    f = _fps_list(fps, len(channels))
+    out = np.zeros((len(channels), len(thresholds), len(min_lengths), len(FIELDS)), np.int64)
+    for c, (track, mc) in enumerate(zip(tracks, channels)):
+        got = score_instances(ls.get_laughter_instances(track, thresholds, min_lengths, f[c]), index, *mc)
+        for k, thr in enumerate(thresholds):
+            for l, min_l in enumerate(min_lengths):
+                out[c, k, l] = got[(thr, min_l)]
+    return out
+
+
+def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index):
+    """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
+    (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
+    TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
+    the run tables never leave the device."""
+    import torch
+
+    import _hip
+    if getattr(probs, "ndim", None) == 1 and hasattr(probs, "unsqueeze"):
+        probs = probs.unsqueeze(0)
+    if getattr(probs, "ndim", None) != 2:
+        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device scorer has no CPU fallback)")
+    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
+        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    _hip.require_cuda(probs, "probs")
+    channels, thresholds, min_lengths = list(channels), list(thresholds), list(min_lengths)
+    C, T = probs.shape
+    K, L = len(thresholds), len(min_lengths)
+    if C != len(channels):
+        raise ValueError(f"{C} tracks for {len(channels)} channels")
+    f = _fps_list(fps, C)
+    out_shape = (C, K, L, len(FIELDS))
+    if C == 0 or T == 0 or K == 0 or L == 0:
+        return np.zeros(out_shape, np.int64)
+    lib = _hip.lib()
+    dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
+    if dix.channels != channels or dix.device != probs.device:
+        raise ValueError("the DeviceIndex was built for other channels or another device")
+    thr = (ctypes.c_double * K)(*[float(t) for t in thresholds])
+    mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
+    fps_host = np.asarray(f, dtype=np.float64)
+    dtype = 0 if probs.dtype == torch.float32 else 1                               # lad_runs_dtype
+    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    ws_bytes = lib.lad_runs_workspace_bytes(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_runs_workspace_bytes")
+    sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, K, L)
+    _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        ws = torch.empty(ws_bytes + sws_bytes, dtype=torch.uint8, device=probs.device)
+        sws = ws[ws_bytes:]
+        fps_dev = torch.from_numpy(fps_host).to(probs.device)
+        scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
+        _hip.check(lib.lad_runs_count(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), stream), "lad_runs_count")
+        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())            # (synchronises)
+        total = int(counts.sum(dtype=np.int64))
+        table = torch.empty((max(total, 1), 2), dtype=torch.int32, device=probs.device)
+        cptr = counts.ctypes.data_as(i32p)
+        _hip.check(lib.lad_runs_fill(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), cptr, _hip.ptr(table), total, stream),
+                   "lad_runs_fill")
+        _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), cptr, C, T, K, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
+                                      dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
+                                      _hip.ptr(fps_dev), fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(sws), _hip.ptr(scores),
+                                      stream), "lad_score_runs")
+        return scores.cpu().numpy()
+
+
+def eval_rows(scores, channels, thresholds, min_lengths, index):
+    """eval_preds (analyse.py:152-225) for every meeting and setting: a list of 14-value rows in EVAL_COLUMNS order, meetings
+    ascending, thresholds-major.  scores: (C, K, L, 7) of score_sweep_host / score_sweep_device for `channels`.  Channels without a
+    participant are left out (analyse.py:27-28); the float sums run over participants in ascending part_id order (:173-197)."""
+    scores = np.asarray(scores)
+    per_meeting = {}
+    for c, (m, chan) in enumerate(channels):
+        part = index.participant(m, chan)
+        if part is not None:
+            per_meeting.setdefault(m, []).append((part, c))
+    rows = []
+    for m in sorted(per_meeting):
+        parts = sorted(per_meeting[m])
+        tot_transc = index.tot_len(m, "laugh")
+        n_transc = index.num_laugh_rows(m)
+        for k, thr in enumerate(thresholds):
+            for l, min_l in enumerate(min_lengths):
+                corr_t = incorr_t = speech_t = noise_t = silence_t = 0
+                n_pred = n_valid = 0
+                for _, c in parts:
+                    s = [int(v) for v in scores[c, k, l]]
+                    n_pred += s[0]
+                    n_valid += s[1]
+                    if s[0] == 0:
+                        continue                                                   # (no row of this participant: groupby skips it)
+                    pred_length = to_sec(s[2])                                     # laugh_match :133-145
+                    correct = to_sec(s[3])
+                    corr_t += correct
+                    incorr_t += pred_length - correct
+                    speech_t += to_sec(s[4])
+                    noise_t += to_sec(s[5])
+                    silence_t += to_sec(s[6])
+                pred_t = corr_t + incorr_t
+                prec = 1 if pred_t == 0 else corr_t / pred_t
+                recall = float("nan") if tot_transc == 0 else corr_t / tot_transc
+                rows.append([m, thr, min_l, prec, recall, corr_t, pred_t, tot_transc, n_pred, n_valid, n_transc, speech_t, noise_t,
+                             silence_t])
+    return rows
+
+
+def calc_sum_stats(rows):
+    """analyse.py:269-298: per (min_len, threshold) the sums of corr_pred_time, tot_pred_time and tot_transc_laugh_time over the
+    meetings (in row order), precision = corr / pred (1 where pred is 0), recall = corr / transcribed (float division: NaN or inf
+    where that is 0).  Rows of SUM_COLUMNS, ordered by (min_len, threshold) as the groupby."""
+    sums = {}
+    for r in rows:
+        acc = sums.setdefault((r[2], r[1]), [0, 0, 0])
+        acc[0] += r[5]
+        acc[1] += r[6]
+        acc[2] += r[7]
+    out = []
+    for (min_l, thr) in sorted(sums):
+        corr, pred, transc = (np.float64(v) for v in sums[(min_l, thr)])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            prec = 1.0 if pred == 0 else float(corr / pred)
+            recall = float(corr / transc)
+        out.append([thr, min_l, prec, recall])
+    return out
