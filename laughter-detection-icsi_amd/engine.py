@@ -15,6 +15,8 @@ step (no allocation inside the step).
 """
 import ctypes
 import math
+import struct
+from typing import FrozenSet, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -54,14 +56,26 @@ def _align4(n):
 class _ConvSpec:
     """One convolution: geometry + where its weights live in the flat buffers."""
 
-    def __init__(self, name, cin, cout, taps, stride, h_in, w_in, has_bias):
+    def __init__(self, name, cin, cout, taps, stride, h_in, w_in, has_bias, base_widths=True):
         self.name, self.cin, self.cout, self.taps, self.stride = name, cin, cout, taps, stride
         self.h_in, self.w_in = h_in, w_in
         self.h_out = (h_in + stride - 1) // stride
         self.w_out = (w_in + stride - 1) // stride
         self.has_bias = has_bias
+        # what the split-operand kernels have instances for, at the stage widths they were validated on (shape only: whether a step
+        # uses them is train_schedule's decision).  b3: forward and data gradient (64 or 32 channels); b3_full: 64 channels, where
+        # the sign bits exist as well
+        self.b3 = cin == cout and cin in (64, 32) and taps == 9 and stride == 1 and w_in <= 46 and base_widths
+        self.b3_full = self.b3 and cin == 64
+        self.b3_wgrad = self.b3 and (cin == 64 or w_in <= 30)   # the 32-channel weight-gradient window holds 64 rows + 2 (W + 2)
+        # the 64 -> 32 stride-2 transition with its shortcut: one split image per direction (3x3 + 1x1 together)
+        self.s2b3 = cin == 64 and cout == 32 and taps == 9 and stride == 2 and (w_in + 1) // 2 <= 45 and base_widths
         self.w = self.b = self.gw = self.gb = None  # views into the flat param / grad buffers
         self.wt_f = self.wt_d = None                # packed images (forward / data-gradient)
+
+    def rows(self, B):
+        """Rows of the layer's input tensor for batch B (shared zero borders + tail)."""
+        return B * (self.h_in + 1) * (self.w_in + 1) + self.w_in + 2
 
 
 class _BnSpec:
@@ -77,9 +91,147 @@ class _BlockSpec:
         self.conv1 = self.bn1 = self.conv2 = self.bn2 = self.sc_conv = self.sc_bn = None
 
 
+def block_geometry(stem_cout, filter_sizes, H, W, base_widths):
+    """The residual blocks of ResNetBigger for an (H, W) input, convolutions only and without tensors (models.py:73-76)."""
+    blocks = []
+    cin, h, w = stem_cout, H, W
+    for bi, cout in enumerate(filter_sizes, start=1):
+        for j in range(2):
+            name = f"block{bi}.{j}"
+            stride = 2 if (j == 0 and bi > 1) else 1
+            b = _BlockSpec(name)
+            b.conv1 = _ConvSpec(name + ".conv1", cin, cout, 9, stride, h, w, True, base_widths)
+            h, w = b.conv1.h_out, b.conv1.w_out
+            b.conv2 = _ConvSpec(name + ".conv2", cout, cout, 9, 1, h, w, True, base_widths)
+            if stride != 1 or cin != cout:
+                b.sc_conv = _ConvSpec(name + ".shortcut.0", cin, cout, 1, stride, b.conv1.h_in, b.conv1.w_in, False, base_widths)
+            blocks.append(b)
+            cin = cout
+    return blocks
+
+
+class _ConvChoice(NamedTuple):
+    """Kernels of one convolution in one training step."""
+    arith: str         # forward and data gradient: "f32" (exact-f32 MFMA) | "b3" (bf16 x 3) | "h2" (f16 x 2)
+    wgrad: str         # weight gradient: "f32" | "b3c" | "h2"
+    wgrad_bn: bool     # the weight-gradient launch may apply the BatchNorm backward of the layer's own output (csrc/wgrad_mfma.hip, DOBN)
+    label_fwd: str     # kernel_events labels of the two launches (bench.py keys on them)
+    label_dgrad: str
+
+
+class _BlockChoice(NamedTuple):
+    entry: str             # "s2b3" | "s2_fused" (conv1 and the 1x1 shortcut in one launch, forward and data gradient) | "plain"
+    a1_virtual: bool       # relu(bn1(c1)) is formed while conv2 and its weight gradient stage c1: never written
+    bits: bool             # the residual ReLU's decisions travel as sign bits (lad_bn_act_bits)
+    # whose arithmetic carries the first pass of the BatchNorm backward that consumes a data gradient: None, "f32" (fuse_bn_bwd:
+    # lad_conv_fwd_bnstat, whatever the layer's own arithmetic) or "split" (fuse_bn_bwd_b3: the layer's split-operand launch)
+    dgrad2_bn: Optional[str]   # conv2's data gradient + this block's bn1
+    dgrad1_bn: Optional[str]   # conv1's data gradient + bn2 of the block below
+    sc_wgrad_fused: bool   # stride-2 block: the shortcut's weight gradient as a tenth tap of conv1's
+    conv1: _ConvChoice
+    conv2: _ConvChoice
+    sc: Optional[_ConvChoice]
+
+
+class _TrainSchedule(NamedTuple):
+    """Every kernel choice of one train-mode forward and its backward (train_schedule)."""
+    blocks: Tuple[_BlockChoice, ...]
+    stem_onepass: bool
+    images: FrozenSet[Tuple[str, str]]   # packed split-operand weight images the step reads: ("h2" | "b3c" | "s2b3", convolution)
+    opts: Tuple[Tuple[str, object], ...]  # the flag values it was built from
+
+
+_ROW_LIMIT = (1 << 31) - (1 << 20)
+
+
+def train_schedule(blocks, B, opts, stem_onepass):
+    """The kernels of a training step at batch B: a pure function of the layer geometry (block_geometry) and the flag values
+    (opts: {name of KERNEL_OPTIONS: value}).  forward(train=True) stores the result in its plan and backward() reads nothing else,
+    so the two passes cannot disagree (a virtual a1 that was never written must not be read from HBM)."""
+    o = dict(opts)
+
+    def arith(cs):
+        # 64 channels (round 3): conv_b3x / wgrad_b3x address a tensor relative to the workgroup's own rows (64-bit bases),
+        # only row NUMBERS are 32-bit.  32 channels: the weight gradient still runs on the round-2 kernel, whose byte offsets
+        # are 32-bit (2 GiB per tensor = batch > 14,000 at 32 x 50 x 22); past that the layer runs on the exact-f32 kernels
+        fits = cs.rows(B) < _ROW_LIMIT if cs.cin == 64 else cs.rows(B) * cs.cin * 4 < _ROW_LIMIT
+        if not (o["bf16x3"] and cs.b3 and (cs.cin == 64 or o["bf16x3_32"]) and fits):
+            return "f32"
+        return "h2" if o["f16x2"] and (cs.cin == 64 or o["f16x2_32"]) else "b3"
+
+    def conv(cs, dgrad_f32=False, label_fwd=None):
+        a = arith(cs)
+        # same split arithmetic as the forward / data-gradient launches of the layer; at 32 channels bf16 x 3 only
+        wg = "f32" if a == "f32" or not cs.b3_wgrad else "h2" if a == "h2" and cs.cin == 64 else "b3c"
+        f32_label = f"conv_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
+        return _ConvChoice(a, wg, bool(o["fuse_bn_bwd_wgrad"]) and wg == "h2",
+                           label_fwd or (f32_label if a == "f32" else f"conv_{a}<{cs.cin},{cs.cout},{cs.taps}>"),
+                           f"conv_s1<{cs.cout},{cs.cin},{cs.taps}>" if a == "f32" or dgrad_f32 else f"conv_{a}<{cs.cout},{cs.cin},{cs.taps}>")
+
+    out = []
+    for bi, b in enumerate(blocks):
+        c1, c2, sc = b.conv1, b.conv2, b.sc_conv
+        a1, a2 = arith(c1), arith(c2)
+        below_bits = bi > 0 and out[bi - 1].bits
+        entry = "plain"
+        if c1.stride != 1 and o["fuse_s2_shortcut"]:
+            entry = "s2b3" if o["bf16x3"] and o["s2_b3"] and c1.s2b3 and c1.rows(B) < _ROW_LIMIT else "s2_fused"
+        # identity-shortcut blocks on the split-operand kernels: the residual ReLU's decisions travel as sign bits
+        # (8 bytes per row instead of re-reading y and writing / re-reading the masked gradient: csrc/bn.hip, conv_b3.hip)
+        bits = bool(o["relu_bits"]) and sc is None and c1.b3_full and a1 != "f32" and not o["fuse_bn_bwd"]
+        dgrad2_bn = "f32" if o["fuse_bn_bwd"] else "split" if o["fuse_bn_bwd_b3"] and a2 != "f32" else None
+        if c1.stride != 1:   # the sums of the block below's bn2 in the epilogue, when that block keeps sign bits
+            fused = entry == "s2b3" or (entry == "s2_fused" and c1.cin == 64 and c1.cout == 32)
+            dgrad1_bn = "split" if fused and o["fuse_bn_bwd_b3"] and below_bits else None
+        elif bits:
+            dgrad1_bn = "split" if o["fuse_bn_bwd_b3"] and below_bits else None
+        else:   # (the f32 epilogue needs y and c2 of the block below: identity shortcuts only; the stem keeps no convolution output)
+            dgrad1_bn = "f32" if o["fuse_bn_bwd"] and bi > 0 and blocks[bi - 1].sc_conv is None else None
+        s2_label = f"conv_{'s2b3' if entry == 's2b3' else 's2'}<{c1.cin},{c1.cout},9>" if c1.stride != 1 else None
+        out.append(_BlockChoice(entry, bool(o["virtual_a1"]) and a2 != "f32" and c2.b3_wgrad, bits, dgrad2_bn, dgrad1_bn,
+                                c1.stride != 1 and bool(o["fuse_s2_shortcut_wgrad"]),
+                                conv(c1, dgrad1_bn == "f32", s2_label), conv(c2, dgrad2_bn == "f32"), conv(sc) if sc is not None else None))
+    images = {(ch.arith if ch.arith == "h2" else "b3c", cs.name) for b, blk in zip(blocks, out)
+              for cs, ch in ((b.conv1, blk.conv1), (b.conv2, blk.conv2)) if ch.arith != "f32"}
+    images |= {("s2b3", b.conv1.name) for b, blk in zip(blocks, out) if blk.entry == "s2b3"}
+    return _TrainSchedule(tuple(out), bool(stem_onepass), frozenset(images), tuple(o.items()))
+
+
+def conv_s1_entry(arith, cin, in_coef=False, gated=False, bn=None):
+    """Entry point of a stride-1 3x3 / 1x1 convolution launch (forward, or data gradient = convolution with the flipped image).
+    in_coef: BatchNorm + ReLU applied to the input while staging; gated: the addend passes a sign-bit gate; bn: the epilogue
+    leaves the sums of a BatchNorm backward whose ReLU mask is recomputed from its input ("x"), read from sign bits ("bits")
+    or from its output ("y").  A combination the library has no kernel for is an error, not a fall-back."""
+    if arith == "h2" and bn != "y":
+        return "lad_conv_h2"
+    if arith == "b3" and in_coef and not gated and bn is None:
+        return "lad_conv_b3c_fwd_f32_bnrelu"
+    if arith == "b3" and gated and not in_coef and cin == 64 and bn in (None, "bits"):
+        return "lad_conv_b3_dgrad_bnstat" if bn else "lad_conv_b3_fwd_f32_gated"
+    if arith == "b3" and not in_coef and not gated and bn in (None, "x"):
+        return "lad_conv_b3c_dgrad_bnstat" if bn else "lad_conv_b3c_fwd_f32"
+    if arith == "f32" and not in_coef and not gated and bn != "bits":
+        return "lad_conv_fwd_bnstat" if bn else "lad_conv_fwd"
+    raise _hip.LadHipError(f"no stride-1 convolution kernel for arithmetic {arith!r} at {cin} channels with in_coef={in_coef}, "
+                           f"gated={gated}, bn={bn!r}")
+
+
+def conv_wgrad_entry(kind, in_coef=False, bn=False):
+    """Entry point of a stride-1 weight-gradient launch.  in_coef: BatchNorm + ReLU applied to the input while staging (a virtual
+    a1); bn: the launch applies the BatchNorm backward of the layer's own output and writes the gradient its data gradient reads."""
+    if kind == "h2":
+        return "lad_conv_wgrad_h2_bnbwd" if bn else "lad_conv_wgrad_h2"
+    if kind == "b3c" and not bn:
+        return "lad_conv_wgrad_b3c"
+    if kind == "f32" and not bn and not in_coef:
+        return "lad_conv_wgrad"
+    raise _hip.LadHipError(f"no weight-gradient kernel for {kind!r} with in_coef={in_coef}, bn={bn}")
+
+
 class ResNetEngine:
-    # flags that select kernels / fusions per layer: snapshotted by a train-mode forward, re-imposed during its backward
-    KERNEL_OPTIONS = ("bf16x3", "bf16x3_32", "f16x2", "f16x2_32", "relu_bits", "virtual_a1", "fuse_bn_bwd", "fuse_bn_bwd_b3", "fuse_bn_bwd_wgrad", "fuse_s2_shortcut",
+    # flags that select kernels / fusions per layer: a train-mode forward freezes them into its schedule (train_schedule), which its
+    # backward follows whatever happens to the attributes in between
+    KERNEL_OPTIONS =("bf16x3", "bf16x3_32", "f16x2", "f16x2_32", "relu_bits", "virtual_a1", "fuse_bn_bwd", "fuse_bn_bwd_b3", "fuse_bn_bwd_wgrad", "fuse_s2_shortcut",
                       "fuse_s2_shortcut_wgrad", "s2_b3")
 
     def __init__(self, model):
@@ -156,7 +308,7 @@ class ResNetEngine:
         self.fuse_s2_shortcut_wgrad = True   # a stride-2 block's 1x1 shortcut weight gradient as a tenth tap of conv1's
         self.defer_wgrad_sums = True   # the 19 per-layer sums of weight-gradient slabs in one launch (csrc/slab_reduce.hip)
         self._defer_on = False
-        self._cur_batch = 0
+        self._schedules = {}   # {(B, H, W, flag values): _TrainSchedule}
         self.relu_bits = True  # False: the residual ReLU mask is re-read from y and the shortcut gradient goes through HBM
         self._side = None
         self._side_readers = {}
@@ -259,28 +411,21 @@ class ResNetEngine:
         m = self.model
         bufs = dict(m.named_buffers())
 
-        def conv(name, cin, cout, taps, stride, h, w, bias):
-            s = _ConvSpec(name, cin, cout, taps, stride, h, w, bias)
-            s.w, s.gw = self._views[name + ".weight"]
-            if bias:
-                s.b, s.gb = self._views[name + ".bias"]
+        def conv(s):
+            """Attach a convolution's parameter views and allocate its packed weight images."""
+            s.w, s.gw = self._views[s.name + ".weight"]
+            if s.has_bias:
+                s.b, s.gb = self._views[s.name + ".bias"]
             dev = self.device
-            s.wt_f = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(cout, cin, taps, 0)), device=dev)
-            s.wt_d = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(cout, cin, taps, 1)), device=dev)
-            # b3: forward and data gradient on the split-operand kernel (64 or 32 channels); b3_full: 64 channels, where the
-            # weight gradient, the sign bits and the virtual activation exist as well
-            s.b3 = cin == cout and cin in (64, 32) and taps == 9 and stride == 1 and w <= 46 and self.base_widths
-            s.b3_full = s.b3 and cin == 64
-            s.b3_wgrad = s.b3 and (cin == 64 or w <= 30)   # the 32-channel weight-gradient window holds 64 rows + 2 (W + 2)
+            s.wt_f = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(s.cout, s.cin, s.taps, 0)), device=dev)
+            s.wt_d = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(s.cout, s.cin, s.taps, 1)), device=dev)
             if s.b3:  # split (bf16 x 3) weight images, forward and data gradient
-                nb = int(self.lib().lad_conv_b3c_packed_weight_bytes(cin))
+                nb = int(self.lib().lad_conv_b3c_packed_weight_bytes(s.cin))
                 s.wt3_f = torch.zeros(nb, device=dev, dtype=torch.uint8)
                 s.wt3_d = torch.zeros(nb, device=dev, dtype=torch.uint8)
-                nb2 = int(self.lib().lad_conv_h2_packed_weight_bytes(cin))   # ... and the f16 x 2 images (csrc/conv_h2.hip)
+                nb2 = int(self.lib().lad_conv_h2_packed_weight_bytes(s.cin))   # ... and the f16 x 2 images (csrc/conv_h2.hip)
                 s.wt2_f = torch.zeros(nb2, device=dev, dtype=torch.uint8)
                 s.wt2_d = torch.zeros(nb2, device=dev, dtype=torch.uint8)
-            # the 64 -> 32 stride-2 transition with its shortcut: one split image per direction (3x3 + 1x1 together)
-            s.s2b3 = cin == 64 and cout == 32 and taps == 9 and stride == 2 and (w + 1) // 2 <= 45 and self.base_widths
             if s.s2b3:
                 s.wt3_s2f = torch.zeros(int(self.lib().lad_conv_s2b3_packed_weight_bytes()), device=dev, dtype=torch.uint8)
                 s.wt3_s2d = torch.zeros(int(self.lib().lad_conv_s2b3_dgrad_packed_weight_bytes()), device=dev, dtype=torch.uint8)
@@ -298,13 +443,6 @@ class ResNetEngine:
         self.stem_w, self.stem_gw = self._views["conv1.weight"]
         self.stem_cout = self.stem_w.shape[0]
         self.stem_bn = bn("bn1", self.stem_cout)
-        self._block_defs = []
-        cin = self.stem_cout
-        for bi, cout in enumerate(m.filter_sizes, start=1):
-            for j in range(2):
-                stride = (1 if bi == 1 else 2) if j == 0 else 1
-                self._block_defs.append((f"block{bi}.{j}", cin if j == 0 else cout, cout, stride))
-            cin = cout
         self._conv_factory, self._bn_factory = conv, bn
         self._geom_specs = {}
         self.head_bn2 = bn("bn2", m.linear_layer_size)
@@ -330,26 +468,22 @@ class ResNetEngine:
         key = (H, W, partial)
         if key in self._geom_specs:
             return self._geom_specs[key]
-        blocks = []
-        h, w = H, W
-        for name, cin, cout, stride in self._block_defs:
-            b = _BlockSpec(name)
-            b.conv1 = self._conv_factory(name + ".conv1", cin, cout, 9, stride, h, w, True)
-            b.bn1 = self._bn_factory(name + ".bn1", cout)
-            h2, w2 = b.conv1.h_out, b.conv1.w_out
-            b.conv2 = self._conv_factory(name + ".conv2", cout, cout, 9, 1, h2, w2, True)
-            b.bn2 = self._bn_factory(name + ".bn2", cout)
-            if stride != 1 or cin != cout:
-                b.sc_conv = self._conv_factory(name + ".shortcut.0", cin, cout, 1, stride, h, w, False)
-                b.sc_bn = self._bn_factory(name + ".shortcut.1", cout)
-            blocks.append(b)
-            h, w = h2, w2
+        blocks = block_geometry(self.stem_cout, self.model.filter_sizes, H, W, self.base_widths)
+        for b in blocks:
+            self._conv_factory(b.conv1)
+            b.bn1 = self._bn_factory(b.name + ".bn1", b.conv1.cout)
+            self._conv_factory(b.conv2)
+            b.bn2 = self._bn_factory(b.name + ".bn2", b.conv1.cout)
+            if b.sc_conv is not None:
+                self._conv_factory(b.sc_conv)
+                b.sc_bn = self._bn_factory(b.name + ".shortcut.1", b.conv1.cout)
+        h, w = blocks[-1].conv2.h_out, blocks[-1].conv2.w_out
         if partial:
             self._geom_specs[key] = (blocks, h, w, 0)
             return self._geom_specs[key]
         if h < 4 or w < 4:
             raise ValueError(f"input ({H},{W}) is too small: AvgPool2d(4) sees a {h}x{w} map")
-        feat = self._block_defs[-1][2] * (h // 4) * (w // 4)
+        feat = blocks[-1].conv2.cout * (h // 4) * (w // 4)
         if feat != self.model.linear_layer_size:
             # same failure the reference hits (BatchNorm1d size check) for e.g. resnet_with_augmentation on (100,44)
             raise RuntimeError(f"running_mean should contain {feat} elements not {self.model.linear_layer_size}")
@@ -379,7 +513,7 @@ class ResNetEngine:
             p["stem_bwd_ws"] = torch.zeros(int(lib.lad_stem_bwd_onepass_workspace_floats()), device=dev)
         max_tiles = int(lib.lad_conv_num_tiles(B, H, W))
         for b in blocks:   # the stride-2 data gradient on the split-operand path writes its BatchNorm sums per parity class
-            if getattr(b.conv1, "s2b3", False):
+            if b.conv1.s2b3:
                 max_tiles = max(max_tiles, int(lib.lad_conv_s2b3_dgrad_partials(B, b.conv1.h_in, b.conv1.w_in)))
         cmax = max([64] + [b.conv1.cout for b in blocks])   # (128 at the resnet_with_augmentation widths)
         p["partials"] = torch.zeros(max_tiles * 2 * cmax, device=dev)
@@ -394,7 +528,7 @@ class ResNetEngine:
             if b.sc_conv is not None:
                 d["cs"] = act(ho, wo, co)
                 d["coefs"] = torch.zeros(6 * co, device=dev)
-            elif train and getattr(b.conv1, "b3_full", False):
+            elif train and b.conv1.b3_full:
                 # sign bits of y, one uint64 per row: what the backward pass needs of the residual ReLU (lad_bn_act_bits)
                 d["ybits"] = torch.zeros(int(lib.lad_act_rows(B, ho, wo)), device=dev, dtype=torch.int64)
             acts.append(d)
@@ -435,7 +569,7 @@ class ResNetEngine:
                 for cs in (b.conv1, b.conv2, b.sc_conv):
                     if cs is not None:
                         n = int(lib.lad_conv_wgrad_workspace_floats(cs.cin, cs.cout, cs.taps))
-                        if getattr(cs, "b3_wgrad", False):
+                        if cs.b3_wgrad:
                             n = max(n, int(lib.lad_conv_wgrad_b3c_workspace_floats(cs.cin)))
                         if cs.stride != 1:   # (conv1 of a stride-2 block also holds the shortcut's slabs in the fused launch)
                             n = int(lib.lad_conv_s2_wgrad_fused_workspace_floats(cs.cin, cs.cout)) if cs.taps == 9 else \
@@ -455,66 +589,51 @@ class ResNetEngine:
         `param.data`, a broadcast): every cached derivative (packed MFMA images, BatchNorm folds, fp16 packs) is stale."""
         self._weights_version += 1
 
-    def _pack_weights(self, blocks, need_dgrad):
-        """Refresh the packed MFMA weight images if the parameters changed since the last pack."""
+    def _pack_weights(self, blocks, need_dgrad, sched=None):
+        """Refresh the packed MFMA weight images the pass about to run reads, if the parameters changed since they were packed: the
+        exact-f32 images (forward only for eval-mode callers) and the split-operand images of a training step's schedule."""
         # a Parameter's _version moves when torch writes it in place (optimizer.step, load_state_dict, init; after
         # `p.data = view` the Parameter keeps its OWN counter, the flat buffer's does not move);
         # _weights_version moves when our own Adam kernel writes the flat buffer
         ver = (self._weights_version, sum(p._version for p in self._param_list))
-        arith = (self.bf16x3, self.f16x2, self.f16x2_32)
-        tag = (ver, need_dgrad, arith)
-        have = self._packed_version.get(id(blocks))
-        if have == tag or have == (ver, True, arith):
+        want = sched.images if sched is not None else frozenset()
+        have = self._packed_version.get(id(blocks))   # (parameter version, data-gradient images too, split images) of the last pack
+        fresh = have is not None and have[0] == ver
+        if fresh and have[1] >= need_dgrad and want <= have[2]:
             return
         lib, st = self.lib(), self._st()
-        key = (id(blocks), need_dgrad)
-        table = self._pack_tables.get(key)
-        if table is None:  # device table of {w, wt, cout, cin, taps, mode} records: pointers never move
-            import struct
-            recs = b""
-            n = 0
-            for blk in blocks:
-                for cs in (blk.conv1, blk.conv2, blk.sc_conv):
-                    if cs is None:
-                        continue
-                    for mode in ((0, 1) if need_dgrad else (0,)):
-                        wt = cs.wt_f if mode == 0 else cs.wt_d
-                        recs += struct.pack("<QQiiii", cs.w.data_ptr(), wt.data_ptr(), cs.cout, cs.cin, cs.taps, mode)
-                        n += 1
-            dev_tab = torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(self.device)
-            table = self._pack_tables[key] = (dev_tab, n)
-        _hip.check(lib.lad_conv_pack_weights_multi(_hip.ptr(table[0]), table[1], st), "lad_conv_pack_weights_multi")
-        if self.bf16x3:
-            for blk in blocks:
-                if getattr(blk.conv1, "s2b3", False) and blk.sc_conv is not None:
-                    c1 = blk.conv1
-                    if need_dgrad:   # both images in one launch
-                        _hip.check(lib.lad_conv_s2b3_pack_weights_pair(_hip.ptr(c1.w), _hip.ptr(blk.sc_conv.w), _hip.ptr(c1.wt3_s2f),
-                                                                       _hip.ptr(c1.wt3_s2d), st), "lad_conv_s2b3_pack_weights_pair")
-                    else:
-                        _hip.check(lib.lad_conv_s2b3_pack_weights(_hip.ptr(c1.w), _hip.ptr(blk.sc_conv.w), _hip.ptr(c1.wt3_s2f), st),
-                                   "lad_conv_s2b3_pack_weights")
-                for cs in (blk.conv1, blk.conv2):
-                    if cs.b3 and not self._h2(cs):
-                        _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(cs.w), 0, _hip.ptr(cs.wt3_f), cs.cin, st), "lad_conv_b3c_pack_weights")
-                        if need_dgrad:
-                            _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(cs.w), 1, _hip.ptr(cs.wt3_d), cs.cin, st),
-                                       "lad_conv_b3c_pack_weights")
+        if not (fresh and have[1] >= need_dgrad):
+            key = (id(blocks), need_dgrad)
+            table = self._pack_tables.get(key)
+            if table is None:  # device table of {w, wt, cout, cin, taps, mode} records: pointers never move
+                recs = [struct.pack("<QQiiii", cs.w.data_ptr(), (cs.wt_f if mode == 0 else cs.wt_d).data_ptr(), cs.cout, cs.cin, cs.taps, mode)
+                        for blk in blocks for cs in (blk.conv1, blk.conv2, blk.sc_conv) if cs is not None
+                        for mode in ((0, 1) if need_dgrad else (0,))]
+                table = self._pack_tables[key] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
+            _hip.check(lib.lad_conv_pack_weights_multi(_hip.ptr(table[0]), table[1], st), "lad_conv_pack_weights_multi")
+        shortcut = {blk.conv1.name: blk.sc_conv for blk in blocks}
+        convs = {cs.name: cs for blk in blocks for cs in (blk.conv1, blk.conv2)}
+        h2 = []
+        for kind, name in sorted(want - have[2] if fresh else want):   # (a training step: both directions of every image)
+            cs = convs[name]
+            if kind == "s2b3":   # both images in one launch
+                _hip.check(lib.lad_conv_s2b3_pack_weights_pair(_hip.ptr(cs.w), _hip.ptr(shortcut[name].w), _hip.ptr(cs.wt3_s2f),
+                                                               _hip.ptr(cs.wt3_s2d), st), "lad_conv_s2b3_pack_weights_pair")
+            elif kind == "b3c":
+                for mode, wt in ((0, cs.wt3_f), (1, cs.wt3_d)):
+                    _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(cs.w), mode, _hip.ptr(wt), cs.cin, st), "lad_conv_b3c_pack_weights")
+            else:
+                h2.append(cs)
+        if h2:
             # the f16 x 2 images: ONE launch packs every layer and direction of both channel counts (a record names its own; 16 workgroups
-            # per image)
-            convs = [cs for blk in blocks for cs in (blk.conv1, blk.conv2) if cs.b3 and cs.cin in (64, 32) and self._h2(cs)]
-            if convs:
-                hkey = (id(blocks), need_dgrad, "h2")
-                htab = self._pack_tables.get(hkey)
-                if htab is None:
-                    import struct
-                    recs = b""
-                    for cs in convs:
-                        for mode in ((0, 1) if need_dgrad else (0,)):
-                            recs += struct.pack("<QQii", cs.w.data_ptr(), (cs.wt2_f if mode == 0 else cs.wt2_d).data_ptr(), mode, cs.cin)
-                    htab = self._pack_tables[hkey] = (torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(self.device), len(recs) // 24)
-                _hip.check(lib.lad_conv_h2_pack_weights_multi(_hip.ptr(htab[0]), htab[1], 0, st), "lad_conv_h2_pack_weights_multi")
-        self._packed_version[id(blocks)] = tag
+            # per image).  The table is cached under the layers it lists: which ones run on f16 x 2 depends on the flags
+            hkey = (id(blocks), "h2", tuple(cs.name for cs in h2))
+            htab = self._pack_tables.get(hkey)
+            if htab is None:
+                recs = [struct.pack("<QQii", cs.w.data_ptr(), wt.data_ptr(), mode, cs.cin) for cs in h2 for mode, wt in ((0, cs.wt2_f), (1, cs.wt2_d))]
+                htab = self._pack_tables[hkey] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
+            _hip.check(lib.lad_conv_h2_pack_weights_multi(_hip.ptr(htab[0]), htab[1], 0, st), "lad_conv_h2_pack_weights_multi")
+        self._packed_version[id(blocks)] = (ver, need_dgrad or have[1], want | have[2]) if fresh else (ver, need_dgrad, want)
 
     def _mark(self, label):
         """HIP event on the launch stream (torch's current stream) when bench.py asked for per-kernel timing."""
@@ -530,86 +649,73 @@ class ResNetEngine:
             ev.record(torch.cuda.current_stream(self.device))
             self.kernel_events[label].append((start, ev))
 
-    def _b3_fits(self, cs):
-        # 64 channels (round 3): conv_b3x / wgrad_b3x address a tensor relative to the workgroup's own rows (64-bit bases),
-        # only row NUMBERS are 32-bit.  32 channels: the weight gradient still runs on the round-2 kernel, whose byte offsets
-        # are 32-bit (2 GiB per tensor = batch > 14,000 at 32 x 50 x 22); past that the layer runs on the exact-f32 kernels
-        rows = self._cur_batch * (cs.h_in + 1) * (cs.w_in + 1) + cs.w_in + 2
-        if cs.cin == 64:
-            return rows < (1 << 31) - (1 << 20)
-        return rows * cs.cin * 4 < (1 << 31) - (1 << 20)
+    def _schedule(self, B, H, W):
+        """The schedule of a training step under the flags as they are now (built once per batch size, geometry and flag values)."""
+        key = (B, H, W, self.stem_onepass) + tuple(getattr(self, k) for k in self.KERNEL_OPTIONS)
+        sched = self._schedules.get(key)
+        if sched is None:
+            sched = self._schedules[key] = train_schedule(self._blocks_for(H, W)[0], B, {k: getattr(self, k) for k in self.KERNEL_OPTIONS},
+                                                          self.stem_onepass)
+        return sched
 
-    def _use_b3(self, cs):
-        return self.bf16x3 and getattr(cs, "b3", False) and (cs.cin == 64 or self.bf16x3_32) and self._b3_fits(cs)
-
-    def _h2(self, cs):
-        """This split-operand layer runs on two f16 planes (csrc/conv_h2.hip) instead of three bf16 planes."""
-        return self.f16x2 and getattr(cs, "b3", False) and (cs.cin == 64 or self.f16x2_32)
-
-    def _conv_h2(self, cs, x, in_coef, wt, bias, addend, abits, out, partials, bn_x, bn_bits, bn_coef, B, h, w, what):
-        _hip.check(self.lib().lad_conv_h2(_hip.ptr(x), _hip.ptr(in_coef), _hip.ptr(wt), _hip.ptr(bias), _hip.ptr(addend), _hip.ptr(abits),
-                                          _hip.ptr(out), _hip.ptr(partials), _hip.ptr(bn_x), _hip.ptr(bn_bits), _hip.ptr(bn_coef),
-                                          B, h, w, cs.cin, self._st()), f"lad_conv_h2({what}) {cs.name}")
-
-    def _split_label(self, cs, transposed=False):
-        """Kernel label of a split-operand launch for bench.py's per-kernel events (the data gradient swaps cin / cout)."""
-        a, b = (cs.cout, cs.cin) if transposed else (cs.cin, cs.cout)
-        return f"{'conv_h2' if self._h2(cs) else 'conv_b3'}<{a},{b},{cs.taps}>"
-
-    def _use_b3_full(self, cs):
-        return self.bf16x3 and getattr(cs, "b3_full", False) and self._b3_fits(cs)
-
-    def _use_s2b3(self, b):
-        c1 = b.conv1
-        rows = self._cur_batch * (c1.h_in + 1) * (c1.w_in + 1) + c1.w_in + 2
-        return (self.bf16x3 and self.s2_b3 and self.fuse_s2_shortcut and getattr(c1, "s2b3", False) and b.sc_conv is not None
-                and rows < (1 << 31) - (1 << 20))
-
-    def _use_bits(self, b, a):
-        # identity-shortcut blocks on the split-operand kernels: the residual ReLU's decisions travel as sign bits
-        # (8 bytes per row instead of re-reading y and writing / re-reading the masked gradient: csrc/bn.hip, conv_b3.hip)
-        return self.relu_bits and "ybits" in a and b.sc_conv is None and self._use_b3_full(b.conv1) and not self.fuse_bn_bwd
-
-    def _conv(self, cs, x, out, partials, B):
-        lib, st = self.lib(), self._st()
-        label = self._split_label(cs) if self._use_b3(cs) else f"conv_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
+    def _conv_s1(self, cs, arith, direction, x, out, B, label=None, *, in_coef=None, bias=None, addend=None, abits=None, partials=None, bn=None):
+        """One stride-1 convolution launch on `arith`.  direction "fwd", or "dgrad": the data gradient = stride-1 convolution of dout
+        with the flipped / transposed image (GEMM K = cout, N = cin).  in_coef: BatchNorm + ReLU of the input, applied while staging;
+        addend (+ abits: gated by sign bits) is added to the result; bn = (x, mask, coef) of the BatchNorm whose backward consumes
+        `out`: its first pass rides in the epilogue and leaves per-tile sums in `partials` (mask None: ReLU decisions recomputed from
+        x; int64: sign bits; float: the BatchNorm's output y)."""
+        bx, bmask, bcoef = bn if bn is not None else (None, None, None)
+        fn = conv_s1_entry(arith, cs.cin, in_coef is not None, abits is not None,
+                           None if bn is None else "x" if bmask is None else "bits" if bmask.dtype == torch.int64 else "y")
+        P, fwd, h, w = _hip.ptr, direction == "fwd", cs.h_in, cs.w_in
+        wt = P(getattr(cs, {"h2": "wt2_", "b3": "wt3_", "f32": "wt_"}[arith] + ("f" if fwd else "d")))
+        cio = (cs.cin, cs.cout) if fwd else (cs.cout, cs.cin)
+        if fn == "lad_conv_h2":
+            args = (P(x), P(in_coef), wt, P(bias), P(addend), P(abits), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w, cs.cin)
+        elif fn == "lad_conv_b3c_fwd_f32":
+            args = (P(x), wt, P(bias), P(addend), P(out), P(partials), B, h, w, cs.cin)
+        elif fn == "lad_conv_b3c_fwd_f32_bnrelu":
+            args = (P(x), P(in_coef), wt, P(bias), P(out), P(partials), B, h, w, cs.cin)
+        elif fn == "lad_conv_b3c_dgrad_bnstat":   # ReLU decisions recomputed from the BatchNorm's input (csrc/conv_b3.hip, STAT epilogue)
+            args = (P(x), wt, P(addend), P(out), P(partials), P(bx), P(bcoef), B, h, w, cs.cin)
+        elif fn == "lad_conv_b3_fwd_f32_gated":
+            args = (P(x), wt, P(bias), P(addend), P(abits), P(out), P(partials), B, h, w)
+        elif fn == "lad_conv_b3_dgrad_bnstat":    # + the sums of a BatchNorm that kept its own sign bits
+            args = (P(x), wt, P(addend), P(abits), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w)
+        elif fn == "lad_conv_fwd":
+            args = (P(x), wt, P(bias), P(addend), P(out), P(partials), B, h, w, *cio, cs.taps)
+        else:
+            args = (P(x), wt, P(addend), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w, *cio, cs.taps)
         t0 = self._mark(label)
-        self._conv_raw(cs, x, out, partials, B, lib, st)
+        _hip.check(getattr(self.lib(), fn)(*args, self._st()), f"{fn}({direction}) {cs.name}")
         self._mark_end(label, t0)
 
-    def _conv_raw(self, cs, x, out, partials, B, lib, st):
-        if self._use_b3(cs) and self._h2(cs):
-            self._conv_h2(cs, x, None, cs.wt2_f, cs.b, None, None, out, partials, None, None, None, B, cs.h_in, cs.w_in, "fwd")
-        elif self._use_b3(cs):
-            _hip.check(lib.lad_conv_b3c_fwd_f32(_hip.ptr(x), _hip.ptr(cs.wt3_f), _hip.ptr(cs.b), None, _hip.ptr(out),
-                                                _hip.ptr(partials), B, cs.h_in, cs.w_in, cs.cin, st), "lad_conv_b3c_fwd_f32 " + cs.name)
-        elif cs.stride == 1:
-            _hip.check(lib.lad_conv_fwd(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(cs.b), None, _hip.ptr(out),
-                                        _hip.ptr(partials), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, st),
-                       "lad_conv_fwd " + cs.name)
-        else:
-            _hip.check(lib.lad_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(cs.b), _hip.ptr(out),
-                                           _hip.ptr(partials), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, st),
-                       "lad_conv_s2_fwd " + cs.name)
+    def _conv_fwd(self, cs, ch, x, out, partials, B, in_coef=None):
+        """Forward convolution with bias; `partials` receives the per-tile sums of the BatchNorm that follows."""
+        if cs.stride == 1:
+            self._conv_s1(cs, ch.arith, "fwd", x, out, B, ch.label_fwd, in_coef=in_coef, bias=cs.b, partials=partials)
+            return
+        t0 = self._mark(ch.label_fwd)
+        _hip.check(self.lib().lad_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(cs.b), _hip.ptr(out), _hip.ptr(partials),
+                                              B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, self._st()), "lad_conv_s2_fwd " + cs.name)
+        self._mark_end(ch.label_fwd, t0)
 
-    def _bn_coef(self, bn, coef, partials, B, h, w, train):
+    def _bn_coef(self, bn, coef, partials, B, h, w):
         lib, st = self.lib(), self._st()
-        if train:
-            n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
-            _hip.check(lib.lad_bn_finalize(_hip.ptr(partials), n_tiles, bn.c, B * h * w, _hip.ptr(bn.g), _hip.ptr(bn.b),
-                                           _hip.ptr(bn.rm), _hip.ptr(bn.rv), 0.1, _hip.ptr(coef), st),
-                       "lad_bn_finalize " + bn.name)
+        n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
+        _hip.check(lib.lad_bn_finalize(_hip.ptr(partials), n_tiles, bn.c, B * h * w, _hip.ptr(bn.g), _hip.ptr(bn.b),
+                                       _hip.ptr(bn.rm), _hip.ptr(bn.rv), 0.1, _hip.ptr(coef), st),
+                   "lad_bn_finalize " + bn.name)
         bn.coef = coef
 
-    def _bn_coef_pair(self, bn_a, coef_a, part_a, bn_b, coef_b, part_b, B, h, w, train):
+    def _bn_coef_pair(self, bn_a, coef_a, part_a, bn_b, coef_b, part_b, B, h, w):
         """_bn_coef for a stride-2 block's bn1 and its shortcut BatchNorm (sums of one shape, left by one launch) in one launch."""
-        if train:
-            lib, st = self.lib(), self._st()
-            n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
-            _hip.check(lib.lad_bn_finalize_pair(_hip.ptr(part_a), _hip.ptr(part_b), n_tiles, bn_a.c, B * h * w,
-                                                _hip.ptr(bn_a.g), _hip.ptr(bn_a.b), _hip.ptr(bn_a.rm), _hip.ptr(bn_a.rv), _hip.ptr(coef_a),
-                                                _hip.ptr(bn_b.g), _hip.ptr(bn_b.b), _hip.ptr(bn_b.rm), _hip.ptr(bn_b.rv), _hip.ptr(coef_b),
-                                                0.1, st), "lad_bn_finalize_pair " + bn_a.name)
+        lib, st = self.lib(), self._st()
+        n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
+        _hip.check(lib.lad_bn_finalize_pair(_hip.ptr(part_a), _hip.ptr(part_b), n_tiles, bn_a.c, B * h * w,
+                                            _hip.ptr(bn_a.g), _hip.ptr(bn_a.b), _hip.ptr(bn_a.rm), _hip.ptr(bn_a.rv), _hip.ptr(coef_a),
+                                            _hip.ptr(bn_b.g), _hip.ptr(bn_b.b), _hip.ptr(bn_b.rm), _hip.ptr(bn_b.rv), _hip.ptr(coef_b),
+                                            0.1, st), "lad_bn_finalize_pair " + bn_a.name)
         bn_a.coef = coef_a
         bn_b.coef = coef_b
 
@@ -639,21 +745,23 @@ class ResNetEngine:
             return torch.zeros(0, device=x.device)
         if not train:
             return self._forward_eval(x.view(-1), B, H, W, frame_stride=H, frames_avail=B * H)
-        if train and B < 2:
+        if B < 2:
             # torch: "Expected more than 1 value per channel when training" (BatchNorm1d on (1, F))
             raise ValueError("Expected more than 1 value per channel when training, got input size "
                              f"torch.Size([{B}, {self.model.linear_layer_size}])")
         lib, st = self.lib(), self._st()
-        self._cur_batch = B
         p = self._plan(B, H, W, True)
         blocks = p["blocks"]
-        self._pack_weights(blocks, need_dgrad=True)
+        # the kernel choices of this pass and of its backward, which reads them from the plan (virtual activations that were never
+        # written, sign bits that exist or not, packed weight images), whatever happens to the flags in between
+        sched = p["schedule"] = self._schedule(B, H, W)
+        self._pack_weights(blocks, need_dgrad=True, sched=sched)
         part = p["partials"]
         # stem (models.py:224)
         # The stem convolution (K = 9) is cheaper to recompute than to store: a statistics-only pass, then conv + BatchNorm +
         # ReLU in one kernel (the folded-BN stem kernel with the batch coefficients); the 596 MB convolution output is
         # never written, and backward() recomputes it the same way (lad_stem_bn_bwd_sums, lad_stem_wgrad_bn).
-        if self.stem_onepass:
+        if sched.stem_onepass:
             # ... and its batch statistics need no convolution pass at all: one input channel, so sum x and sum x^2 are combinations of 54
             # moments of the nine taps (csrc/stem.hip, lad_stem_bn_stats: one pass over the 9 MB of features)
             bn = self.stem_bn
@@ -661,114 +769,91 @@ class ResNetEngine:
                                              0.1, _hip.ptr(p["stem_coef"]), _hip.ptr(p["stem_mom"]), _hip.ptr(p["stem_mom_ws"]), B, H, W,
                                              self.stem_cout, st), "lad_stem_bn_stats")
             bn.coef = p["stem_coef"]
-            p["stem_mom_live"] = True
         else:
             _hip.check(lib.lad_stem_fwd(_hip.ptr(x), _hip.ptr(self.stem_w), None, _hip.ptr(part), B, H, W, self.stem_cout, st),
                        "lad_stem_fwd")
-            self._bn_coef(self.stem_bn, p["stem_coef"], part, B, H, W, train)
-            p["stem_mom_live"] = False
+            self._bn_coef(self.stem_bn, p["stem_coef"], part, B, H, W)
         c0 = self.stem_cout
         scale, shift = p["stem_coef"][:c0], p["stem_coef"][c0:2 * c0]
         _hip.check(lib.lad_stem_fwd_eval(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(scale), _hip.ptr(shift), _hip.ptr(p["stem_a"]),
                                          B, H, W, c0, H, B * H, st), "lad_stem_fwd_eval (train)")
         cur = p["stem_a"]
-        for b, a in zip(blocks, p["acts"]):
+        for b, ch, a in zip(blocks, sched.blocks, p["acts"]):
             ho, wo, co = b.conv1.h_out, b.conv1.w_out, b.conv1.cout
-            fuse_sc_fwd = b.sc_conv is not None and b.conv1.stride != 1 and self.fuse_s2_shortcut
-            if fuse_sc_fwd and train and self._use_s2b3(b):   # ... on the split-operand path (csrc/conv_b3.hip, conv_s2b3_kernel)
-                label = f"conv_s2b3<{b.conv1.cin},{b.conv1.cout},9>"
-                t0 = self._mark(label)
-                _hip.check(lib.lad_conv_s2b3_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.wt3_s2f), _hip.ptr(b.conv1.b), _hip.ptr(a["c1"]), _hip.ptr(part),
-                                                 _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]), B, b.conv1.h_in, b.conv1.w_in, st),
-                           "lad_conv_s2b3_fwd " + b.conv1.name)
-                self._mark_end(label, t0)
-            elif fuse_sc_fwd:   # conv1 and the 1x1 shortcut convolution in one launch (csrc/conv_mfma.hip, conv_s2_kernel<SC>)
-                label = f"conv_s2<{b.conv1.cin},{b.conv1.cout},9>"
-                t0 = self._mark(label)
-                _hip.check(lib.lad_conv_s2_fwd_fused(_hip.ptr(cur), _hip.ptr(b.conv1.wt_f), _hip.ptr(b.conv1.b), _hip.ptr(b.sc_conv.wt_f),
-                                                     _hip.ptr(a["c1"]), _hip.ptr(part), _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]),
-                                                     B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, b.conv1.cout, st),
-                           "lad_conv_s2_fwd_fused " + b.conv1.name)
-                self._mark_end(label, t0)
+            if ch.entry == "plain":
+                self._conv_fwd(b.conv1, ch.conv1, cur, a["c1"], part, B)
+                self._bn_coef(b.bn1, a["coef1"], part, B, ho, wo)
             else:
-                self._conv(b.conv1, cur, a["c1"], part, B)
-            if fuse_sc_fwd:   # bn1 and the shortcut's BatchNorm: one launch
-                self._bn_coef_pair(b.bn1, a["coef1"], part, b.sc_bn, a["coefs"], p["partials_sc"], B, ho, wo, train)
-            else:
-                self._bn_coef(b.bn1, a["coef1"], part, B, ho, wo, train)
-            a["a1_virtual"] = self.virtual_a1 and self._use_b3(b.conv2) and getattr(b.conv2, "b3_wgrad", False)
-            if a["a1_virtual"]:
+                t0 = self._mark(ch.conv1.label_fwd)
+                if ch.entry == "s2b3":   # conv1 and the 1x1 shortcut on the split-operand path (csrc/conv_b3.hip, conv_s2b3_kernel)
+                    _hip.check(lib.lad_conv_s2b3_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.wt3_s2f), _hip.ptr(b.conv1.b), _hip.ptr(a["c1"]), _hip.ptr(part),
+                                                     _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]), B, b.conv1.h_in, b.conv1.w_in, st),
+                               "lad_conv_s2b3_fwd " + b.conv1.name)
+                else:   # ... in one launch of the exact-f32 kernel (csrc/conv_mfma.hip, conv_s2_kernel<SC>)
+                    _hip.check(lib.lad_conv_s2_fwd_fused(_hip.ptr(cur), _hip.ptr(b.conv1.wt_f), _hip.ptr(b.conv1.b), _hip.ptr(b.sc_conv.wt_f),
+                                                         _hip.ptr(a["c1"]), _hip.ptr(part), _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]),
+                                                         B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, b.conv1.cout, st),
+                               "lad_conv_s2_fwd_fused " + b.conv1.name)
+                self._mark_end(ch.conv1.label_fwd, t0)
+                # bn1 and the shortcut's BatchNorm: one launch
+                self._bn_coef_pair(b.bn1, a["coef1"], part, b.sc_bn, a["coefs"], p["partials_sc"], B, ho, wo)
+            if ch.a1_virtual:
                 # relu(bn1(c1)) is formed while conv2 (and, in backward, its weight gradient) stage c1: never written
-                label = self._split_label(b.conv2)
-                t0 = self._mark(label)
-                if self._h2(b.conv2):
-                    self._conv_h2(b.conv2, a["c1"], a["coef1"], b.conv2.wt2_f, b.conv2.b, None, None, a["c2"], part, None, None, None,
-                                  B, ho, wo, "fwd, bnrelu")
-                else:
-                    _hip.check(lib.lad_conv_b3c_fwd_f32_bnrelu(_hip.ptr(a["c1"]), _hip.ptr(a["coef1"]), _hip.ptr(b.conv2.wt3_f),
-                                                               _hip.ptr(b.conv2.b), _hip.ptr(a["c2"]), _hip.ptr(part), B, ho, wo, b.conv2.cin, st),
-                               "lad_conv_b3c_fwd_f32_bnrelu " + b.conv2.name)
-                self._mark_end(label, t0)
+                self._conv_fwd(b.conv2, ch.conv2, a["c1"], a["c2"], part, B, in_coef=a["coef1"])
             else:
                 self._bn_act(a["c1"], a["coef1"], None, None, a["a1"], B, ho, wo, co)
-                self._conv(b.conv2, a["a1"], a["c2"], part, B)
-            self._bn_coef(b.bn2, a["coef2"], part, B, ho, wo, train)
+                self._conv_fwd(b.conv2, ch.conv2, a["a1"], a["c2"], part, B)
+            self._bn_coef(b.bn2, a["coef2"], part, B, ho, wo)
             if b.sc_conv is not None:
-                if not fuse_sc_fwd:
-                    self._conv(b.sc_conv, cur, a["cs"], part, B)
-                    self._bn_coef(b.sc_bn, a["coefs"], part, B, ho, wo, train)
+                if ch.entry == "plain":
+                    self._conv_fwd(b.sc_conv, ch.sc, cur, a["cs"], part, B)
+                    self._bn_coef(b.sc_bn, a["coefs"], part, B, ho, wo)
                 self._bn_act(a["c2"], a["coef2"], a["cs"], a["coefs"], a["y"], B, ho, wo, co)
-            elif self._use_bits(b, a):
+            elif ch.bits:
                 _hip.check(lib.lad_bn_act_bits(_hip.ptr(a["c2"]), _hip.ptr(a["coef2"]), _hip.ptr(cur), None, _hip.ptr(a["y"]),
                                                _hip.ptr(a["ybits"]), B, ho, wo, co, st), "lad_bn_act_bits")
-                a["bits_live"] = True
             else:
                 self._bn_act(a["c2"], a["coef2"], cur, None, a["y"], B, ho, wo, co)
-                a["bits_live"] = False
             a["x"] = cur
             cur = a["y"]
         last = blocks[-1].conv2
         _hip.check(lib.lad_pool_fwd(_hip.ptr(cur), _hip.ptr(p["pooled"]), B, p["h4"], p["w4"], last.cout, st), "lad_pool_fwd")
-        if True:
-            m1 = m2 = None
-            rng = isinstance(drop_masks, str) and drop_masks == "rng"
-            if drop_masks is not None and not rng:
-                m1, m2 = drop_masks
-                _hip.require_cuda(m1, "drop mask 1", torch.float32)
-                _hip.require_cuda(m2, "drop mask 2", torch.float32)
-                if tuple(m1.shape) != (B, p["feat"]) or tuple(m2.shape) != (B, 32):
-                    raise ValueError("dropout masks must be (B,linear_layer_size) and (B,32)")
-            if labels is not None:
-                _hip.require_cuda(labels, "labels", torch.int32)
-                if labels.numel() != B:
-                    raise ValueError("labels must have one entry per sample")
-            if rng:
-                # the head's launch draws the two dropout masks itself and advances the BatchNorm layers' num_batches_tracked: none of
-                # torch's four mask launches + one increment per step (csrc/head.hip, Philox4x32-10; round 6)
-                keep = 1.0 - float(self.model.dropout.p)
-                if keep < 1.0:
-                    if "m1" not in p:
-                        p["m1"] = torch.zeros((B, p["feat"]), device=self.device)
-                        p["m2"] = torch.zeros((B, 32), device=self.device)
-                    m1, m2 = p["m1"], p["m2"]
-                seed = int(torch.cuda.default_generators[self.device.index or 0].initial_seed()) & ((1 << 64) - 1)
-                if seed != self._rng_seed:       # (torch.manual_seed since the last draw: the sequence starts again)
-                    self._rng_seed = seed
-                    self._rng_counter.zero_()
-                _hip.check(lib.lad_head_fwd_train_rng(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2), keep,
-                                                      seed, _hip.ptr(self._rng_counter), _hip.ptr(self._nbt), int(self._nbt.numel()),
-                                                      _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]), _hip.ptr(p["probs"]),
-                                                      _hip.ptr(p["metrics"]), st), "lad_head_fwd_train_rng")
-            else:
-                _hip.check(lib.lad_head_fwd_train(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2),
-                                                  _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]),
-                                                  _hip.ptr(p["probs"]), _hip.ptr(p["metrics"]), st), "lad_head_fwd_train")
-            p["saved"] = (x, labels, m1, m2, B, H, W)
-            # the kernel choices of this forward pass: backward() must make the same ones (virtual activations that were
-            # never written, sign bits that exist or not, packed weight images), whatever happens to the flags in between
-            p["options"] = {k: getattr(self, k) for k in self.KERNEL_OPTIONS}
-            self._last_train_plan = p
-            self._train_forwards += 1  # running statistics moved: the eval-mode folds are stale
+        m1 = m2 = None
+        rng = isinstance(drop_masks, str) and drop_masks == "rng"
+        if drop_masks is not None and not rng:
+            m1, m2 = drop_masks
+            _hip.require_cuda(m1, "drop mask 1", torch.float32)
+            _hip.require_cuda(m2, "drop mask 2", torch.float32)
+            if tuple(m1.shape) != (B, p["feat"]) or tuple(m2.shape) != (B, 32):
+                raise ValueError("dropout masks must be (B,linear_layer_size) and (B,32)")
+        if labels is not None:
+            _hip.require_cuda(labels, "labels", torch.int32)
+            if labels.numel() != B:
+                raise ValueError("labels must have one entry per sample")
+        if rng:
+            # the head's launch draws the two dropout masks itself and advances the BatchNorm layers' num_batches_tracked: none of
+            # torch's four mask launches + one increment per step (csrc/head.hip, Philox4x32-10; round 6)
+            keep = 1.0 - float(self.model.dropout.p)
+            if keep < 1.0:
+                if "m1" not in p:
+                    p["m1"] = torch.zeros((B, p["feat"]), device=self.device)
+                    p["m2"] = torch.zeros((B, 32), device=self.device)
+                m1, m2 = p["m1"], p["m2"]
+            seed = int(torch.cuda.default_generators[self.device.index or 0].initial_seed()) & ((1 << 64) - 1)
+            if seed != self._rng_seed:       # (torch.manual_seed since the last draw: the sequence starts again)
+                self._rng_seed = seed
+                self._rng_counter.zero_()
+            _hip.check(lib.lad_head_fwd_train_rng(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2), keep,
+                                                  seed, _hip.ptr(self._rng_counter), _hip.ptr(self._nbt), int(self._nbt.numel()),
+                                                  _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]), _hip.ptr(p["probs"]),
+                                                  _hip.ptr(p["metrics"]), st), "lad_head_fwd_train_rng")
+        else:
+            _hip.check(lib.lad_head_fwd_train(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2),
+                                              _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]),
+                                              _hip.ptr(p["probs"]), _hip.ptr(p["metrics"]), st), "lad_head_fwd_train")
+        p["saved"] = (x, labels, m1, m2, B, H, W)
+        self._last_train_plan = p
+        self._train_forwards += 1  # running statistics moved: the eval-mode folds are stale
         return p["probs"]
 
     # ------------------------------------------------------------------------------------ eval (inference) path
@@ -1444,7 +1529,10 @@ class ResNetEngine:
         self._side_pending = True
 
     def _overlap_small_on(self):
-        return self._cur_batch >= 256 if self.overlap_wgrad_small == "auto" else bool(self.overlap_wgrad_small)
+        if self.overlap_wgrad_small != "auto":
+            return bool(self.overlap_wgrad_small)
+        p = getattr(self, "_last_train_plan", None)   # "auto": by the batch size of the step that runs (or ran last)
+        return p is not None and p["saved"][4] >= 256
 
     def _w(self, buf):
         """`buf` is about to be overwritten on the main stream: wait for a side-stream reader, if any."""
@@ -1459,77 +1547,32 @@ class ResNetEngine:
             self._side_pending = False
             self._side_readers.clear()
 
-    def _bnbwd_in_wgrad(self, cs):
-        """Does this layer's weight gradient apply the BatchNorm backward of its own output (csrc/wgrad_mfma.hip, DOBN)?  The 64-channel
-        f16 x 2 launches on the main stream only: the launch also writes the gradient its data-gradient launch reads."""
-        return (self.fuse_bn_bwd_wgrad and not self.overlap_wgrad and self._use_b3(cs) and getattr(cs, "b3_wgrad", False)
-                and self._h2(cs) and cs.cin == 64 and cs.cout == 64 and cs.stride == 1)
-
     def _wg_ws(self, p, cs):
         return p["wgrad_ws_of"][cs.name] if self._defer_on else p["wgrad_ws"]
 
-    def _wgrad(self, p, cs, x, dout, B, h, w):
-        lib = self.lib()
-        if self._use_b3(cs) and getattr(cs, "b3_wgrad", False):
-            # same split arithmetic as the forward / data-gradient launches of this layer (csrc/wgrad_mfma.hip)
-            fn = lib.lad_conv_wgrad_h2 if (self._h2(cs) and cs.cin == 64) else lib.lad_conv_wgrad_b3c
-            self._on_side(lambda st: _hip.check(fn(_hip.ptr(x), None, _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)),
-                                                                       _hip.ptr(cs.gw), _hip.ptr(cs.gb), B, h, w, cs.cin, st),
-                                                "lad_conv_wgrad_b3c " + cs.name), dout, small=cs.cin <= 32)
-            return
-        self._on_side(lambda st: _hip.check(lib.lad_conv_wgrad(_hip.ptr(x), _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)), _hip.ptr(cs.gw),
-                                                               _hip.ptr(cs.gb), B, h, w, cs.cin, cs.cout, cs.taps, st),
-                                            "lad_conv_wgrad " + cs.name), dout, small=cs.cin <= 32)
-
-    def _dgrad(self, cs, dout, addend, dx, B, h, w, bnstat=None, partials=None):
-        # data gradient = stride-1 convolution of dout with the flipped/transposed image: GEMM K = cout, N = cin.
-        # bnstat = (x, y or None, coef) of the BatchNorm whose backward consumes dx: its first pass rides in the epilogue.
-        fused_ok = bnstat is not None and self.fuse_bn_bwd and cs.taps == 9
-        fused_b3 = (bnstat is not None and not fused_ok and self.fuse_bn_bwd_b3 and self._use_b3(cs) and bnstat[1] is None)
-        label = self._split_label(cs, True) if (self._use_b3(cs) and not fused_ok) else f"conv_s1<{cs.cout},{cs.cin},{cs.taps}>"
-        t0 = self._mark(label)
-        if fused_b3:   # bn1 of a block: ReLU decisions recomputed from its input (csrc/conv_b3.hip, STAT epilogue)
-            bx, _, bcoef = bnstat
-            if self._h2(cs):
-                self._conv_h2(cs, dout, None, cs.wt2_d, None, addend, None, dx, partials, bx, None, bcoef, B, h, w, "dgrad, bnstat")
-            else:
-                _hip.check(self.lib().lad_conv_b3c_dgrad_bnstat(_hip.ptr(dout), _hip.ptr(cs.wt3_d), _hip.ptr(addend), _hip.ptr(dx),
-                                                                _hip.ptr(partials), _hip.ptr(bx), _hip.ptr(bcoef), B, h, w, cs.cin, self._st()),
-                           "lad_conv_b3c_dgrad_bnstat " + cs.name)
-            fused = True
-        elif fused_ok:
-            bx, by, bcoef = bnstat
-            _hip.check(self.lib().lad_conv_fwd_bnstat(_hip.ptr(dout), _hip.ptr(cs.wt_d), _hip.ptr(addend), _hip.ptr(dx),
-                                                      _hip.ptr(partials), _hip.ptr(bx), _hip.ptr(by), _hip.ptr(bcoef), B, h, w,
-                                                      cs.cout, cs.cin, cs.taps, self._st()), "lad_conv_fwd_bnstat " + cs.name)
-            fused = True
-        else:
-            self._dgrad_raw(cs, dout, addend, dx, B, h, w)
-            fused = False
-        self._mark_end(label, t0)
-        return fused
-
-    def _dgrad_raw(self, cs, dout, addend, dx, B, h, w):
-        if self._use_b3(cs) and self._h2(cs):
-            self._conv_h2(cs, dout, None, cs.wt2_d, None, addend, None, dx, None, None, None, None, B, h, w, "dgrad")
-            return
-        if self._use_b3(cs):
-            _hip.check(self.lib().lad_conv_b3c_fwd_f32(_hip.ptr(dout), _hip.ptr(cs.wt3_d), None, _hip.ptr(addend), _hip.ptr(dx), None,
-                                                       B, h, w, cs.cin, self._st()), "lad_conv_b3c_fwd_f32(dgrad) " + cs.name)
-            return
-        _hip.check(self.lib().lad_conv_fwd(_hip.ptr(dout), _hip.ptr(cs.wt_d), None, _hip.ptr(addend), _hip.ptr(dx), None, B, h, w,
-                                           cs.cout, cs.cin, cs.taps, self._st()), "lad_conv_fwd(dgrad) " + cs.name)
+    def _conv_wgrad(self, p, cs, kind, x, dout, B, *, in_coef=None, bn=None):
+        """Weight (and bias) gradient of a stride-1 convolution on `kind`, from its input x and the gradient dout of its output.
+        in_coef: x is the raw output of the convolution before (a virtual a1): BatchNorm + ReLU are applied while staging.
+        bn = (dy, bn_x, bits, coef): the launch first applies the element-wise half of the BatchNorm backward of the layer's own
+        output (p["bcoef"], left by lad_bn_bwd*) to dy and WRITES dout for the data-gradient launch: main stream only."""
+        fn = conv_wgrad_entry(kind, in_coef is not None, bn is not None)
+        lib, P, h, w, ws = self.lib(), _hip.ptr, cs.h_in, cs.w_in, self._wg_ws(p, cs)
+        if bn is not None:
+            dy, bx, bits, coef = bn
+            _hip.check(lib.lad_conv_wgrad_h2_bnbwd(P(x), P(in_coef), P(dy), P(bx), P(bits), P(coef), P(p["bcoef"]), P(dout), P(ws), P(cs.gw),
+                                                   P(cs.gb), B, h, w, cs.cin, self._st()), f"{fn} {cs.name}")
+        elif kind == "f32":
+            self._on_side(lambda st: _hip.check(lib.lad_conv_wgrad(P(x), P(dout), P(ws), P(cs.gw), P(cs.gb), B, h, w, cs.cin, cs.cout, cs.taps, st),
+                                                f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
+        else:   # same split arithmetic as the forward / data-gradient launches of this layer (csrc/wgrad_mfma.hip)
+            self._on_side(lambda st: _hip.check(getattr(lib, fn)(P(x), P(in_coef), P(dout), P(ws), P(cs.gw), P(cs.gb), B, h, w, cs.cin, st),
+                                                f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
 
     def backward(self, dprobs=None):
         """Gradient of the last train-mode forward into the flat gradient buffer (overwrites it).
 
         dprobs None: the loss is the mean BCE against the labels given to forward() (train.py:279-289);
         otherwise dprobs (B,) is dLoss/dprobs from autograd."""
-        p = getattr(self, "_last_train_plan", None)
-        live = {k: getattr(self, k) for k in self.KERNEL_OPTIONS}
-        if p is not None and "options" in p:
-            for k, v in p["options"].items():   # the forward pass's choices (see forward()); restored below
-                setattr(self, k, v)
         try:
             self._backward(dprobs)
         except BaseException:
@@ -1538,9 +1581,6 @@ class ResNetEngine:
                 self.lib().lad_wgrad_defer_begin()
                 self.lib().lad_wgrad_defer_flush(None)
             raise
-        finally:
-            for k, v in live.items():
-                setattr(self, k, v)
 
     def _backward(self, dprobs):
         p = getattr(self, "_last_train_plan", None)
@@ -1550,8 +1590,7 @@ class ResNetEngine:
         if dprobs is None and labels is None:
             raise _hip.LadHipError("backward() needs dprobs or labels passed to forward()")
         lib, st = self.lib(), self._st()
-        self._cur_batch = B
-        blocks, acts = p["blocks"], p["acts"]
+        blocks, acts, sched = p["blocks"], p["acts"], p["schedule"]
         last = blocks[-1].conv2
         # weight-gradient slab sums: one launch at the end instead of one per layer (not with the side stream: the flush
         # would have to follow launches on two streams)
@@ -1568,7 +1607,7 @@ class ResNetEngine:
         pre2 = False  # did the producer of `dy` already reduce for this block's bn2?
         pre2_tiles = 0  # ... into how many partials, if not one per 128-row tile (the stride-2 data gradient)
         for bi in range(len(blocks) - 1, -1, -1):
-            b, a = blocks[bi], acts[bi]
+            b, a, ch = blocks[bi], acts[bi], sched.blocks[bi]
             c1s, c2s = b.conv1, b.conv2
             ho, wo, co = c1s.h_out, c1s.w_out, c1s.cout
             hi, wi = c1s.h_in, c1s.w_in
@@ -1576,12 +1615,14 @@ class ResNetEngine:
             free = [t for t in G if t is not dy]
             aux, da1 = (self._w(a["aux"]) if "aux" in a else free[0]), free[1]
             dc2, dc1 = self._w(a["dc2"]), self._w(a["dc1"])
-            bits = a["ybits"] if a.get("bits_live") else None
+            bits = a["ybits"] if ch.bits else None
+            lower = acts[bi - 1]   # (the block below: read only where the schedule says that its bn2's sums ride in a launch of this one)
             # the element-wise half of a 64-channel BatchNorm backward rides in the weight-gradient launch that consumes it
-            # (lad_conv_wgrad_h2_bnbwd writes dc for the data-gradient launch): lad_bn_bwd* then only leaves the coefficients
-            fuse2 = bits is not None and self._bnbwd_in_wgrad(c2s)
-            fuse1 = c1s.stride == 1 and self._bnbwd_in_wgrad(c1s)
-            if bits is not None:
+            # (lad_conv_wgrad_h2_bnbwd writes dc for the data-gradient launch): lad_bn_bwd* then only leaves the coefficients.
+            # On the main stream only: the launch also writes the gradient its data-gradient launch reads
+            fuse2 = ch.bits and ch.conv2.wgrad_bn and not self.overlap_wgrad
+            fuse1 = ch.conv1.wgrad_bn and not self.overlap_wgrad
+            if ch.bits:
                 # dc2 only; the shortcut's share dy * [y > 0] is formed from dy and the bits in conv1's data gradient below
                 _hip.check(lib.lad_bn_bwd_bits(_hip.ptr(dy), _hip.ptr(bits), _hip.ptr(a["c2"]), _hip.ptr(a["coef2"]), _hip.ptr(b.bn2.g),
                                                None if fuse2 else _hip.ptr(dc2), _hip.ptr(b.bn2.gg), _hip.ptr(b.bn2.gb), _hip.ptr(p["bn_ws"]),
@@ -1593,129 +1634,86 @@ class ResNetEngine:
             else:
                 self._bn_bwd(p, b.bn2, dy, a["y"], a["c2"], a["coef2"], dc2, B, ho, wo, 1, mode=2, aux=aux,
                              sbn=b.sc_bn, xs=a["cs"], scoef=a["coefs"])
-            if fuse2:
-                xin, xcoef = (a["c1"], a["coef1"]) if a.get("a1_virtual") else (a["a1"], None)
-                _hip.check(lib.lad_conv_wgrad_h2_bnbwd(_hip.ptr(xin), _hip.ptr(xcoef), _hip.ptr(dy), _hip.ptr(a["c2"]), _hip.ptr(bits),
-                                                       _hip.ptr(a["coef2"]), _hip.ptr(p["bcoef"]), _hip.ptr(dc2), _hip.ptr(self._wg_ws(p, c2s)),
-                                                       _hip.ptr(c2s.gw), _hip.ptr(c2s.gb), B, ho, wo, c2s.cin, st),
-                           "lad_conv_wgrad_h2_bnbwd " + c2s.name)
-            elif a.get("a1_virtual"):
-                wfn = lib.lad_conv_wgrad_h2 if (self._h2(c2s) and c2s.cin == 64) else lib.lad_conv_wgrad_b3c
-                self._on_side(lambda sst, c2s=c2s, a=a, dc2=dc2, wfn=wfn: _hip.check(wfn(
-                    _hip.ptr(a["c1"]), _hip.ptr(a["coef1"]), _hip.ptr(dc2), _hip.ptr(self._wg_ws(p, c2s)), _hip.ptr(c2s.gw), _hip.ptr(c2s.gb),
-                    B, ho, wo, c2s.cin, sst), "lad_conv_wgrad_b3c(bnrelu) " + c2s.name), dc2, small=c2s.cin <= 32)
-            else:
-                self._wgrad(p, c2s, a["a1"], dc2, B, ho, wo)
-            pre1 = self._dgrad(c2s, dc2, None, da1, B, ho, wo, bnstat=(a["c1"], None, a["coef1"]), partials=p["partials"])
-            self._bn_bwd(p, b.bn1, da1, None, a["c1"], a["coef1"], None if fuse1 else dc1, B, ho, wo, 2, mode=0, pre=pre1)  # mask recomputed from c1
-            pre2, pre2_tiles = False, 0
-            if fuse1:
-                _hip.check(lib.lad_conv_wgrad_h2_bnbwd(_hip.ptr(a["x"]), None, _hip.ptr(da1), _hip.ptr(a["c1"]), None, _hip.ptr(a["coef1"]),
-                                                       _hip.ptr(p["bcoef"]), _hip.ptr(dc1), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.gw),
-                                                       _hip.ptr(c1s.gb), B, hi, wi, c1s.cin, st), "lad_conv_wgrad_h2_bnbwd " + c1s.name)
+            xin, xcoef = (a["c1"], a["coef1"]) if ch.a1_virtual else (a["a1"], None)
+            self._conv_wgrad(p, c2s, ch.conv2.wgrad, xin, dc2, B, in_coef=xcoef, bn=(dy, a["c2"], bits, a["coef2"]) if fuse2 else None)
+            # conv2's data gradient, with the first pass of bn1's backward in its epilogue (ReLU decisions recomputed from c1)
+            stat = (a["c1"], None, a["coef1"]) if ch.dgrad2_bn else None
+            self._conv_s1(c2s, "f32" if ch.dgrad2_bn == "f32" else ch.conv2.arith, "dgrad", dc2, da1, B, ch.conv2.label_dgrad,
+                          bn=stat, partials=p["partials"] if stat else None)
+            self._bn_bwd(p, b.bn1, da1, None, a["c1"], a["coef1"], None if fuse1 else dc1, B, ho, wo, 2, mode=0, pre=stat is not None)
+            if c1s.stride == 1:   # (with the BatchNorm backward on board, the launch writes dc1)
+                self._conv_wgrad(p, c1s, ch.conv1.wgrad, a["x"], dc1, B, bn=(da1, a["c1"], None, a["coef1"]) if fuse1 else None)
             if self.debug_capture is not None:
                 self.debug_capture[b.name] = {"dy": dy.clone(), "dc2": dc2.clone(), "aux": aux.clone() if bits is None else None, "da1": da1.clone(),
                                               "dc1": dc1.clone()}
             if c1s.stride == 1:
-                if not fuse1:
-                    self._wgrad(p, c1s, a["x"], dc1, B, hi, wi)
                 dx = dy  # dy is dead after the first bn_bwd; never aliases dc1 / aux
                 if b.sc_conv is not None:
                     # a stride-1 projection shortcut (resnet_with_augmentation's block1.0, 64 -> 128): aux is the gradient into its
                     # BatchNorm's input; the 1x1 convolution's data gradient (into da1, dead since bn1's backward) becomes the
                     # addend of conv1's data gradient below, its weight gradient reads aux
-                    sc = b.sc_conv
-                    self._wgrad(p, sc, a["x"], aux, B, hi, wi)
-                    self._dgrad_raw(sc, aux, None, da1, B, hi, wi)
+                    self._conv_wgrad(p, b.sc_conv, ch.sc.wgrad, a["x"], aux, B)
+                    self._conv_s1(b.sc_conv, ch.sc.arith, "dgrad", aux, da1, B)
                     aux = da1
-                # who consumes dx: the bn2 of the block below (identity shortcut only: its sums need y and c2), or the stem bn
-                if bi == 0:
-                    stat = None  # the stem's convolution output is not kept: its BatchNorm sums come from lad_stem_bn_bwd_sums
-                elif blocks[bi - 1].sc_conv is None:
-                    stat = (acts[bi - 1]["c2"], acts[bi - 1]["y"], acts[bi - 1]["coef2"])
-                else:
-                    stat = None
-                if bits is not None:
-                    label = self._split_label(c1s, True)
-                    t0 = self._mark(label)
-                    below = acts[bi - 1] if bi > 0 and acts[bi - 1].get("bits_live") else None
-                    if below is not None and self.fuse_bn_bwd_b3 and self._h2(c1s):
-                        self._conv_h2(c1s, dc1, None, c1s.wt2_d, None, dy, bits, dx, p["partials"], below["c2"], below["ybits"], below["coef2"],
-                                      B, hi, wi, "dgrad, gated, bnstat")
-                        pre2 = True
-                    elif self._h2(c1s):
-                        self._conv_h2(c1s, dc1, None, c1s.wt2_d, None, dy, bits, dx, None, None, None, None, B, hi, wi, "dgrad, gated")
-                        pre2 = False
-                    elif below is not None and self.fuse_bn_bwd_b3:   # + the sums of the block below's bn2 (its own sign bits)
-                        _hip.check(lib.lad_conv_b3_dgrad_bnstat(_hip.ptr(dc1), _hip.ptr(c1s.wt3_d), _hip.ptr(dy), _hip.ptr(bits), _hip.ptr(dx),
-                                                                _hip.ptr(p["partials"]), _hip.ptr(below["c2"]), _hip.ptr(below["ybits"]),
-                                                                _hip.ptr(below["coef2"]), B, hi, wi, st),
-                                   "lad_conv_b3_dgrad_bnstat " + c1s.name)
-                        pre2 = True
-                    else:
-                        _hip.check(lib.lad_conv_b3_fwd_f32_gated(_hip.ptr(dc1), _hip.ptr(c1s.wt3_d), None, _hip.ptr(dy), _hip.ptr(bits),
-                                                                 _hip.ptr(dx), None, B, hi, wi, st), "lad_conv_b3_fwd_f32_gated " + c1s.name)
-                        pre2 = False
-                    self._mark_end(label, t0)
-                else:
-                    pre2 = self._dgrad(c1s, dc1, aux, dx, B, hi, wi, bnstat=stat, partials=p["partials"])
-                dy = dx
+                # conv1's data gradient; who consumes dx: the bn2 of the block below (mask from its sign bits on the split-operand
+                # kernels, from its y on exact f32), or the stem's BatchNorm, whose sums come from lad_stem_bn_bwd_sums.  A block
+                # that keeps sign bits adds the shortcut's share dy * [y > 0] here
+                stat = (lower["c2"], lower["ybits" if ch.dgrad1_bn == "split" else "y"], lower["coef2"]) if ch.dgrad1_bn else None
+                self._conv_s1(c1s, "f32" if ch.dgrad1_bn == "f32" else ch.conv1.arith, "dgrad", dc1, dx, B, ch.conv1.label_dgrad,
+                              addend=dy if ch.bits else aux, abits=bits, bn=stat, partials=p["partials"] if stat else None)
+                pre2, pre2_tiles = stat is not None, 0
             else:
                 # stride-2 block: gradients of conv1 and of the 1x1 shortcut at their true cost (csrc/conv_s2_bwd.hip)
-                GI = p["g"][(hi, wi)]
-                dx = GI[0]
+                dx = p["g"][(hi, wi)][0]
                 sc = b.sc_conv
-                fuse_sc = self.fuse_s2_shortcut_wgrad
-                if fuse_sc:   # conv1's and the shortcut's weight gradients in one launch (same input rows; csrc/conv_s2_bwd.hip)
+
+                def s2_wgrad(cs, dout, xin=a["x"]):   # one convolution's weight gradient in a launch of its own
+                    self._on_side(lambda sst: _hip.check(lib.lad_conv_s2_wgrad(
+                        _hip.ptr(xin), _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)), _hip.ptr(cs.gw), _hip.ptr(cs.gb), B, hi, wi, cs.cin, cs.cout,
+                        cs.taps, sst), "lad_conv_s2_wgrad " + cs.name), dout, small=cs.cin <= 32)
+
+                if ch.sc_wgrad_fused:   # conv1's and the shortcut's weight gradients in one launch (same input rows; csrc/conv_s2_bwd.hip)
                     self._on_side(lambda sst, c1s=c1s, sc=sc, dc1=dc1, aux=aux, xin=a["x"]: _hip.check(lib.lad_conv_s2_wgrad_fused(
                         _hip.ptr(xin), _hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.gw), _hip.ptr(c1s.gb),
                         _hip.ptr(sc.gw), B, hi, wi, c1s.cin, c1s.cout, sst), "lad_conv_s2_wgrad_fused " + c1s.name), dc1, small=c1s.cin <= 32)
                     if dc1.data_ptr() in self._side_readers:   # (it ran on the side stream) the launch reads aux as well
                         self._side_readers[aux.data_ptr()] = self._side_readers[dc1.data_ptr()]
                 else:
-                    self._on_side(lambda sst, c1s=c1s, dc1=dc1, xin=a["x"]: _hip.check(lib.lad_conv_s2_wgrad(
-                        _hip.ptr(xin), _hip.ptr(dc1), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.gw), _hip.ptr(c1s.gb), B, hi, wi,
-                        c1s.cin, c1s.cout, 9, sst), "lad_conv_s2_wgrad " + c1s.name), dc1, small=c1s.cin <= 32)
-                below = acts[bi - 1] if bi > 0 and acts[bi - 1].get("bits_live") else None
-                if self._use_s2b3(b):
-                    # both data gradients on the split-operand path, parity class by parity class (dgrad_s2b3_kernel); with the
-                    # sums of the block below's bn2 in the epilogue when that block keeps sign bits
-                    stat = self.fuse_bn_bwd_b3 and below is not None
+                    s2_wgrad(c1s, dc1)
+                # with the sums of the block below's bn2 in the epilogue when that block keeps sign bits (dx is final when it is written)
+                stat = (lower["c2"], lower["ybits"], lower["coef2"]) if ch.dgrad1_bn else (None, None, None)
+                n_part = 0
+                if ch.entry == "s2b3":
+                    # both data gradients on the split-operand path, parity class by parity class (dgrad_s2b3_kernel)
                     n_part = int(lib.lad_conv_s2b3_dgrad_partials(B, hi, wi))
-                    assert not stat or n_part * 2 * 64 <= p["partials"].numel()
+                    assert not ch.dgrad1_bn or n_part * 2 * 64 <= p["partials"].numel()
                     _hip.check(lib.lad_conv_s2b3_dgrad(_hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(c1s.wt3_s2d), _hip.ptr(dx),
-                                                       _hip.ptr(p["partials"]) if stat else None, _hip.ptr(below["c2"]) if stat else None,
-                                                       _hip.ptr(below["ybits"]) if stat else None, _hip.ptr(below["coef2"]) if stat else None,
-                                                       B, hi, wi, st), "lad_conv_s2b3_dgrad " + c1s.name)
-                    if stat:
-                        pre2, pre2_tiles = True, n_part
-                elif self.fuse_s2_shortcut and self.fuse_bn_bwd_b3 and below is not None and c1s.cin == 64 and c1s.cout == 32:
-                    # ... and dx is final when it is written: the sums of the block below's bn2 ride in the epilogue
+                                                       _hip.ptr(p["partials"]) if ch.dgrad1_bn else None, _hip.ptr(stat[0]), _hip.ptr(stat[1]),
+                                                       _hip.ptr(stat[2]), B, hi, wi, st), "lad_conv_s2b3_dgrad " + c1s.name)
+                elif ch.entry == "s2_fused" and ch.dgrad1_bn:
                     n_part = int(lib.lad_conv_s2_dgrad_partials(B, hi, wi))
                     assert n_part * 2 * 64 <= p["partials"].numel()
                     _hip.check(lib.lad_conv_s2_dgrad_fused_bnstat(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx),
-                                                                  _hip.ptr(p["partials"]), _hip.ptr(below["c2"]), _hip.ptr(below["ybits"]),
-                                                                  _hip.ptr(below["coef2"]), B, hi, wi, c1s.cin, c1s.cout, st),
+                                                                  _hip.ptr(p["partials"]), _hip.ptr(stat[0]), _hip.ptr(stat[1]),
+                                                                  _hip.ptr(stat[2]), B, hi, wi, c1s.cin, c1s.cout, st),
                                "lad_conv_s2_dgrad_fused_bnstat " + c1s.name)
-                    pre2, pre2_tiles = True, n_part
-                elif self.fuse_s2_shortcut:   # both data gradients in one launch, dx written once
+                elif ch.entry == "s2_fused":   # both data gradients in one launch, dx written once
                     _hip.check(lib.lad_conv_s2_dgrad_fused(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx),
                                                            B, hi, wi, c1s.cin, c1s.cout, st), "lad_conv_s2_dgrad_fused " + c1s.name)
                 else:
                     _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(dx), B, hi, wi, c1s.cin, c1s.cout, 9, 0,
                                                      st), "lad_conv_s2_dgrad " + c1s.name)
-                if not fuse_sc:
-                    self._on_side(lambda sst, sc=sc, aux=aux, xin=a["x"]: _hip.check(lib.lad_conv_s2_wgrad(
-                        _hip.ptr(xin), _hip.ptr(aux), _hip.ptr(self._wg_ws(p, sc)), _hip.ptr(sc.gw), None, B, hi, wi, sc.cin, sc.cout, 1,
-                        sst), "lad_conv_s2_wgrad " + sc.name), aux, small=sc.cin <= 32)
-                if not self.fuse_s2_shortcut:
+                pre2, pre2_tiles = ch.dgrad1_bn is not None, n_part
+                if not ch.sc_wgrad_fused:
+                    s2_wgrad(sc, aux)
+                if ch.entry == "plain":
                     _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx), B, hi, wi, sc.cin, sc.cout, 1, 1, st),
                                "lad_conv_s2_dgrad " + sc.name)
-                dy = dx
+            dy = dx
         # stem: bn1 + conv1 weight gradient.  The input needs no gradient and the convolution is recomputed from the features:
         # sums (x recomputed) -> lad_bn_bwd finalises them into dgamma / dbeta / bcoef (dx = None: nothing to apply) ->
         # the weight-gradient kernel applies the BatchNorm backward on the fly.  Neither x nor dz ever exist in HBM.
-        if p.get("stem_mom_live"):
+        if sched.stem_onepass:
             # ONE pass over dy (the BatchNorm's sums and the centred tap products together), the rest from the forward's moments
             bn = self.stem_bn
             _hip.check(lib.lad_stem_bwd_onepass(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(dy), _hip.ptr(p["stem_coef"]), _hip.ptr(bn.g),
@@ -1754,9 +1752,9 @@ class ResNetEngine:
             return (body > 0).permute(0, 3, 1, 2).cpu()
 
         out = {"stem": unpack(p["stem_a"], H, W, self.stem_cout)}
-        for b, a in zip(p["blocks"], p["acts"]):
+        for b, ch, a in zip(p["blocks"], p["schedule"].blocks, p["acts"]):
             ho, wo, co = b.conv1.h_out, b.conv1.w_out, b.conv1.cout
-            if a.get("a1_virtual"):
+            if ch.a1_virtual:
                 # never stored: the sign of the kernels' fmaf(c1, scale, shift), taken from the same expression in double (the
                 # product is exact there and the sum keeps its sign; a separate fp32 multiply + add does NOT always agree)
                 c = a["c1"][:B * (ho + 1) * (wo + 1) * co].view(B, ho + 1, wo + 1, co)[:, 1:, 1:, :].double()

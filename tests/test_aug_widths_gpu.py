@@ -286,6 +286,8 @@ def test_kernel_selection_is_exact_f32_only():
         for cs in (b.conv1, b.conv2, b.sc_conv):
             if cs is not None:
                 assert not cs.b3 and not cs.s2b3, cs.name
+    for b in eng._last_train_plan["schedule"].blocks:
+        assert all(c.arith == "f32" and c.wgrad == "f32" for c in (b.conv1, b.conv2, b.sc) if c is not None)
 
 
 def test_eval_probabilities_match_the_reference_golden(golden_dir):

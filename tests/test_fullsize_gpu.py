@@ -126,8 +126,7 @@ def test_batch_2048_stays_on_the_split_operand_kernels_and_agrees_with_f32():
     for b3 in (True, False):
         eng.bf16x3 = b3
         probs = eng.forward(x, train=True, labels=t).clone()
-        blocks = eng._last_train_plan["blocks"]
-        assert eng._use_b3(blocks[0].conv1) == b3
+        assert (eng._last_train_plan["schedule"].blocks[0].conv1.arith != "f32") == b3
         eng.backward(None)
         res[b3] = (probs, {k: v.clone() for k, v in eng.grad_views().items()})
     eng.bf16x3 = True

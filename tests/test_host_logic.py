@@ -251,3 +251,127 @@ def test_librosa_convention_host_tables_are_the_third_party_goldens(golden_dir):
     assert np.abs(feats.dct2_ortho(44, 20) - scipy_fft.dct(eye, type=2, norm="ortho", axis=0)[:20].T).max() < 1e-14
     sig = pytest.importorskip("scipy.signal")
     assert np.abs(feats.hann_window_periodic(400) - sig.get_window("hann", 400, fftbins=True)).max() < 1e-15
+
+
+# ------------------------------------------------------------------------------------------ the training schedule (engine.train_schedule)
+_ALL_ON = dict(bf16x3=True, bf16x3_32=True, f16x2=True, f16x2_32=True, relu_bits=True, virtual_a1=True, fuse_bn_bwd=False, fuse_bn_bwd_b3=True,
+               fuse_bn_bwd_wgrad=True, fuse_s2_shortcut=True, fuse_s2_shortcut_wgrad=True, s2_b3=True)   # ResNetEngine's defaults
+
+
+def _rows(sched):
+    """A schedule as one dict per block; a convolution as "<forward / data-gradient arithmetic>/<weight-gradient kernel>[+bn]"."""
+    def conv(c):
+        return None if c is None else f"{c.arith}/{c.wgrad}{'+bn' if c.wgrad_bn else ''}"
+
+    return [dict(entry=b.entry, a1_virtual=b.a1_virtual, bits=b.bits, dgrad2_bn=b.dgrad2_bn, dgrad1_bn=b.dgrad1_bn, sc_wgrad_fused=b.sc_wgrad_fused,
+                 c1=conv(b.conv1), c2=conv(b.conv2), sc=conv(b.sc)) for b in sched.blocks]
+
+
+def _row(entry, a1_virtual, bits, dgrad2_bn, dgrad1_bn, sc_wgrad_fused, c1, c2, sc):
+    return dict(entry=entry, a1_virtual=a1_virtual, bits=bits, dgrad2_bn=dgrad2_bn, dgrad1_bn=dgrad1_bn, sc_wgrad_fused=sc_wgrad_fused, c1=c1, c2=c2, sc=sc)
+
+
+def _launchable(engine, blocks, sched):
+    """Every stride-1 convolution and weight-gradient launch the engine makes from this schedule has an entry point."""
+    mask = {None: None, "split": "bits", "f32": "y"}
+    for b, ch in zip(blocks, sched.blocks):
+        if b.conv1.stride == 1:
+            engine.conv_s1_entry(ch.conv1.arith, b.conv1.cin)
+            engine.conv_wgrad_entry(ch.conv1.wgrad, bn=ch.conv1.wgrad_bn)
+            engine.conv_s1_entry("f32" if ch.dgrad1_bn == "f32" else ch.conv1.arith, b.conv1.cin, gated=ch.bits, bn=mask[ch.dgrad1_bn])
+            if ch.sc is not None:
+                engine.conv_s1_entry(ch.sc.arith, b.sc_conv.cin)
+                engine.conv_wgrad_entry(ch.sc.wgrad)
+        engine.conv_s1_entry(ch.conv2.arith, b.conv2.cin, in_coef=ch.a1_virtual)
+        engine.conv_wgrad_entry(ch.conv2.wgrad, in_coef=ch.a1_virtual, bn=ch.bits and ch.conv2.wgrad_bn)
+        engine.conv_s1_entry("f32" if ch.dgrad2_bn == "f32" else ch.conv2.arith, b.conv2.cin, bn="x" if ch.dgrad2_bn else None)
+
+
+def test_train_schedule_of_resnet_base_and_of_the_augmentation_widths():
+    """engine.train_schedule: the kernels of a training step as a literal table -- resnet_base on (100, 44) with the default flags at
+    four batch sizes (past 2 GiB per tensor the 32-channel layers leave the split-operand kernels, the 64-channel ones do not), every
+    flag flipped alone at batch 512 (which fields move, and no others), resnet_with_augmentation on (128, 44) (exact f32, nothing
+    fused).  No schedule asks for a launch the library has no entry point for; such a combination is an error."""
+    import _hip
+    import engine
+    base = engine.block_geometry(64, [64, 32, 16, 16], 100, 44, True)
+    assert [(b.name, b.conv1.cin, b.conv1.cout, b.conv1.stride, b.conv1.h_in, b.conv1.w_in, b.sc_conv is not None) for b in base] == [
+        ("block1.0", 64, 64, 1, 100, 44, False), ("block1.1", 64, 64, 1, 100, 44, False),
+        ("block2.0", 64, 32, 2, 100, 44, True), ("block2.1", 32, 32, 1, 50, 22, False),
+        ("block3.0", 32, 16, 2, 50, 22, True), ("block3.1", 16, 16, 1, 25, 11, False),
+        ("block4.0", 16, 16, 2, 25, 11, True), ("block4.1", 16, 16, 1, 13, 6, False)]
+    small = [_row("s2_fused", False, False, None, None, True, "f32/f32", "f32/f32", "f32/f32"),
+             _row("plain", False, False, None, None, False, "f32/f32", "f32/f32", None)] * 2
+    default = [_row("plain", True, True, "split", None, False, "h2/h2+bn", "h2/h2+bn", None),
+               _row("plain", True, True, "split", "split", False, "h2/h2+bn", "h2/h2+bn", None),
+               _row("s2b3", True, False, "split", "split", True, "f32/f32", "h2/b3c", "f32/f32"),
+               _row("plain", True, False, "split", None, False, "h2/b3c", "h2/b3c", None)] + small
+    for B in (32, 512, 2048):
+        sched = engine.train_schedule(base, B, _ALL_ON, True)
+        assert _rows(sched) == default, B
+        assert sched.stem_onepass is True and dict(sched.opts) == _ALL_ON
+        assert sched.images == {("h2", n) for n in ("block1.0.conv1", "block1.0.conv2", "block1.1.conv1", "block1.1.conv2", "block2.0.conv2",
+                                                    "block2.1.conv1", "block2.1.conv2")} | {("s2b3", "block2.0.conv1")}
+        _launchable(engine, base, sched)
+    labels = [(b.conv1.label_fwd, b.conv1.label_dgrad, b.conv2.label_fwd, b.conv2.label_dgrad) for b in sched.blocks]
+    assert labels[:4] == [("conv_h2<64,64,9>",) * 4, ("conv_h2<64,64,9>",) * 4,
+                          ("conv_s2b3<64,32,9>", "conv_s1<32,64,9>", "conv_h2<32,32,9>", "conv_h2<32,32,9>"), ("conv_h2<32,32,9>",) * 4]
+    assert labels[4] == ("conv_s2<32,16,9>", "conv_s1<16,32,9>", "conv_s1<16,16,9>", "conv_s1<16,16,9>") and sched.blocks[4].sc.label_fwd == "conv_s2<32,16,1>"
+    # batch 16000: 32 x 50 x 22 floats per item pass 2 GiB (the 32-channel kernels' 32-bit byte offsets); 64 channels count rows
+    sched = engine.train_schedule(base, 16000, _ALL_ON, True)
+    assert _rows(sched) == default[:2] + [_row("s2b3", False, False, None, "split", True, "f32/f32", "f32/f32", "f32/f32"),
+                                          _row("plain", False, False, None, None, False, "f32/f32", "f32/f32", None)] + small
+    assert sched.images == {("h2", n) for n in ("block1.0.conv1", "block1.0.conv2", "block1.1.conv1", "block1.1.conv2")} | {("s2b3", "block2.0.conv1")}
+    _launchable(engine, base, sched)
+    # one flag flipped at batch 512: {block: fields that move}
+    f32 = dict(c1="f32/f32", c2="f32/f32")
+    moves = {
+        "bf16x3": {0: dict(a1_virtual=False, bits=False, dgrad2_bn=None, **f32), 1: dict(a1_virtual=False, bits=False, dgrad2_bn=None, dgrad1_bn=None, **f32),
+                   2: dict(entry="s2_fused", a1_virtual=False, dgrad2_bn=None, dgrad1_bn=None, c2="f32/f32"), 3: dict(a1_virtual=False, dgrad2_bn=None, **f32)},
+        "bf16x3_32": {2: dict(a1_virtual=False, dgrad2_bn=None, c2="f32/f32"), 3: dict(a1_virtual=False, dgrad2_bn=None, **f32)},
+        "f16x2": {0: dict(c1="b3/b3c", c2="b3/b3c"), 1: dict(c1="b3/b3c", c2="b3/b3c"), 2: dict(c2="b3/b3c"), 3: dict(c1="b3/b3c", c2="b3/b3c")},
+        "f16x2_32": {2: dict(c2="b3/b3c"), 3: dict(c1="b3/b3c", c2="b3/b3c")},
+        "relu_bits": {0: dict(bits=False), 1: dict(bits=False, dgrad1_bn=None), 2: dict(dgrad1_bn=None)},
+        "virtual_a1": {i: dict(a1_virtual=False) for i in range(4)},
+        # (on: exact-f32 epilogues wherever a BatchNorm's x and y are both in HBM; no sign bits then)
+        "fuse_bn_bwd": {0: dict(bits=False, dgrad2_bn="f32"), 1: dict(bits=False, dgrad2_bn="f32", dgrad1_bn="f32"), 2: dict(dgrad2_bn="f32", dgrad1_bn=None),
+                        3: dict(dgrad2_bn="f32"), 4: dict(dgrad2_bn="f32"), 5: dict(dgrad2_bn="f32"), 6: dict(dgrad2_bn="f32"), 7: dict(dgrad2_bn="f32")},
+        "fuse_bn_bwd_b3": {0: dict(dgrad2_bn=None), 1: dict(dgrad2_bn=None, dgrad1_bn=None), 2: dict(dgrad2_bn=None, dgrad1_bn=None), 3: dict(dgrad2_bn=None)},
+        "fuse_bn_bwd_wgrad": {0: dict(c1="h2/h2", c2="h2/h2"), 1: dict(c1="h2/h2", c2="h2/h2")},
+        "fuse_s2_shortcut": {2: dict(entry="plain", dgrad1_bn=None), 4: dict(entry="plain"), 6: dict(entry="plain")},
+        "fuse_s2_shortcut_wgrad": {i: dict(sc_wgrad_fused=False) for i in (2, 4, 6)},
+        "s2_b3": {2: dict(entry="s2_fused")},
+    }
+    assert sorted(moves) == sorted(engine.ResNetEngine.KERNEL_OPTIONS)
+    for flag, moved in moves.items():
+        sched = engine.train_schedule(base, 512, {**_ALL_ON, flag: not _ALL_ON[flag]}, True)
+        assert _rows(sched) == [{**row, **moved.get(i, {})} for i, row in enumerate(default)], flag
+        assert sched.stem_onepass is True
+        _launchable(engine, base, sched)
+    assert engine.train_schedule(base, 512, {**_ALL_ON, "fuse_bn_bwd": True}, True).blocks[1].conv1.label_dgrad == "conv_s1<64,64,9>"
+    sched = engine.train_schedule(base, 512, _ALL_ON, False)
+    assert sched.stem_onepass is False and _rows(sched) == default
+    # resnet_with_augmentation: whatever the flags say, exact f32 and no split-operand fusion; with the engine's own (all off) nothing at all
+    aug = engine.block_geometry(64, [128, 64, 32, 32], 128, 44, False)
+    assert [(b.conv1.cin, b.conv1.cout, b.conv1.stride, b.sc_conv is not None) for b in aug][:3] == [(64, 128, 1, True), (128, 128, 1, False), (128, 64, 2, True)]
+    sched = engine.train_schedule(aug, 32, dict.fromkeys(_ALL_ON, False), True)
+    assert _rows(sched) == [_row("plain", False, False, None, None, False, "f32/f32", "f32/f32", "f32/f32"),
+                            _row("plain", False, False, None, None, False, "f32/f32", "f32/f32", None)] * 4
+    assert sched.images == frozenset()
+    _launchable(engine, aug, sched)
+    sched = engine.train_schedule(aug, 32, _ALL_ON, True)
+    assert all(c is None or c == "f32/f32" for r in _rows(sched) for c in (r["c1"], r["c2"], r["sc"]))
+    assert not any(r["a1_virtual"] or r["bits"] or r["entry"] == "s2b3" or r["dgrad2_bn"] or r["dgrad1_bn"] for r in _rows(sched)) and not sched.images
+    _launchable(engine, aug, sched)
+    # what the library has no kernel for is refused, not replaced
+    assert engine.conv_s1_entry("h2", 64, gated=True, bn="bits") == "lad_conv_h2"
+    assert engine.conv_s1_entry("b3", 64, gated=True, bn="bits") == "lad_conv_b3_dgrad_bnstat"
+    assert engine.conv_s1_entry("f32", 16, bn="y") == "lad_conv_fwd_bnstat"
+    assert engine.conv_wgrad_entry("h2", in_coef=True, bn=True) == "lad_conv_wgrad_h2_bnbwd"
+    for bad in (dict(arith="f32", cin=64, gated=True), dict(arith="f32", cin=64, in_coef=True), dict(arith="b3", cin=32, gated=True),
+                dict(arith="b3", cin=64, bn="y"), dict(arith="h2", cin=64, bn="y"), dict(arith="f32", cin=64, bn="bits"), dict(arith="f16", cin=64)):
+        with pytest.raises(_hip.LadHipError):
+            engine.conv_s1_entry(**bad)
+    for bad in (dict(kind="f32", in_coef=True), dict(kind="f32", bn=True), dict(kind="b3c", bn=True), dict(kind="b3", bn=False)):
+        with pytest.raises(_hip.LadHipError):
+            engine.conv_wgrad_entry(**bad)

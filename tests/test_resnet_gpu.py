@@ -395,7 +395,7 @@ def test_virtual_activation_gives_the_same_gradients():
         t = torch.from_numpy(recipe.make_labels(23, B)).cuda()
         probs = m.engine.forward(x, train=True, labels=t).clone()
         m.engine.backward(None)
-        assert any(a.get("a1_virtual") for a in m.engine._last_train_plan["acts"]) == flag
+        assert any(b.a1_virtual for b in m.engine._last_train_plan["schedule"].blocks) == flag
         out.append((probs, m.engine.flat_grad().clone(), m.engine.export_relu_masks()))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
     for k, v in out[0][2].items():
@@ -661,7 +661,7 @@ def test_fused_shortcut_launches_give_the_same_gradients():
         x = torch.from_numpy(recipe.make_features(32, B)).cuda()
         t = torch.from_numpy(recipe.make_labels(33, B)).cuda()
         probs = m.engine.forward(x, train=True, labels=t).clone()
-        assert m.engine._use_s2b3(m.engine._last_train_plan["blocks"][2]) == (fuse and s2b3)
+        assert (m.engine._last_train_plan["schedule"].blocks[2].entry == "s2b3") == (fuse and s2b3)
         m.engine.backward(None)
         out.append((probs, {k: v.double().cpu() for k, v in m.engine.grad_views().items()}))
     assert torch.equal(out[0][0], out[1][0])
@@ -685,14 +685,16 @@ def test_split_operand_kernels_past_2_gib():
     blocks = eng._blocks_for(100, 44)[0]
     c64, c32 = blocks[0].conv1, blocks[3].conv1
     assert (c64.cin, c32.cin) == (64, 32) and c64.b3 and c32.b3
-    eng._cur_batch = 512
-    assert eng._use_b3(c64) and eng._use_b3_full(c64) and eng._use_b3(c32)
-    eng._cur_batch = 1844
-    assert eng._use_b3(c64)
-    eng._cur_batch = 2048
-    assert eng._use_b3(c64) and eng._use_b3_full(c64) and eng._use_b3(c32)
-    eng._cur_batch = 16000
-    assert eng._use_b3(c64) and not eng._use_b3(c32)
+
+    def split(B):   # (c64 on the split-operand kernels, ... with everything that exists at 64 channels only: sign bits, c32 likewise)
+        sched = eng._schedule(B, 100, 44)
+        on64 = sched.blocks[0].conv1.arith != "f32"
+        return on64, on64 and c64.b3_full and sched.blocks[0].bits, sched.blocks[3].conv1.arith != "f32"
+
+    assert split(512) == (True, True, True)
+    assert split(1844)[0]
+    assert split(2048) == (True, True, True)
+    assert split(16000)[0] and not split(16000)[2]
 
 
 def test_deferred_weight_gradient_sums():
@@ -742,7 +744,7 @@ def test_sign_bit_path_gives_the_same_gradients():
         t = torch.from_numpy(recipe.make_labels(23, B)).cuda()
         m.engine.forward(x, train=True, labels=t)
         m.engine.backward(None)
-        assert any(a.get("bits_live") for a in m.engine._last_train_plan["acts"]) == flag
+        assert any(b.bits for b in m.engine._last_train_plan["schedule"].blocks) == flag
         out.append(m.engine.flat_grad().clone())
     assert float(out[0].abs().max()) > 0
     assert torch.equal(out[0], out[1])
@@ -2112,9 +2114,10 @@ def test_relu_decisions_differ_from_the_oracle_only_at_the_boundary(B, seed):
 
 
 def test_flags_changed_between_forward_and_backward_do_not_split_the_passes():
-    """The per-layer kernel choices are made once, by the train-mode forward, and its backward repeats them (advisor, round 2:
-    a1 kept virtual by the forward but expected in HBM by the backward, stale packed images, ...): flipping engine flags in
-    between changes nothing for the pass in flight and takes effect from the next forward on."""
+    """The per-layer kernel choices are made once, by the train-mode forward (engine.train_schedule, kept in its plan), and its
+    backward reads nothing else (advisor, round 2: a1 kept virtual by the forward but expected in HBM by the backward, stale packed
+    images, ...): flipping EVERY kernel flag in between changes nothing for the pass in flight, the engine's attributes stay what
+    the caller set, and they take effect from the next forward on.  A backward() that raises leaves them alone as well."""
     B = 4
     m, _ = build_model(71)
     m.train()
@@ -2125,15 +2128,62 @@ def test_flags_changed_between_forward_and_backward_do_not_split_the_passes():
     eng.backward(None)
     g_ref = eng.flat_grad().clone()
     eng.forward(x, train=True, labels=t)
-    eng.bf16x3 = eng.virtual_a1 = eng.relu_bits = eng.fuse_bn_bwd_b3 = eng.fuse_s2_shortcut = False
+    flags = eng.KERNEL_OPTIONS + ("stem_onepass",)
+    flipped = {k: not getattr(eng, k) for k in flags}
+    assert len(flipped) == 13
+    for k, v in flipped.items():
+        setattr(eng, k, v)
     eng.backward(None)
     assert torch.equal(eng.flat_grad(), g_ref)
-    assert eng.bf16x3 is False and eng.virtual_a1 is False          # the caller's settings are back after the pass
+    assert {k: getattr(eng, k) for k in flags} == flipped           # the caller's settings are untouched by the pass
     eng.forward(x, train=True, labels=t)                            # ... and now they apply
+    sched = eng._last_train_plan["schedule"]
+    assert dict(sched.opts) == {k: flipped[k] for k in eng.KERNEL_OPTIONS} and sched.stem_onepass is flipped["stem_onepass"]
+    assert all(c.arith == "f32" for b in sched.blocks for c in (b.conv1, b.conv2)) and not any(b.a1_virtual or b.bits for b in sched.blocks)
     eng.backward(None)
     g_f32 = eng.flat_grad().clone()
     assert not torch.equal(g_f32, g_ref)
     assert float((g_f32 - g_ref).norm() / g_ref.norm()) < 2e-2
+    # a backward() that raises (no forward to differentiate: an error of the engine, not a device fault)
+    m2, _ = build_model(71)
+    m2.train()
+    eng2 = m2.engine
+    eng2.virtual_a1 = eng2.f16x2_32 = False
+    before = {k: getattr(eng2, k) for k in flags}
+    with pytest.raises(_lib().LadHipError):
+        eng2.backward(None)
+    assert {k: getattr(eng2, k) for k in flags} == before and eng2._defer_on is False
+    eng2.virtual_a1 = eng2.f16x2_32 = True
+    eng2.forward(x, train=True, labels=t)                           # the library's deferral queue is off and empty: a normal step
+    eng2.backward(None)
+    assert torch.equal(eng2.flat_grad(), g_ref)
+
+
+@pytest.mark.parametrize("first", [False, True])
+def test_f16x2_32_changed_on_a_live_engine(first):
+    """engine.f16x2_32 changed between two steps of ONE engine: block2's 32 -> 32 convolutions move between the bf16 x 3 and the
+    f16 x 2 kernels, whose packed weight images (and the pack table that lists the layers on f16 x 2) must follow -- probabilities
+    and gradient equal, bit for bit, to an engine that had the final value from the start."""
+    B = 4
+    x = torch.from_numpy(recipe.make_features(72, B)).cuda()
+    t = torch.from_numpy(recipe.make_labels(73, B)).cuda()
+    m, _ = build_model(71)
+    m.train()
+    eng = m.engine
+    eng.f16x2_32 = first
+    eng.forward(x, train=True, labels=t)
+    eng.backward(None)
+    eng.f16x2_32 = not first
+    probs = eng.forward(x, train=True, labels=t).clone()
+    eng.backward(None)
+    m_ref, _ = build_model(71)
+    m_ref.train()
+    m_ref.engine.f16x2_32 = not first
+    p_ref = m_ref.engine.forward(x, train=True, labels=t).clone()
+    m_ref.engine.backward(None)
+    assert float(m_ref.engine.flat_grad().abs().max()) > 0
+    assert torch.equal(probs, p_ref)
+    assert torch.equal(eng.flat_grad(), m_ref.engine.flat_grad())
 
 
 def test_backward_is_reproducible_next_to_another_process():
