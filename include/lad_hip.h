@@ -629,6 +629,47 @@ int lad_score_runs(const void *runs_workspace, const int32_t *table, const int32
                    const double *fps_host, const double *min_lengths, int32_t n_min_lengths, void *workspace,
                    int64_t *scores, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sampling-rate conversion of one channel by up / down = sr_out / sr_in (reduced), polyphase FIR on the device.
+ * Replaces the host resampling of the reference's readers: librosa.load(audio_path, sr=44100) in front of the wav cuts
+ * (segment_laughter.py:134) and librosa.load(sr=8000) of the code it descends from (laugh_segmenter.py:157-185).
+ * Convention: scipy.signal.resample_poly with its defaults.  For a prototype filter h of 2 * half + 1 taps
+ *   y[n] = sum_j x[j] * h[half + n * down - j * up],  j in [0, n_in) with the h index in [0, 2 * half]
+ * (zero phase, x zero-extended at both ends), n in [0, lad_resample_out_len(n_in, up, down)).
+ * Table layout: float32 table[up][K], K = 2 * (half / up) + 1 + (half % up != 0), L = (K - 1) / 2 = half / up;
+ *   table[p][t] = h[half + p - (t - L) * up]  where that index lies in [0, 2 * half], 0 elsewhere
+ * so every h[i] sits in exactly one cell (p = (i - half) mod up, t = L - (i - half - p) / up) and the zero padding is at
+ * the two ends of a row: t = 0 where half + p + L * up > 2 * half, t = K - 1 where half + p - (K - 1 - L) * up < 0.
+ * Output n with n * down = c * up + p is sum_{t = 0}^{K - 1} table[p][t] * x[c - L + t], summed in that order with one fused
+ * multiply-add per tap: the order depends on nothing but p, and a call for outputs [out_first, out_first + n_out) writes the
+ * same bits as those outputs of a call for the whole signal.
+ * ---------------------------------------------------------------------------------------------- */
+enum lad_resample_dtype { LAD_RESAMPLE_F32 = 0, LAD_RESAMPLE_I16 = 1 };
+/* ceil(n_in * up / down): the length librosa.load(sr=...) returns (segment_laughter.py:134); needs no GPU.  -1 and
+ * lad_last_error() for n_in < 0, up or down < 1, or n_in * up beyond 64 bits. */
+int64_t lad_resample_out_len(int64_t n_in, int32_t up, int32_t down);
+/* outputs one workgroup computes from one staged input span (segment_laughter.py:134 has no such notion: the tests place
+ * their chunk cuts from it) */
+int32_t lad_resample_tile_outputs(void);
+/* limits of lad_resample (laugh_segmenter.py:157-185 resamples on the host without any): largest up, down and K ... */
+int32_t lad_resample_max_up(void);
+int32_t lad_resample_max_down(void);
+int32_t lad_resample_max_taps(void);
+/* ... and the LDS one workgroup may use for the table and a tile's input span (laugh_segmenter.py:157-185) */
+int64_t lad_resample_max_lds_bytes(void);
+/* LDS bytes a ratio needs (the table -- none for up == 1 with K >= 3 * down -- plus one tile's input span, about
+ * (tile - 1) * down / up + K + 8 samples); needs no GPU.  A ratio is
+ * supported iff it is within the three limits above and this is <= lad_resample_max_lds_bytes(); -1 and lad_last_error()
+ * outside the three limits (segment_laughter.py:134). */
+int64_t lad_resample_lds_bytes(int32_t up, int32_t down, int32_t K);
+/* y[0 .. n_out) = outputs out_first .. out_first + n_out of the conversion of x[0 .. n_in) (segment_laughter.py:134,
+ * laugh_segmenter.py:157-185); one launch on `stream`.  x: DEVICE float32 or int16 PCM (x_dtype: lad_resample_dtype; int16 is
+ * scaled by 1 / 32768 in the kernel); table: DEVICE, layout above; y: DEVICE float32[n_out].  LAD_ERR_INVALID with
+ * lad_last_error() set and nothing launched for an unknown x_dtype, up, down or K < 1, a ratio beyond the limits,
+ * out_first + n_out > lad_resample_out_len(n_in, up, down), or a null pointer; n_out == 0 returns LAD_OK without a launch. */
+int lad_resample(const void *x, int32_t x_dtype, int64_t n_in, const float *table, int32_t up, int32_t down, int32_t K,
+                 int64_t out_first, int64_t n_out, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

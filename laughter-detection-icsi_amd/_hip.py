@@ -163,6 +163,15 @@ SIGNATURES = {
     "lad_score_runs": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_void_p,
                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
                                ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
+    # sampling-rate conversion (csrc/resample.hip)
+    "lad_resample_out_len": (c_i64, [c_i64, c_i32, c_i32]),
+    "lad_resample_tile_outputs": (c_i32, []),
+    "lad_resample_max_up": (c_i32, []),
+    "lad_resample_max_down": (c_i32, []),
+    "lad_resample_max_taps": (c_i32, []),
+    "lad_resample_max_lds_bytes": (c_i64, []),
+    "lad_resample_lds_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "lad_resample": (c_int, [c_void_p, c_i32, c_i64, c_void_p, c_i32, c_i32, c_i32, c_i64, c_i64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -30,9 +30,10 @@ from utils import get_feat_extractor  # noqa: E402
 SPLITS = ['train', 'dev', 'test']
 
 
-def compute_features_per_split(split_audio, output_dir, rank=0, world=1, use_kaldi=False):
+def compute_features_per_split(split_audio, output_dir, rank=0, world=1, use_kaldi=False, resample=False):
     """split_audio: {split: [audio paths]} -> writes <output_dir>/feats/<split>/<id>.npy and
-    <output_dir>/cutsets/{split}_feats.jsonl (one record per recording: id, path, num_frames, num_features, frame_shift, extractor configuration)."""
+    <output_dir>/cutsets/{split}_feats.jsonl (one record per recording: id, path, num_frames, num_features, frame_shift, extractor configuration).
+    resample=True: audio at another rate than 16 kHz is converted on the GPU first (load_data.load_audio_device) instead of refused."""
     extractor = get_feat_extractor(num_samples=cfg.FEAT['num_samples'], num_filters=cfg.FEAT['num_filters'], use_kaldi=use_kaldi)
     os.makedirs(os.path.join(output_dir, 'cutsets'), exist_ok=True)
     written = {}
@@ -44,7 +45,10 @@ def compute_features_per_split(split_audio, output_dir, rank=0, world=1, use_kal
             path = paths[i]
             rec_id = os.path.splitext(os.path.relpath(path, os.path.commonpath(paths) if len(paths) > 1 else os.path.dirname(path)))[0]
             rec_id = rec_id.replace(os.sep, '_')
-            pcm = torch.from_numpy(load_data.load_audio(path)).to(extractor.config.device)
+            if resample:
+                pcm = load_data.load_audio_device(path, device=extractor.config.device, resample=True)
+            else:
+                pcm = torch.from_numpy(load_data.load_audio(path)).to(extractor.config.device)
             feats = extractor.extract_long(pcm.contiguous()).cpu().numpy()
             out = os.path.join(feats_dir, rec_id + '.npy')
             np.save(out, feats)
@@ -64,6 +68,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--audio_root', required=True, help='directory with one sub-directory per split holding .wav / .npy audio')
     ap.add_argument('--output_dir', required=True)
+    ap.add_argument('--resample', action='store_true', help='convert audio at another rate than 16 kHz on the GPU instead of refusing it')
     args = ap.parse_args(argv)
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(local)
@@ -72,7 +77,7 @@ def main(argv=None):
         d = os.path.join(args.audio_root, split)
         if os.path.isdir(d):
             split_audio[split] = sorted(os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith(('.wav', '.npy')))
-    out = compute_features_per_split(split_audio, args.output_dir, rank, world)
+    out = compute_features_per_split(split_audio, args.output_dir, rank, world, resample=args.resample)
     if rank == 0:
         for split, recs in out.items():
             print(f'{split}: {len(recs)} recordings, {sum(r["num_frames"] for r in recs)} frames')

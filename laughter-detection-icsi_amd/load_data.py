@@ -8,7 +8,8 @@ DataLoader(batch_size=32)).
 Lhotse manifests are replaced by the data-frame CSVs the reference itself produces (create_data_df.py:171-172 schema,
 `{split}_df.csv`) plus the audio files they name: channels are featurised once on the GPU and kept in HBM.
 Audio: 16 kHz mono .wav (int16/float) or .npy float arrays; NIST .sph needs external conversion (sph2pipe), as in
-the reference's own tooling (analysis/output_processing/laughs_to_wav.py).
+the reference's own tooling (analysis/output_processing/laughs_to_wav.py).  Files at another sampling rate are refused unless
+the caller asks for `resample=True` (load_audio_device: converted on the GPU, csrc/resample.hip).
 """
 import os
 import sys
@@ -43,6 +44,34 @@ def load_audio(path, sampling_rate=16000):
             return (x.astype(np.float32) / 2147483648.0)
         return x.astype(np.float32)
     raise ValueError(f"unsupported audio format {ext!r} ({path}): convert NIST sphere files with sph2pipe first")
+
+
+def load_audio_device(path, sampling_rate=16000, device="cuda", resample=False, source_rate=None):
+    """Mono float32 GPU tensor at `sampling_rate`: the file is read, uploaded and, with resample=True and a file at another
+    rate, converted on the device (resample.Resampler; 16-bit PCM stays int16 until the kernel scales it, exactly as load_audio
+    does).  Without resample=True a file at another rate raises the ValueError of load_audio.  `.npy` arrays carry no rate:
+    `source_rate` says it (default: `sampling_rate`)."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        sr, x = int(source_rate or sampling_rate), np.load(path).astype(np.float32).reshape(-1)
+    elif ext == ".wav":
+        from scipy.io import wavfile
+        sr, x = wavfile.read(path)
+        if x.ndim > 1:
+            x = x[:, 0]
+    else:
+        raise ValueError(f"unsupported audio format {ext!r} ({path}): convert NIST sphere files with sph2pipe first")
+    if sr != sampling_rate and not resample:
+        raise ValueError(f"{path}: expected {sampling_rate} Hz audio, got {sr}")
+    if x.dtype == np.int32:
+        x = x.astype(np.float32) / 2147483648.0
+    elif x.dtype != np.int16:
+        x = x.astype(np.float32)
+    pcm = torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    if sr == sampling_rate:
+        return pcm if pcm.dtype == torch.float32 else pcm.to(torch.float32) / 32768.0
+    import resample as resample_mod
+    return resample_mod.get_resampler(sr, sampling_rate, pcm.device)(pcm)
 
 
 class SegmentSampler:
@@ -162,7 +191,7 @@ def _stored_features(manifest, path, num_filters, extractor=None):
 
 
 def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, audio_root=None, seed=None, rank=0,
-                               world=1, store=None, index_seed=INDEX_SHUFFLE_SEED, feats_manifest=None):
+                               world=1, store=None, index_seed=INDEX_SHUFFLE_SEED, feats_manifest=None, resample=False):
     '''
     Create a dataloader for the provided split
         - split needs to be one of 'train', 'dev' and 'test'
@@ -178,6 +207,7 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
           reference trains from stored features too (compute_features.py:105-111 writes them, load_data.py:24-25 and
           datasets.py:56 read them).  The stored matrices are the extractor's raw float32 output (no lilcom stage), so the
           batches are bit-equal to those of the audio path; channels the manifest does not list fall back to their audio.
+        - resample: audio files at another rate than 16 kHz are converted on the GPU (load_audio_device) instead of refused
     '''
     table = load_segment_table(cutset_dir, split, shuffle=shuffle, seed=seed, world=world, index_seed=index_seed)
     if store is None:
@@ -196,6 +226,8 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
             stored = _stored_features(manifest, path, cfg.FEAT['num_filters'], getattr(store, 'extractor', None)) if manifest is not None else None
             if stored is not None:
                 store.add_features(key, stored)
+            elif resample:
+                store.add_audio(key, load_audio_device(path, device=store.device, resample=True))
             else:
                 store.add_audio(key, load_audio(path))
     dataset = LadDataset(store, table)
@@ -218,14 +250,18 @@ class InferenceLoader:
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
 
 
-def create_inference_dataloader(audio_path, batch_size=32):
+def create_inference_dataloader(audio_path, batch_size=32, resample=False):
     '''
     Create inference dataloader for the audio file `audio_path`: the whole file is featurised in one GPU launch and the
     windows are read out of that (T, F) matrix.  `loader.dataset.feats` is the matrix itself, for
     `model.engine.predict_windows`, which skips the window materialisation altogether.
+    resample=True: a file at another rate than 16 kHz is converted on the GPU first (load_audio_device) instead of refused.
     '''
     extractor = get_feat_extractor(num_samples=cfg.FEAT['num_samples'], num_filters=cfg.FEAT['num_filters'])
-    pcm = torch.from_numpy(load_audio(audio_path)).to(extractor.config.device)
+    if resample:
+        pcm = load_audio_device(audio_path, device=extractor.config.device, resample=True)
+    else:
+        pcm = torch.from_numpy(load_audio(audio_path)).to(extractor.config.device)
     feats_all = extractor.extract_long(pcm.contiguous())
     dataset = InferenceDataset(feats_all)
     return InferenceLoader(dataset, batch_size=batch_size)

@@ -57,10 +57,11 @@ def build_model(config_name, model_path, device):
     return model
 
 
-def predict_file_device(model, audio_path, chunk=None, rank=0, world=1, precision="fp32"):
+def predict_file_device(model, audio_path, chunk=None, rank=0, world=1, precision="fp32", resample=False):
     """probs (T,) float32 GPU tensor for the stride-one-frame windows of the file + its duration in seconds.
-    chunk=None: the engine's own chunk size for the precision (engine.PREDICT_CHUNK)."""
-    loader = load_data.create_inference_dataloader(audio_path)
+    chunk=None: the engine's own chunk size for the precision (engine.PREDICT_CHUNK).  resample=True: a file at another rate than
+    16 kHz is converted on the GPU (csrc/resample.hip) instead of refused; its duration stays frames over its own rate."""
+    loader = load_data.create_inference_dataloader(audio_path, resample=resample)
     feats = loader.dataset.feats
     T = feats.shape[0]
     sh = parallel.shard_indices(T, rank, world)
@@ -71,19 +72,26 @@ def predict_file_device(model, audio_path, chunk=None, rank=0, world=1, precisio
     return probs, file_length
 
 
-def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32"):
+def predict_file(model, audio_path, chunk=None, rank=0, world=1, precision="fp32", resample=False):
     """predict_file_device with the track copied to the host: probs (T,) float32 numpy + the duration in seconds."""
-    probs, file_length = predict_file_device(model, audio_path, chunk=chunk, rank=rank, world=world, precision=precision)
+    probs, file_length = predict_file_device(model, audio_path, chunk=chunk, rank=rank, world=world, precision=precision,
+                                             resample=resample)
     return probs.cpu().numpy(), file_length
 
 
-def save_audio_instances(instances, audio_path, output_dir):
+def save_audio_instances(instances, audio_path, output_dir, rate=None):
     """One `laugh_<i>.wav` per instance (segment_laughter.py:133-149).  The reference re-reads the file with
-    `librosa.load(sr=44100)`, i.e. resampled; here the cut is taken from the file's own samples at its own rate
-    (no resampler on this path) -- same instants, same int16 scaling (`maxv = 32767`)."""
+    `librosa.load(sr=44100)`, i.e. resampled.  rate=None: the cut is taken from the file's own samples at its own rate;
+    rate=44100 (or any other): the file is converted once on the GPU to that rate (load_data.load_audio_device) and the
+    instances are cut from that -- the reference's behaviour.  Same instants, same int16 scaling (`maxv = 32767`)."""
     from scipy.io import wavfile
     sr = audio_utils.get_sampling_rate(audio_path)
-    y = load_data.load_audio(audio_path, sampling_rate=sr)
+    if rate is None or int(rate) == sr:
+        y = load_data.load_audio(audio_path, sampling_rate=sr)
+    else:
+        y = load_data.load_audio_device(audio_path, sampling_rate=int(rate), device=torch.device('cuda', torch.cuda.current_device()),
+                                        resample=True, source_rate=sr).cpu().numpy()
+        sr = int(rate)
     maxv = np.iinfo(np.int16).max
     paths = []
     for index, instance in enumerate(instances):
@@ -95,16 +103,19 @@ def save_audio_instances(instances, audio_path, output_dir):
 
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
-                  precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host"):
+                  precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
+                  save_audio_rate=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
-    segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary)."""
+    segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
+    resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
+    (None: the file's own)."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if save_to_audio_files and output_dir is None:
         raise Exception("Need to specify an output directory to save audio files")   # segment_laughter.py:138-140
     start_time = time.time()
     predict = predict_file_device if segmenter == "device" else predict_file
-    probs, file_length = predict(model, audio_path, rank=rank, world=world, precision=precision)
+    probs, file_length = predict(model, audio_path, rank=rank, world=world, precision=precision, resample=resample)
     if segmenter == "device":
         torch.cuda.synchronize(probs.device)   # (the host path's copy waits for the model pass: the same split of the two legs)
     predict_time = time.time() - start_time
@@ -127,7 +138,7 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
             if save_to_textgrid or (save_to_audio_files and len(instances) > 0):
                 os.makedirs(out_dir, exist_ok=True)
             if save_to_audio_files and len(instances) > 0:
-                wav_paths = save_audio_instances(instances, audio_path, out_dir)
+                wav_paths = save_audio_instances(instances, audio_path, out_dir, rate=save_audio_rate)
                 if verbose:
                     print(laugh_segmenter.format_outputs(instances, wav_paths))   # segment_laughter.py:148
             if save_to_textgrid:
@@ -150,8 +161,8 @@ def build_parser():
     parser.add_argument('--input_audio_file', required=True, type=str)
     parser.add_argument('--output_dir', type=str, default=None)
     parser.add_argument('--save_to_audio_files', type=str, default='False',
-                        help="laugh_<i>.wav per instance, cut from the file at its own sampling rate (the reference resamples to 44.1 kHz "
-                             "with librosa and defaults this flag to 'True'; here it is opt-in: it needs --output_dir)")
+                        help="laugh_<i>.wav per instance, cut from the file at its own sampling rate or at --save_audio_rate (the reference "
+                             "resamples to 44.1 kHz with librosa and defaults this flag to 'True'; here it is opt-in: it needs --output_dir)")
     parser.add_argument('--save_probs', type=str, default=None, help='(not in the reference) write the per-frame probabilities to this .npy')
     parser.add_argument('--save_to_textgrid', type=str, default='True')
     parser.add_argument('--gpus', type=int, default=None,
@@ -160,6 +171,12 @@ def build_parser():
     parser.add_argument('--segmenter', type=str, default='host', choices=['host', 'device'],
                         help="(not in the reference) where the probability track is cut into instances: 'host' copies it to the host "
                              "(numpy, one pass per threshold); 'device' cuts it on the GPU, all thresholds in one pass -- same output")
+    parser.add_argument('--resample', type=str, default='False',
+                        help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
+                             "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
+    parser.add_argument('--save_audio_rate', type=int, default=None,
+                        help="sampling rate of the laugh_<i>.wav cuts: the file is converted to it once on the GPU (the reference writes "
+                             "44100); default: the file's own rate, no conversion")
     return parser
 
 
@@ -182,7 +199,7 @@ def main(argv=None):
     load_and_pred(model, args.input_audio_file, thresholds, min_lengths, args.output_dir,
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
-                  segmenter=args.segmenter)
+                  segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate)
 
 
 if __name__ == '__main__':
