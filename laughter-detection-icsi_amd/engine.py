@@ -228,11 +228,189 @@ def conv_wgrad_entry(kind, in_coef=False, bn=False):
     raise _hip.LadHipError(f"no weight-gradient kernel for {kind!r} with in_coef={in_coef}, bn={bn}")
 
 
+# ---------------------------------------------------------------------------------------- sliding-window inference: the layout
+def _s2_shortcut_rides(b, opts):
+    """fp16 eval: the 1x1 shortcut of down-sampling block b inside conv1's launch?  Measured per group of 8,192 windows
+    (profiles/r05_infer_s2_shortcut.log): 64 -> 32: 344 us against 314 + 72; 16 -> 16: 41 against 30 + 14; 32 -> 16: 219 against
+    157 + 44 -- there the second accumulator costs the launch more than the second gather saves."""
+    return bool(opts["f16_s2_shortcut_fused"]) and b.conv1.cin != 32
+
+
+def _block_fits_lds(b, B, opts, hw=None):
+    """Worth trying lad_f16_block_fwd (include/lad_hip.h) on B images of block b (hw: their height and width when they are not the
+    spec's own, as for the strips of a window geometry)?  Identity block; 64 channels on >= 256 images of at most 512 positions
+    (the boundary strips of level 1), or 16 / 32 channels on >= 512 small images (the strips of level 2, the windows at levels
+    3 and 4).  The entry point itself answers LAD_NOT_COVERED for what does not fit a CU's LDS."""
+    c = b.conv1
+    if b.sc_conv is not None or c.stride != 1 or c.taps != 9 or c.cin != c.cout:
+        return False
+    h, w = hw if hw is not None else (c.h_in, c.w_in)
+    img = (h + 1) * (w + 1)
+    if c.cin == 64:
+        return bool(opts["strip_block_fused"]) and B >= 256 and img <= 512 and img + w <= 562
+    return bool(opts["small_block_fused"]) and c.cin in (16, 32) and B >= 512 and img <= 2048
+
+
+def _tail_blocks_ok(tail):
+    """The layers lad_f16_tail_fwd runs: two (down-sampling block with a 1x1 shortcut, identity block) pairs, 32 -> 16 -> 16 channels."""
+    if len(tail) != 4:
+        return False
+    for k, b in enumerate(tail):
+        down = k % 2 == 0
+        cin = 32 if k == 0 else 16
+        if (b.conv1.cin, b.conv1.cout, b.conv1.taps, b.conv1.stride) != (cin, 16, 9, 2 if down else 1):
+            return False
+        if (b.conv2.cin, b.conv2.cout, b.conv2.taps, b.conv2.stride) != (16, 16, 9, 1):
+            return False
+        if down != (b.sc_conv is not None) or (down and (b.sc_conv.cin, b.sc_conv.cout, b.sc_conv.taps, b.sc_conv.stride) != (cin, 16, 1, 2)):
+            return False
+    return True
+
+
+class _StreamLayout(NamedTuple):
+    """Where everything of one group of B sliding windows lies and which launches are tried on it (stream_layout).  Rows are rows of
+    a PNHWC tensor (one position, all channels).  cat = [strips: n_strip_max images of img_t_rows][stream image][spare rows] at
+    level 1, cat2 = [strips: n_strip2_max images of img_t2][phase-0 stream image][phase-1 stream image][tail] at level 2."""
+    B: int
+    H: int
+    W: int
+    half: bool
+    mode: str                  # "per_window" | "assembled" | "direct" | "shared2"
+    run: Optional[Tuple[int, int]]   # (windows of the run, its largest group) when the streams are the run's, not the group's
+    # level 1 (None from Ht on in "per_window"; stream_row0 and cat_rows None in "assembled": no common buffer there)
+    n1: int                    # leading stride-1 identity blocks at full resolution
+    band: int                  # rows of a window that differ from the stream at the end of level 1 (either end)
+    Ht: Optional[int]          # rows of a strip: the top band rows of one window over the bottom band rows of another
+    Hs: Optional[int]          # rows of the GROUP's stream image (stream_rows: of the image the windows read)
+    n_strip: Optional[int]     # strips of this group: one per frame offset
+    n_strip_max: Optional[int]   # ... of the run's largest group: what cat has room for
+    img_t_rows: Optional[int]  # rows of one strip image
+    stream_row0: Optional[int]   # first row of the stream image in cat (of the run's first window: a group adds d * (W + 1))
+    cat_rows: Optional[int]
+    # level 2 (None outside "shared2")
+    k3: Optional[int]          # the block that leaves level 2 (the next down-sampling one)
+    H2: Optional[int]
+    W2: Optional[int]
+    band2: Optional[int]
+    Ht2: Optional[int]
+    shift2: Optional[int]      # level-2 strip s = top of window s over bottom of window s - shift2
+    h2s: Optional[int]         # rows of one phase's stream image
+    n_strip2: Optional[int]
+    n_strip2_max: Optional[int]
+    img_t2: Optional[int]
+    img_s2: Optional[int]
+    stream2_base: Optional[int]   # first row of the phase-0 stream image in cat2
+    rows2: Optional[int]
+    # launches that are TRIED (lad_f16_block_fwd*, lad_f16_conv_s2_strips_fwd and lad_f16_tail_fwd may still answer LAD_NOT_COVERED,
+    # and the launch code falls back where it always did); all False in fp32
+    window_fused: Tuple[bool, ...]    # per block of the model: lad_f16_block_fwd on the B windows
+    rides: Tuple[bool, ...]           # per block: a down-sampling block's 1x1 shortcut in conv1's launch (any image count)
+    stream_fused: Tuple[bool, ...]    # blocks[:n1] on the stream image
+    strip_fused: Tuple[bool, ...]     # blocks[:n1] on the n_strip strips
+    stem_kept: bool                   # the stream's stem output is kept for the strips' first block
+    strip_stem_rows: bool             # ... which runs as lad_f16_block_fwd_stem_rows (no stem launch for the strips)
+    stream2_fused: Tuple[bool, ...]   # blocks[n1 + 1:k3] on the two phase streams
+    strip2_fused: Tuple[bool, ...]    # blocks[n1 + 1:k3] on the n_strip2 level-2 strips
+    strips2_resident: bool            # the level-2 strips' entry on lad_f16_conv_s2_strips_fwd
+    tail_fused: bool                  # everything behind level 2 on lad_f16_tail_fwd
+
+    @property
+    def stream_rows(self):
+        """Rows of the level-1 stream image the windows read: the run's, or the group's own."""
+        return self.Hs if self.run is None else self.run[0] + self.H - 1
+
+
+def stream_layout(blocks, B, H, W, half, opts, run=None):
+    """The layout of one group of B windows of H frames at a stride of one frame: a pure function of the layer geometry
+    (block_geometry), the group and the switch values (opts: {name of INFER_OPTIONS: value}); run: (windows, largest group) of the
+    run of groups whose streams are computed once, or None.  _forward_eval_stream stores the result in the window plan and its
+    launches read nothing else."""
+    o = dict(opts)
+    n = len(blocks)
+    window_fused = tuple(bool(half) and _block_fits_lds(b, B, o) for b in blocks)
+    rides = tuple(bool(half) and b.sc_conv is not None and b.conv1.stride == 2 and b.sc_conv.stride == 2 and b.conv1.taps == 9
+                  and b.sc_conv.taps == 1 and _s2_shortcut_rides(b, o) for b in blocks)
+    n1 = 0
+    while n1 < n and blocks[n1].conv1.stride == 1 and blocks[n1].sc_conv is None and blocks[n1].conv1.h_out == H:
+        n1 += 1
+    band = 1 + 2 * n1                       # 3x3 convolutions at full resolution: the stem + two per block
+    if n1 == 0 or H < 4 * band or B < 2:    # nothing to share
+        return _StreamLayout(B, H, W, bool(half), "per_window", None, n1, band, *(None,) * 20, window_fused, rides, (), (), False, False,
+                             (), (), False, False)
+    Hs, Ht = B + H - 1, 2 * band
+    n_strip = B + H - Ht                    # one strip per frame offset: the top rows of one window, the bottom rows of another
+    nb = blocks[n1] if n1 < n else None
+    # `direct`: the strips and the stream go into ONE buffer and the stride-2 block that follows reads every window's rows
+    # from where they lie (lad_f16_conv_s2_fwd_windows) -- no assembled copy (1.2 GB written and read per 2048 windows)
+    direct = bool(half and nb is not None and nb.sc_conv is not None and nb.conv1.stride == 2
+                  and (nb.conv1.cin, nb.conv1.cout) == (64, 32) and o["stream_direct"])
+    img_t_rows = (Ht + 1) * (W + 1)
+    # level 2 shared as well: the stride-2 block and the stride-1 blocks behind it, up to the next stride-2 block
+    k3 = n1 + 1
+    while direct and k3 < n and blocks[k3].conv1.stride == 1 and blocks[k3].sc_conv is None:
+        k3 += 1
+    n2 = k3 - n1 - 1
+    margin2 = 1 + 2 * n2                    # stride-1 3x3 convolutions at level 2
+    band2 = band // 2 + 1 + margin2         # rows of a window that differ from the stream at the end of level 2 (either end)
+    Ht2 = 2 * band2                         # level-2 strips, paired like level 1's: top of window s over bottom of window s - shift2
+    shift2 = 2 * (H // 2 - Ht2)
+    share2 = bool(direct and o["stream_level2"] and H % 2 == 0 and k3 < n and blocks[k3].sc_conv is not None
+                  and blocks[k3].conv1.stride == 2 and (blocks[k3].conv1.cin, blocks[k3].conv1.cout) == (32, 16)
+                  and H // 2 >= 2 * Ht2)
+    if not (share2 and o["stream_super"]):
+        run = None                          # (a run's streams are a feature of the fully shared path)
+    mode = "shared2" if share2 else "direct" if direct else "assembled"
+    stream_rows = Hs if run is None else run[0] + H - 1
+    n_strip_max = n_strip if run is None else run[1] + H - Ht
+    stream_row0 = cat_rows = None
+    if direct:
+        # ONE buffer: [strips of the group (a run: room for its largest)][the stream]; + two zero rows where the odd-phase level-2
+        # stream reads the level-1 stream from its second row on
+        stream_row0 = n_strip_max * img_t_rows
+        cat_rows = stream_row0 + (stream_rows + 1) * (W + 1) + W + 2 + (2 * (W + 1) if share2 else 0)
+    strip_fused = tuple(bool(half) and _block_fits_lds(b, n_strip, o, (Ht, W)) for b in blocks[:n1])
+    stream_fused = tuple(bool(half) and _block_fits_lds(b, 1, o, (stream_rows, W)) for b in blocks[:n1])
+    stem_kept = bool(half and o["strip_stem_shared"])
+    # rows 1 .. Ht - 2 of strip s ARE rows s + 1 .. of the stream's stem output: the first block's launch takes them from there
+    strip_stem_rows = stem_kept and Ht >= 3 and strip_fused[0] and blocks[0].conv1.cin == 64
+    level1 = (n1, band, Ht, Hs, n_strip, n_strip_max, img_t_rows, stream_row0, cat_rows)
+    if not share2:
+        return _StreamLayout(B, H, W, bool(half), mode, None, *level1, *(None,) * 13, window_fused, rides, stream_fused, strip_fused,
+                             stem_kept, strip_stem_rows, (), (), False, False)
+    H2, W2 = nb.conv1.h_out, nb.conv1.w_out
+    h2s = (stream_rows + 1) // 2            # rows of a level-2 stream image
+    n_strip2 = B + shift2
+    n_strip2_max = n_strip2 if run is None else run[1] + shift2
+    img_t2, img_s2 = (Ht2 + 1) * (W2 + 1), (h2s + 1) * (W2 + 1)
+    stream2_base = n_strip2_max * img_t2
+    rows2 = stream2_base + 2 * img_s2 + W2 + 2
+    return _StreamLayout(B, H, W, True, mode, run, *level1, k3, H2, W2, band2, Ht2, shift2, h2s, n_strip2, n_strip2_max, img_t2, img_s2,
+                         stream2_base, rows2, window_fused, rides, stream_fused, strip_fused, stem_kept, strip_stem_rows,
+                         tuple(_block_fits_lds(b, 2, o, (h2s, W2)) for b in blocks[n1 + 1:k3]),
+                         tuple(_block_fits_lds(b, n_strip2, o, (Ht2, W2)) for b in blocks[n1 + 1:k3]),
+                         rides[n1] and bool(o["strip2_resident"]) and (nb.conv1.cin, nb.conv1.cout) == (64, 32),
+                         bool(o["tail_fused"]) and _tail_blocks_ok(blocks[k3:]))
+
+
+class _StreamRun:
+    """A run of groups of predict_windows (fp16) whose level-1 / level-2 streams are computed ONCE.  cat, cat2 and stem (the run's
+    buffers, _sup_buffer) are filled when the run's first group computes the streams."""
+    __slots__ = ("i0", "S", "B_max", "base", "frames_avail", "cat", "cat2", "stem")
+
+    def __init__(self, i0, S, B_max, base, frames_avail):
+        self.i0, self.S, self.B_max = i0, S, B_max      # first window, windows, largest group
+        self.base, self.frames_avail = base, frames_avail   # address of the run's first frame, frames from there on
+        self.cat = self.cat2 = self.stem = None
+
+
 class ResNetEngine:
     # flags that select kernels / fusions per layer: a train-mode forward freezes them into its schedule (train_schedule), which its
     # backward follows whatever happens to the attributes in between
     KERNEL_OPTIONS =("bf16x3", "bf16x3_32", "f16x2", "f16x2_32", "relu_bits", "virtual_a1", "fuse_bn_bwd", "fuse_bn_bwd_b3", "fuse_bn_bwd_wgrad", "fuse_s2_shortcut",
                       "fuse_s2_shortcut_wgrad", "s2_b3")
+    # switches of the sliding-window inference path: stream_layout freezes them into the layout of a group of windows
+    INFER_OPTIONS = ("stream_direct", "stream_level2", "stream_super", "strip_block_fused", "small_block_fused", "tail_fused", "strip2_resident",
+                     "strip_stem_shared", "f16_s2_shortcut_fused")
 
     def __init__(self, model):
         self.model = model
@@ -243,7 +421,8 @@ class ResNetEngine:
         self._lib = None
         self._grad_dirty = False  # flat grad buffer holds a gradient that must be accumulated into
         self._train_forwards = 0
-        self._fold_tag = None
+        self._fold_tag = {}    # {id(layer table): state tag of its BatchNorm folds}: the sliding-window path alternates between geometries
+        self._f16_tags = {}    # ... of its half-precision weight images
         self._weights_version = 0
         # data-gradient epilogues can carry the first pass of the BatchNorm backward that follows (lad_conv_fwd_bnstat).
         # Measured at bs 512: -1.0 ms of reduce passes, +0.3 ms in the four fused conv launches, +0.3 ms in the finalize
@@ -301,7 +480,7 @@ class ResNetEngine:
         self._tail_param_cache = {}
         self._sup_cache = {}
         self._sup_plans = {}                 # {"l1" / "l2": keys of the run-long eval plans, released with the run's buffer}
-        self._probs_out = None               # (predict_windows: where the head of the current group of windows writes)
+        self._layouts = {}                   # {(B, H, W, half, switch values, run): _StreamLayout}
         # fp16 eval: a down-sampling block's 1x1 shortcut rides in its 3x3 convolution's launch (lad_f16_conv_s2_fwd*_sc; round 5)
         self.f16_s2_shortcut_fused = True
         self.fuse_s2_shortcut = True         # ... and its forward / data gradient inside conv1's launches (lad_conv_s2_*_fused)
@@ -864,8 +1043,7 @@ class ResNetEngine:
     def _fold_eval(self, blocks):
         """Per-channel (scale, shift) of every BatchNorm that follows a convolution, from the running statistics
         (eval mode of models.py:110-115,224), refreshed only when parameters or statistics changed."""
-        tags = self._fold_tag if isinstance(self._fold_tag, dict) else {}
-        self._fold_tag = tags   # per layer table: the sliding-window path alternates between three geometries
+        tags = self._fold_tag
         tag = self._state_tag()
         if tags.get(id(blocks)) == tag:
             return
@@ -887,9 +1065,7 @@ class ResNetEngine:
 
     def _pack_f16(self, blocks):
         """Half-precision weight images for the fp16 inference kernels (refreshed with the folds)."""
-        tags = getattr(self, "_f16_tags", None)
-        if tags is None:
-            tags = self._f16_tags = {}
+        tags = self._f16_tags
         tag = self._state_tag()
         if tags.get(id(blocks)) == tag:
             return
@@ -976,9 +1152,11 @@ class ResNetEngine:
         _hip.check(fn(fptr, _hip.ptr(self.stem_w), _hip.ptr(self.stem_bn.fold[0]), _hip.ptr(self.stem_bn.fold[1]), optr, B, H, W,
                       self.stem_cout, frame_stride, max(0, frames_avail), st), name)
 
-    def _eval_blocks(self, half, p, blocks, cur, B, final_out=None):
+    def _eval_blocks(self, half, p, blocks, cur, B, fused, rides, final_out=None):
         """Residual blocks `blocks` of plan p on the activation `cur` (one of the plan's rotating buffers of its level).
-        final_out: where the LAST block's output goes instead of a rotating buffer (a slice of a caller's tensor)."""
+        fused / rides: per block, whether lad_f16_block_fwd is tried and whether a down-sampling block's shortcut rides in conv1's
+        launch (the layout's flags for these blocks on B images).  final_out: where the LAST block's output goes instead of a
+        rotating buffer (a slice of a caller's tensor)."""
         conv = self._conv_eval_f16 if half else self._conv_eval
         lv = p["lv"]
         for bi, b in enumerate(blocks):
@@ -987,29 +1165,21 @@ class ResNetEngine:
             a1, y = free[0], free[1]
             if final_out is not None and bi == len(blocks) - 1:
                 y = final_out
-            if half and self._block_fits_lds(b, B):
+            if fused[bi]:
                 # both convolutions + the residual with the image(s) resident in LDS (csrc/conv_f16.hip: block_f16_strip_kernel at 64
                 # channels, block_f16_small_kernel at 16 / 32)
                 label = f"block_f16<{b.conv1.cin}>"
                 t0 = self._mark(label)
-                rc = self.lib().lad_f16_block_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.wt_h), _hip.ptr(b.bn1.fold[0]), _hip.ptr(b.bn1.fold[1]),
-                                                  _hip.ptr(b.conv2.wt_h), _hip.ptr(b.bn2.fold[0]), _hip.ptr(b.bn2.fold[1]), _hip.ptr(y),
+                rc = self.lib().lad_f16_block_fwd(_hip.ptr(cur), *self._f16_args(b.conv1, b.bn1), *self._f16_args(b.conv2, b.bn2), _hip.ptr(y),
                                                   B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, self._st())
                 if rc != _hip.LAD_NOT_COVERED:      # (this geometry is not covered, nothing was launched -> the two convolutions)
                     _hip.check(rc, "lad_f16_block_fwd " + b.conv1.name)
                     self._mark_end(label, t0)
                     cur = y
                     continue
-            if (half and b.sc_conv is not None and b.conv1.stride == 2 and b.sc_conv.stride == 2 and b.conv1.taps == 9
-                    and b.sc_conv.taps == 1 and self._s2_shortcut_rides(b)):
+            if rides[bi]:
                 cs = free[2]
-                label = f"conv_f16_s2sc<{b.conv1.cin},{b.conv1.cout}>"
-                t0 = self._mark(label)
-                _hip.check(self.lib().lad_f16_conv_s2_fwd_sc(
-                    _hip.ptr(cur), _hip.ptr(b.conv1.wt_h), _hip.ptr(b.bn1.fold[0]), _hip.ptr(b.bn1.fold[1]), _hip.ptr(a1),
-                    _hip.ptr(b.sc_conv.wt_h), _hip.ptr(b.sc_bn.fold[0]), _hip.ptr(b.sc_bn.fold[1]), _hip.ptr(cs), B, b.conv1.h_in,
-                    b.conv1.w_in, b.conv1.cin, b.conv1.cout, 1, self._st()), "lad_f16_conv_s2_fwd_sc " + b.conv1.name)
-                self._mark_end(label, t0)
+                self._s2_plain_f16(b, _hip.ptr(cur), (_hip.ptr(a1), _hip.ptr(cs)), B, b.conv1.h_in, b.conv1.w_in, True)
                 conv(b.conv2, b.bn2, a1, cs, y, B, 1)
                 cur = y
                 continue
@@ -1023,32 +1193,71 @@ class ResNetEngine:
             cur = y
         return cur
 
-    def _s2_shortcut_rides(self, b):
-        """fp16 eval: the 1x1 shortcut of down-sampling block b inside conv1's launch?  Measured per group of 8,192 windows
-        (profiles/r05_infer_s2_shortcut.log): 64 -> 32: 344 us against 314 + 72; 16 -> 16: 41 against 30 + 14; 32 -> 16: 219 against
-        157 + 44 -- there the second accumulator costs the launch more than the second gather saves."""
-        return self.f16_s2_shortcut_fused and b.conv1.cin != 32
+    @staticmethod
+    def _f16_args(cs, bn):
+        """{fp16 weight image, folded scale, folded shift} of one convolution, as the half-precision entry points take them."""
+        return _hip.ptr(cs.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1])
 
-    def _block_fits_lds(self, b, B):
-        """Worth trying lad_f16_block_fwd (include/lad_hip.h)?  Identity block; 64 channels on >= 256 images of at most 512 positions
-        (the boundary strips of level 1), or 16 / 32 channels on >= 512 small images (the strips of level 2, the windows at levels
-        3 and 4).  The entry point itself answers LAD_NOT_COVERED for what does not fit a CU's LDS."""
-        c = b.conv1
-        if b.sc_conv is not None or c.stride != 1 or c.taps != 9 or c.cin != c.cout:
-            return False
-        img = (c.h_in + 1) * (c.w_in + 1)
-        if c.cin == 64:
-            return self.strip_block_fused and B >= 256 and img <= 512 and img + c.w_in <= 562
-        return self.small_block_fused and c.cin in (16, 32) and B >= 512 and img <= 2048
+    def _s2_entry_f16(self, b, launch_one, launch_sc, rides):
+        """conv1 (-> slot 0) and the 1x1 shortcut (-> slot 1) of the down-sampling block b in half precision: ONE launch
+        (launch_sc()) when the shortcut rides, else launch_one(convolution, its BatchNorm, slot, relu) for each; with the event
+        marks bench.py keys on."""
+        if rides:
+            label = f"conv_f16_s2sc<{b.conv1.cin},{b.conv1.cout}>"
+            t0 = self._mark(label)
+            launch_sc()
+            self._mark_end(label, t0)
+            return
+        for cs, bn, slot, relu in ((b.conv1, b.bn1, 0, 1), (b.sc_conv, b.sc_bn, 1, 0)):
+            label = f"conv_f16_s2<{cs.cin},{cs.cout},{cs.taps}>"
+            t0 = self._mark(label)
+            launch_one(cs, bn, slot, relu)
+            self._mark_end(label, t0)
 
-    def _eval_tail(self, half, p, cur, B):
+    def _s2_plain_f16(self, b, src, dst, B, h, w, rides):
+        """... on B whole images of h x w at the device pointer src; dst: the pointers of the two outputs."""
+        lib, st = self.lib(), self._st()
+
+        def one(cs, bn, slot, relu):
+            _hip.check(lib.lad_f16_conv_s2_fwd(src, *self._f16_args(cs, bn), dst[slot], B, h, w, cs.cin, cs.cout, cs.taps, relu, st),
+                       "lad_f16_conv_s2_fwd " + cs.name)
+
+        def both():
+            _hip.check(lib.lad_f16_conv_s2_fwd_sc(src, *self._f16_args(b.conv1, b.bn1), dst[0], *self._f16_args(b.sc_conv, b.sc_bn), dst[1],
+                                                  B, h, w, b.conv1.cin, b.conv1.cout, 1, st), "lad_f16_conv_s2_fwd_sc " + b.conv1.name)
+        self._s2_entry_f16(b, one, both, rides)
+
+    def _s2_mapped_f16(self, b, src, dst, wmap, rides, strips_resident=False):
+        """... reading every image through the window map of include/lad_hip.h, wmap = (images, H, W, band, strip rows, strip shift,
+        first stream row, phases, rows of a phase image, rows of src, output rows per image or 0 for all), from the tensor src
+        ([strips][stream(s)]).  strips_resident: the one-launch form is tried on lad_f16_conv_s2_strips_fwd first (the strips' input
+        rows resident in LDS as parity classes instead of gathered per lane: csrc/s2strip_f16.hip, round 6)."""
+        lib, st = self.lib(), self._st()
+
+        def one(cs, bn, slot, relu):
+            _hip.check(lib.lad_f16_conv_s2_fwd_mapped(_hip.ptr(src), *self._f16_args(cs, bn), _hip.ptr(dst[slot]), *wmap,
+                                                      cs.cin, cs.cout, cs.taps, relu, st), "lad_f16_conv_s2_fwd_mapped " + cs.name)
+
+        def both():
+            args = (_hip.ptr(src), *self._f16_args(b.conv1, b.bn1), _hip.ptr(dst[0]), *self._f16_args(b.sc_conv, b.sc_bn), _hip.ptr(dst[1]))
+            if strips_resident:
+                rc = lib.lad_f16_conv_s2_strips_fwd(*args, *wmap[:7], *wmap[9:], st)
+                if rc != _hip.LAD_NOT_COVERED:
+                    _hip.check(rc, "lad_f16_conv_s2_strips_fwd " + b.conv1.name)
+                    return
+            _hip.check(lib.lad_f16_conv_s2_fwd_mapped_sc(*args, *wmap, b.conv1.cin, b.conv1.cout, 1, st),
+                       "lad_f16_conv_s2_fwd_mapped_sc " + b.conv1.name)
+        self._s2_entry_f16(b, one, both, rides)
+
+    def _eval_tail(self, half, p, cur, B, probs_out=None):
+        """Pooling and classifier.  probs_out (predict_windows): the slice of ITS output these windows belong to -- the head writes
+        there (no copy per chunk)."""
         lib, st = self.lib(), self._st()
         last = p["blocks"][-1].conv2
         p["block_out"] = cur
         pool, name = (lib.lad_f16_pool_fwd, "lad_f16_pool_fwd") if half else (lib.lad_pool_fwd, "lad_pool_fwd")
         _hip.check(pool(_hip.ptr(cur), _hip.ptr(p["pooled"]), B, p["h4"], p["w4"], last.cout, st), name)
-        # predict_windows hands in the slice of ITS output these windows belong to: the head writes there (no copy per chunk)
-        probs = self._probs_out if self._probs_out is not None else p["probs"]
+        probs = probs_out if probs_out is not None else p["probs"]
         _hip.check(lib.lad_head_fwd_eval(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(probs), st),
                    "lad_head_fwd_eval")
         return probs
@@ -1058,7 +1267,16 @@ class ResNetEngine:
             raise ValueError(f"precision 'fp16' runs the stage widths {list(BASE_WIDTHS)} (resnet_base) only; this model has "
                              f"{list(self.model.filter_sizes)}: use precision 'fp32'")
 
-    def _forward_eval_any(self, half, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats=0):
+    def _layout(self, blocks, B, H, W, half, run=None):
+        """The layout of a group of windows under the switches as they are now (built once per group size, geometry, switch values
+        and run)."""
+        key = (B, H, W, half, run) + tuple(getattr(self, k) for k in self.INFER_OPTIONS)
+        lay = self._layouts.get(key)
+        if lay is None:
+            lay = self._layouts[key] = stream_layout(blocks, B, H, W, half, {k: getattr(self, k) for k in self.INFER_OPTIONS}, run)
+        return lay
+
+    def _forward_eval_any(self, half, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats=0, probs_out=None):
         """Eval-mode forward of B images taken from a (frames, W) feature matrix (see lad_stem_fwd_eval): every BatchNorm is
         folded into the epilogue of the convolution in front of it, so the whole model is stem + 19 convolution launches +
         pool + head.  half: activations / weights in fp16 on the 16-bit matrix cores (csrc/conv_f16.hip), f32 in and out."""
@@ -1066,171 +1284,131 @@ class ResNetEngine:
             self._require_half()
         p = self._plan_eval(B, H, W, torch.float16 if half else torch.float32)
         blocks = p["blocks"]
+        lay = self._layout(blocks, B, H, W, half)
         self._eval_prepare(blocks, half)
         cur = p["lv"][(H, W)][0]
         fptr = ctypes.c_void_p(feat_flat.data_ptr() + 4 * feat_offset_floats)
         self._eval_stem(half, fptr, cur, 0, B, H, W, frame_stride, frames_avail)
-        cur = self._eval_blocks(half, p, blocks, cur, B)
-        return self._eval_tail(half, p, cur, B)
-
-    def _forward_eval_f16(self, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats=0):
-        return self._forward_eval_any(True, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats)
+        cur = self._eval_blocks(half, p, blocks, cur, B, lay.window_fused, lay.rides)
+        return self._eval_tail(half, p, cur, B, probs_out)
 
     def _forward_eval(self, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats=0):
         return self._forward_eval_any(False, feat_flat, B, H, W, frame_stride, frames_avail, feat_offset_floats)
 
-    def _forward_eval_stream(self, half, feat_flat, B, H, W, frames_avail, feat_offset_floats=0, sup=None):
+    def _forward_eval_stream(self, half, feat_flat, B, H, W, frames_avail, feat_offset_floats=0, run=None, d=0, probs_out=None):
         """The same probabilities for B windows AT A STRIDE OF ONE FRAME, with the full-resolution layers (stem + the stride-1
         blocks of level 1: 75 % of the model's arithmetic) run once over the shared stream and on one boundary strip per
         frame offset instead of on every window (csrc/gather.hip, lad_assemble_windows, for the argument): a ninth of that work.
-        In half precision the second level is shared the same way (_eval_level2_shared).
-        sup (predict_windows, fp16): the streams are computed ONCE for a run of groups -- {"d": this group's first window within the
-        run, "S": windows of the run, "B_max": its largest group, "base": address of the run's first frame, "frames_avail": frames
-        from there on} + what this function keeps in it.  A row of a stream depends on the frames within `band` rows of it only, so
-        every row a window uses is the row the group's own stream image would hold, bit for bit."""
+        In half precision the second level is shared the same way (_stream_level2).  Where everything lies and what is launched is
+        the group's _StreamLayout (stream_layout), kept in the window plan as p["layout"].
+        run (predict_windows, fp16) with d = this group's first window within it: the streams are computed ONCE for a run of
+        groups.  A row of a stream depends on the frames within `band` rows of it only, so every row a window uses is the row the
+        group's own stream image would hold, bit for bit."""
         dtype = torch.float16 if half else torch.float32
         pw = self._plan_eval(B, H, W, dtype)
-        blocks = pw["blocks"]
-        n1 = 0
-        while n1 < len(blocks) and blocks[n1].conv1.stride == 1 and blocks[n1].sc_conv is None and blocks[n1].conv1.h_out == H:
-            n1 += 1
-        band = 1 + 2 * n1                       # 3x3 convolutions at full resolution: the stem + two per block
-        if n1 == 0 or H < 4 * band or B < 2:    # nothing to share
-            return self._forward_eval_any(half, feat_flat, B, H, W, 1, frames_avail, feat_offset_floats)
-        lib, st = self.lib(), self._st()
-        Hs, Ht = B + H - 1, 2 * band
-        ps = self._plan_eval(1, Hs, W, dtype, partial=True)
-        n_strip = B + H - Ht                    # one strip per frame offset: the top rows of one window, the bottom rows of another
-        pt = self._plan_eval(n_strip, Ht, W, dtype, partial=True)
-        for p in (pw, ps, pt):
+        lay = pw["layout"] = self._layout(pw["blocks"], B, H, W, half, None if run is None else (run.S, run.B_max))
+        if lay.mode == "per_window":
+            return self._forward_eval_any(half, feat_flat, B, H, W, 1, frames_avail, feat_offset_floats, probs_out)
+        if lay.run is None:
+            run, d = None, 0
+        plans = {"pw": pw, "ps": self._plan_eval(1, lay.Hs, W, dtype, partial=True),
+                 "pt": self._plan_eval(lay.n_strip, lay.Ht, W, dtype, partial=True)}
+        for p in plans.values():
             self._eval_prepare(p["blocks"], half)
-        esize = 2 if half else 4
-        C = self.stem_cout
-        base = feat_flat.data_ptr() + 4 * feat_offset_floats
-        nb = blocks[n1] if n1 < len(blocks) else None
-        direct = (half and nb is not None and nb.sc_conv is not None and nb.conv1.stride == 2
-                  and (nb.conv1.cin, nb.conv1.cout) == (64, 32) and self.stream_direct)
-        # `direct`: the strips and the stream go into ONE buffer and the stride-2 block that follows reads every window's rows
-        # from where they lie (lad_f16_conv_s2_fwd_windows) -- no assembled copy (1.2 GB written and read per 2048 windows)
-        img_t_rows = (Ht + 1) * (W + 1)
-        cat, out_t, out_s = None, None, None
-        # level 2 shared as well: the stride-2 block and the stride-1 blocks behind it, up to the next stride-2 block
-        k3 = n1 + 1
-        while direct and k3 < len(blocks) and blocks[k3].conv1.stride == 1 and blocks[k3].sc_conv is None:
-            k3 += 1
-        n2 = k3 - n1 - 1
-        margin2 = 1 + 2 * n2                    # stride-1 3x3 convolutions at level 2
-        band2 = band // 2 + 1 + margin2         # rows of a window that differ from the stream at the end of level 2 (either end)
-        Ht2 = 2 * band2                         # level-2 strips, paired like level 1's: top of window s over bottom of window s - shift2
-        shift2 = 2 * (H // 2 - Ht2)
-        share2 = (direct and self.stream_level2 and H % 2 == 0 and k3 < len(blocks) and blocks[k3].sc_conv is not None
-                  and blocks[k3].conv1.stride == 2 and (blocks[k3].conv1.cin, blocks[k3].conv1.cout) == (32, 16)
-                  and H // 2 >= 2 * Ht2)
-        if sup is not None and not share2:
-            sup = None                          # (the run's streams are a feature of the fully shared path)
-        if sup is not None:
-            # ONE buffer for the run: [strips of the current group (room for the largest)][the run's stream]; a group's windows find
-            # their stream rows sup["d"] rows further down
-            n_strip_max, Hs_S = sup["B_max"] + H - Ht, sup["S"] + H - 1
-            sup["stream_row0"] = n_strip_max * img_t_rows
-            n_rows = n_strip_max * img_t_rows + (Hs_S + 1) * (W + 1) + W + 2 + 2 * (W + 1)
-            cat = sup.get("cat")
-            if cat is None:
-                cat = sup["cat"] = self._sup_buffer("l1", n_rows * C, dtype, (sup["S"], sup["B_max"], H, W))
-                psS = self._plan_eval(1, Hs_S, W, dtype, partial=True, owner="l1")
+        bufs = {}
+        src = (feat_flat.data_ptr() + 4 * feat_offset_floats, frames_avail)   # the group's first frame, frames from there on
+        self._stream_level1(lay, plans, bufs, run, src)
+        self._strips_level1(lay, plans, bufs, run, src, d)
+        if lay.mode == "shared2":
+            self._stream_level2(lay, plans, bufs, run, d)
+        return self._stream_tail(lay, plans, bufs, d, probs_out)
+
+    def _stream_level1(self, lay, plans, bufs, run, src):
+        """The level-1 stream: frames [0, B + H - 1) of the group -- or [0, S + H - 1) of the run, once -- as one tall image through
+        the stem and blocks[:n1].  Leaves bufs["cat"] (None in "assembled"), ["stem"] (the kept stem output, or None) and
+        ["stream"] (the stream's level-1 output where it is a tensor of its own: "assembled")."""
+        half, W, C, n1 = lay.half, lay.W, self.stem_cout, lay.n1
+        dtype = torch.float16 if half else torch.float32
+        rows, ride = lay.stream_rows, lay.rides[:n1]
+        if run is not None:
+            # ONE buffer for the run: [strips of the current group (room for the largest)][the run's stream]
+            bufs["cat"] = run.cat
+            if run.cat is None:
+                key = (run.S, run.B_max, lay.H, W)
+                bufs["cat"] = run.cat = self._sup_buffer("l1", lay.cat_rows * C, dtype, key)
+                psS = self._plan_eval(1, rows, W, dtype, partial=True, owner="l1")
                 self._eval_prepare(psS["blocks"], half)
-                if half and self.strip_stem_shared:
+                if lay.stem_kept:
                     # the run's stem output is KEPT (2 GB for a 60-minute channel): the strips' first block reads its inner rows from it
-                    cS = sup["stem"] = self._sup_buffer("l0", int(lib.lad_act_rows(1, Hs_S, W)) * C, dtype, (sup["S"], sup["B_max"], H, W))
+                    cS = run.stem = self._sup_buffer("l0", int(self.lib().lad_act_rows(1, rows, W)) * C, dtype, key)
                 else:
-                    cS = psS["lv"][(Hs_S, W)][0]
-                self._eval_stem(half, ctypes.c_void_p(sup["base"]), cS, 0, 1, Hs_S, W, 1, sup["frames_avail"])
-                self._eval_blocks(half, psS, psS["blocks"][:n1], cS, 1, final_out=cat[sup["stream_row0"] * C:])
-            out_t = cat[:(n_strip * img_t_rows + W + 2) * C]
-            if n_strip < n_strip_max:           # (behind a shorter last group's strips lie an earlier group's: the W + 2 rows its last
-                cat[n_strip * img_t_rows * C:(n_strip * img_t_rows + W + 2) * C].zero_()   # strip reads below itself must be zero)
-        elif direct:
-            # (+ two zero rows: the odd-phase level-2 stream reads the level-1 stream from its second row on)
-            n_rows = n_strip * img_t_rows + (Hs + 1) * (W + 1) + W + 2 + (2 * (W + 1) if share2 else 0)
+                    cS = psS["lv"][(rows, W)][0]
+                self._eval_stem(half, ctypes.c_void_p(run.base), cS, 0, 1, rows, W, 1, run.frames_avail)
+                self._eval_blocks(half, psS, psS["blocks"][:n1], cS, 1, lay.stream_fused, ride, final_out=run.cat[lay.stream_row0 * C:])
+            bufs["stem"], bufs["stream"] = run.stem, None
+            return
+        pw, ps = plans["pw"], plans["ps"]
+        cat = out_s = None
+        if lay.cat_rows is not None:
             cat = pw.get("l1cat")
-            if cat is None or cat.numel() != n_rows * C:
-                cat = pw["l1cat"] = torch.zeros(n_rows * C, device=self.device, dtype=dtype)
-            out_t = cat[:(n_strip * img_t_rows + W + 2) * C]    # (the strips' tail rows are the stream's border row: zeros either way)
-            out_s = cat[n_strip * img_t_rows * C:]
-        stem_keep, stem_rows, stem_row0 = (sup.get("stem"), sup["S"] + H - 1, sup["d"]) if sup is not None else (None, Hs, 0)
-        if sup is None:
-            # the stream: frames [0, B + H - 1) of the chunk as one tall image
-            if half and self.strip_stem_shared:
-                if ps.get("stem_keep") is None:
-                    ps["stem_keep"] = torch.zeros(int(lib.lad_act_rows(1, Hs, W)) * C, device=self.device, dtype=dtype)
-                cs_ = stem_keep = ps["stem_keep"]
-            else:
-                cs_ = ps["lv"][(Hs, W)][0]
-            self._eval_stem(half, ctypes.c_void_p(base), cs_, 0, 1, Hs, W, 1, frames_avail)
-            cs_ = self._eval_blocks(half, ps, ps["blocks"][:n1], cs_, 1, final_out=out_s)
-        # the strips: frames [s, s + 2 band) for every offset s (gather.hip: upper half = top of window s, lower half = bottom of
-        # window s - (H - 2 band))
+            if cat is None or cat.numel() != lay.cat_rows * C:
+                cat = pw["l1cat"] = torch.zeros(lay.cat_rows * C, device=self.device, dtype=dtype)
+            out_s = cat[lay.stream_row0 * C:]
+        stem = None
+        if lay.stem_kept:
+            if ps.get("stem_keep") is None:
+                ps["stem_keep"] = torch.zeros(int(self.lib().lad_act_rows(1, rows, W)) * C, device=self.device, dtype=dtype)
+            cs = stem = ps["stem_keep"]
+        else:
+            cs = ps["lv"][(rows, W)][0]
+        self._eval_stem(half, ctypes.c_void_p(src[0]), cs, 0, 1, rows, W, 1, src[1])
+        bufs["cat"], bufs["stem"] = cat, stem
+        bufs["stream"] = self._eval_blocks(half, ps, ps["blocks"][:n1], cs, 1, lay.stream_fused, ride, final_out=out_s)
+
+    def _strips_level1(self, lay, plans, bufs, run, src, d):
+        """The level-1 strips: frames [s, s + 2 band) for every offset s (gather.hip: upper half = top of window s, lower half =
+        bottom of window s - (H - 2 band)) through the stem and blocks[:n1], into the head of cat.  Leaves bufs["strips"]."""
+        half, W, C, n1, n_strip, Ht = lay.half, lay.W, self.stem_cout, lay.n1, lay.n_strip, lay.Ht
+        lib, st, cat, pt = self.lib(), self._st(), bufs["cat"], plans["pt"]
+        out_t = None
+        if cat is not None:
+            # (the strips' tail rows are the stream's border row: zeros either way -- except behind a run's shorter last group, where
+            # an earlier group's strips lie: the W + 2 rows its last strip reads below itself must be zero)
+            out_t = cat[:(n_strip * lay.img_t_rows + W + 2) * C]
+            if n_strip < lay.n_strip_max:
+                cat[n_strip * lay.img_t_rows * C:(n_strip * lay.img_t_rows + W + 2) * C].zero_()
         ct = None
         b0 = pt["blocks"][0]
-        if half and self.strip_stem_shared and stem_keep is not None and Ht >= 3 and self._block_fits_lds(b0, n_strip) and b0.conv1.cin == 64:
+        fused, ride = lay.strip_fused, lay.rides[:n1]
+        if lay.strip_stem_rows:
             # Rows 1 .. Ht - 2 of strip s ARE rows s + 1 .. of the stream's stem output (their input frames lie inside the strip either way):
             # the first block's launch takes them from there and computes the strip's first and last row itself
             # (lad_f16_block_fwd_stem_rows; round 6) -- no stem launch for the strips, no strip-sized stem tensor written or read
             y0 = out_t if n1 == 1 else pt["lv"][(Ht, W)][1]
             label = f"block_f16<{b0.conv1.cin}>"
             t0 = self._mark(label)
-            rc = lib.lad_f16_block_fwd_stem_rows(_hip.ptr(stem_keep), stem_rows, stem_row0, ctypes.c_void_p(base), max(0, frames_avail),
+            rc = lib.lad_f16_block_fwd_stem_rows(_hip.ptr(bufs["stem"]), lay.stream_rows, d, ctypes.c_void_p(src[0]), max(0, src[1]),
                                                  _hip.ptr(self.stem_w), _hip.ptr(self.stem_bn.fold[0]), _hip.ptr(self.stem_bn.fold[1]),
-                                                 _hip.ptr(b0.conv1.wt_h), _hip.ptr(b0.bn1.fold[0]), _hip.ptr(b0.bn1.fold[1]),
-                                                 _hip.ptr(b0.conv2.wt_h), _hip.ptr(b0.bn2.fold[0]), _hip.ptr(b0.bn2.fold[1]), _hip.ptr(y0),
+                                                 *self._f16_args(b0.conv1, b0.bn1), *self._f16_args(b0.conv2, b0.bn2), _hip.ptr(y0),
                                                  n_strip, Ht, W, st)
             if rc != _hip.LAD_NOT_COVERED:
                 _hip.check(rc, "lad_f16_block_fwd_stem_rows " + b0.conv1.name)
                 self._mark_end(label, t0)
-                ct = y0 if n1 == 1 else self._eval_blocks(half, pt, pt["blocks"][1:n1], y0, n_strip, final_out=out_t)
+                ct = y0 if n1 == 1 else self._eval_blocks(half, pt, pt["blocks"][1:n1], y0, n_strip, fused[1:], ride[1:], final_out=out_t)
         if ct is None:
             ct = pt["lv"][(Ht, W)][0]
-            self._eval_stem(half, ctypes.c_void_p(base), ct, 0, n_strip, Ht, W, 1, frames_avail)
-            ct = self._eval_blocks(half, pt, pt["blocks"][:n1], ct, n_strip, final_out=out_t)
-        if share2:
-            return self._eval_level2_shared(pw, cat, n_rows, n_strip, B, H, W, band, Ht, Hs, n1, k3, band2, Ht2, shift2, sup)
-        if direct:
-            L = pw["lv"][(nb.conv1.h_out, nb.conv1.w_out)]
-            a1, cs2, y = L[0], L[1], L[2]
-            if self._s2_shortcut_rides(nb):
-                label = f"conv_f16_s2sc<{nb.conv1.cin},{nb.conv1.cout}>"
-                t0 = self._mark(label)
-                _hip.check(lib.lad_f16_conv_s2_fwd_mapped_sc(
-                    _hip.ptr(cat), _hip.ptr(nb.conv1.wt_h), _hip.ptr(nb.bn1.fold[0]), _hip.ptr(nb.bn1.fold[1]), _hip.ptr(a1),
-                    _hip.ptr(nb.sc_conv.wt_h), _hip.ptr(nb.sc_bn.fold[0]), _hip.ptr(nb.sc_bn.fold[1]), _hip.ptr(cs2), B, H, W, band, Ht,
-                    H - Ht, n_strip * img_t_rows, 1, 0, n_rows, 0, nb.conv1.cin, nb.conv1.cout, 1, st),
-                    "lad_f16_conv_s2_fwd_mapped_sc " + nb.conv1.name)
-                self._mark_end(label, t0)
-            else:
-                for cs_spec, bn, dst, relu in ((nb.conv1, nb.bn1, a1, 1), (nb.sc_conv, nb.sc_bn, cs2, 0)):
-                    label = f"conv_f16_s2<{cs_spec.cin},{cs_spec.cout},{cs_spec.taps}>"
-                    t0 = self._mark(label)
-                    _hip.check(lib.lad_f16_conv_s2_fwd_windows(_hip.ptr(cat), _hip.ptr(cs_spec.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                                               _hip.ptr(dst), B, H, W, band, cs_spec.cin, cs_spec.cout, cs_spec.taps, relu, st),
-                               "lad_f16_conv_s2_fwd_windows " + cs_spec.name)
-                    self._mark_end(label, t0)
-            self._conv_eval_f16(nb.conv2, nb.bn2, a1, cs2, y, B, 1)
-            cur = self._eval_blocks(half, pw, blocks[n1 + 1:], y, B)
-            return self._eval_tail(half, pw, cur, B)
-        # every window's level-1 output, then the rest of the model per window
-        cur = pw["lv"][(H, W)][0]
-        _hip.check(lib.lad_assemble_windows(_hip.ptr(cs_), _hip.ptr(ct), _hip.ptr(cur), B, H, W, band, C * esize, st), "lad_assemble_windows")
-        cur = self._eval_blocks(half, pw, blocks[n1:], cur, B)
-        return self._eval_tail(half, pw, cur, B)
+            self._eval_stem(half, ctypes.c_void_p(src[0]), ct, 0, n_strip, Ht, W, 1, src[1])
+            ct = self._eval_blocks(half, pt, pt["blocks"][:n1], ct, n_strip, fused, ride, final_out=out_t)
+        bufs["strips"] = ct
 
-    def _sup_buffer(self, name, numel, dtype, layout):
-        """Zero-initialised buffer of a run's streams (+ the strips of its current group), kept between runs of the same LAYOUT
+    def _sup_buffer(self, name, numel, dtype, run_key):
+        """Zero-initialised buffer of a run's streams (+ the strips of its current group), kept between runs of the same run_key
         (run length, largest group, window geometry: [strips][stream][spare zero rows] -- two runs of equal size but another split
         would find old stream data where zero rows are expected): every region of it is rewritten or explicitly zeroed where a reader
         expects zeros (the W + 2 rows behind a shorter last group's strips); the border rows, tails and spare rows that nobody writes
-        stay as allocated.  A run of another layout REPLACES the buffer and the run-long eval plans that fed it (four activation
+        stay as allocated.  A run of another key REPLACES the buffer and the run-long eval plans that fed it (four activation
         buffers per level: 8 + 2 GB for a 60-minute channel), so a long-lived process holds one run's memory whatever it predicts."""
-        key = ("sup", name, numel, dtype, layout)
+        key = ("sup", name, numel, dtype, run_key)
         buf = self._sup_cache.get(key)
         if buf is None:
             for k in [k for k in self._sup_cache if k[1] == name]:
@@ -1251,155 +1429,108 @@ class ResNetEngine:
             return
         for gk in [gk for gk, gv in self._geom_specs.items() if gv[0] is blocks]:
             del self._geom_specs[gk]
-        for tags in (self._fold_tag if isinstance(self._fold_tag, dict) else {}, getattr(self, "_f16_tags", None) or {}, self._packed_version):
+        for tags in (self._fold_tag, self._f16_tags, self._packed_version):
             tags.pop(id(blocks), None)
         for k in [k for k in self._pack_tables if k[0] == id(blocks)]:
             del self._pack_tables[k]
 
-    def _eval_level2_shared(self, pw, cat, cat_rows, n_strip, B, H, W, band, Ht, Hs, n1, k3, band2, Ht2, shift2, sup=None):
+    def _stream_level2(self, lay, plans, bufs, run, d):
         """fp16 sliding windows, second resolution level.  Row r of window i at level 2 looks at level-1 rows 2r - 1 .. 2r + 1 of the
         window = stream rows i + 2r - 1 ..: windows i = 2j + phase share ONE level-2 stream per phase (row j + r of it), which
         is the stride-2 block run on the level-1 stream from row `phase` on; the rows that see a window's own top / bottom
         (band2 of them, either end) come from strips of Ht2 = 2 band2 rows, paired like level 1's (strip s = the first band2
         rows of window s over the last band2 of window s - shift2: the same 12 positions of the same phase stream, padded
         above for the one and below for the other), whose stride-2 layer reads the level-1 strips and stream through the
-        window map.  The stride-2 block of level 3 then reads every window from the two streams and the strips
-        (lad_f16_conv_s2_fwd_mapped, phases = 2), and the rest of the model runs per window as before."""
-        lib, st = self.lib(), self._st()
+        window map.  Leaves bufs["cat2"] = [strips][phase-0 stream][phase-1 stream]; the two streams are computed once per run."""
         dtype, esize = torch.float16, 2
-        blocks = pw["blocks"]
-        nb = blocks[n1]
+        H, W, n1, k3, Ht2, W2, h2s = lay.H, lay.W, lay.n1, lay.k3, lay.Ht2, lay.W2, lay.h2s
+        pw, cat = plans["pw"], bufs["cat"]
+        nb = pw["blocks"][n1]
         C1, C2 = nb.conv1.cin, nb.conv1.cout
-        H2, W2 = nb.conv1.h_out, nb.conv1.w_out
-        Wp, Wp2 = W + 1, W2 + 1
-        Hs_S = Hs if sup is None else sup["S"] + H - 1             # rows of the level-1 stream image (the group's / the run's)
-        h2s = (Hs_S + 1) // 2                                      # rows of a level-2 stream image
         ps2 = self._plan_eval(2, 2 * h2s, W, dtype, partial=True)
-        n_strip2 = B + shift2
-        n_strip2_max = n_strip2 if sup is None else sup["B_max"] + shift2
-        pt2 = self._plan_eval(n_strip2, 2 * Ht2, W, dtype, partial=True)
+        pt2 = self._plan_eval(lay.n_strip2, 2 * Ht2, W, dtype, partial=True)
         for p in (ps2, pt2):
             self._eval_prepare(p["blocks"], True)
-        img_t2, img_s2 = (Ht2 + 1) * Wp2, (h2s + 1) * Wp2
-        stream2_base = n_strip2_max * img_t2                       # first row of the phase-0 stream image in cat2
-        rows2 = stream2_base + 2 * img_s2 + W2 + 2
-        d = 0 if sup is None else sup["d"]                          # this group's first window within the run (even)
-        if sup is None:
+        streams_ready = False
+        if run is None:
             cat2 = pw.get("l2cat")
-            if cat2 is None or cat2.numel() != rows2 * C2:
-                cat2 = pw["l2cat"] = torch.zeros(rows2 * C2, device=self.device, dtype=dtype)
-            stream_base = n_strip * (Ht + 1) * Wp
+            if cat2 is None or cat2.numel() != lay.rows2 * C2:
+                cat2 = pw["l2cat"] = torch.zeros(lay.rows2 * C2, device=self.device, dtype=dtype)
+        elif run.cat2 is not None:
+            cat2, streams_ready = run.cat2, True
         else:
-            cat2 = sup.get("cat2")
-            stream_base = sup["stream_row0"]
-        streams_ready = cat2 is not None and sup is not None
-        if sup is not None and cat2 is None:
-            cat2 = sup["cat2"] = self._sup_buffer("l2", rows2 * C2, dtype, (sup["S"], sup["B_max"], H, W))
+            cat2 = run.cat2 = self._sup_buffer("l2", lay.rows2 * C2, dtype, (run.S, run.B_max, H, W))
             ps2 = self._plan_eval(2, 2 * h2s, W, dtype, partial=True, owner="l2")   # (a replaced buffer took the old run's plans with it)
             self._eval_prepare(ps2["blocks"], True)
-        out_t2 = cat2[:(n_strip2 * img_t2 + W2 + 2) * C2]
-        if n_strip2 < n_strip2_max:
-            cat2[n_strip2 * img_t2 * C2:(n_strip2 * img_t2 + W2 + 2) * C2].zero_()
-        out_s2 = cat2[stream2_base * C2:]
-        stream_row0 = stream_base + d * Wp                          # row 0 of this group's window 0 in the level-1 stream
-        stream2_row0 = stream2_base + (d // 2) * Wp2                # ... in the phase streams of level 2 (d even: phases keep their parity)
+        bufs["cat2"] = cat2
+        out_t2 = cat2[:(lay.n_strip2 * lay.img_t2 + W2 + 2) * C2]
+        if lay.n_strip2 < lay.n_strip2_max:
+            cat2[lay.n_strip2 * lay.img_t2 * C2:(lay.n_strip2 * lay.img_t2 + W2 + 2) * C2].zero_()
 
-        def s2_launches(b, launch, launch_sc=None):
-            """conv1 (-> slot 0) and the 1x1 shortcut (-> slot 1) of the down-sampling block b: one launch (launch_sc) or two."""
-            if launch_sc is not None and self._s2_shortcut_rides(b):
-                label = f"conv_f16_s2sc<{b.conv1.cin},{b.conv1.cout}>"
-                t0 = self._mark(label)
-                launch_sc(b)
-                self._mark_end(label, t0)
-                return
-            for cs_, bn, slot, relu in ((b.conv1, b.bn1, 0, 1), (b.sc_conv, b.sc_bn, 1, 0)):
-                label = f"conv_f16_s2<{cs_.cin},{cs_.cout},{cs_.taps}>"
-                t0 = self._mark(label)
-                launch(cs_, bn, slot, relu)
-                self._mark_end(label, t0)
-
-        def sc_args(b):
-            return (_hip.ptr(b.conv1.wt_h), _hip.ptr(b.bn1.fold[0]), _hip.ptr(b.bn1.fold[1])), \
-                   (_hip.ptr(b.sc_conv.wt_h), _hip.ptr(b.sc_bn.fold[0]), _hip.ptr(b.sc_bn.fold[1]))
-
-        def rest_of_level(p, b, L, n_img, final_out):
-            n_after = k3 - n1 - 1
-            y = final_out if n_after == 0 else L[2]
+        def rest_of_level(p, b, L, n_img, fused, final_out):
+            y = final_out if k3 == n1 + 1 else L[2]
             self._conv_eval_f16(b.conv2, b.bn2, L[0], L[1], y, n_img, 1)
-            if n_after:
-                self._eval_blocks(True, p, p["blocks"][n1 + 1:k3], y, n_img, final_out=final_out)
+            if k3 > n1 + 1:
+                self._eval_blocks(True, p, p["blocks"][n1 + 1:k3], y, n_img, fused, lay.rides[n1 + 1:k3], final_out=final_out)
 
-        # the two phase streams (once per run)
-        Ls = None if streams_ready else ps2["lv"][(h2s, W2)]
-        bs = ps2["blocks"][n1]
-        for phase in (() if streams_ready else (0, 1)):
-            src = ctypes.c_void_p(cat.data_ptr() + (stream_base + phase * Wp) * C1 * esize)
+        if not streams_ready:   # the two phase streams: the stride-2 block on the level-1 stream from row `phase` on
+            Ls, bs = ps2["lv"][(h2s, W2)], ps2["blocks"][n1]
+            for phase in (0, 1):
+                src = ctypes.c_void_p(cat.data_ptr() + (lay.stream_row0 + phase * (W + 1)) * C1 * esize)
+                off = phase * lay.img_s2 * C2 * esize
+                self._s2_plain_f16(bs, src, (ctypes.c_void_p(Ls[0].data_ptr() + off), ctypes.c_void_p(Ls[1].data_ptr() + off)),
+                                   1, lay.stream_rows, W, lay.rides[n1])
+            rest_of_level(ps2, bs, Ls, 2, lay.stream2_fused, cat2[lay.stream2_base * C2:])
+        # the strips: the first and the last Ht2 rows of every window, read from the level-1 strips and stream where they lie
+        Lt, bt = pt2["lv"][(Ht2, W2)], pt2["blocks"][n1]
+        wmap = (lay.B, H, W, lay.band, lay.Ht, H - lay.Ht, lay.stream_row0 + d * (W + 1), 1, 0, lay.cat_rows, Ht2)
+        self._s2_mapped_f16(bt, cat, Lt, wmap, lay.rides[n1], lay.strips2_resident)
+        rest_of_level(pt2, bt, Lt, lay.n_strip2, lay.strip2_fused, out_t2)
 
-            def launch(cs_, bn, slot, relu, src=src, phase=phase):
-                dst = ctypes.c_void_p(Ls[slot].data_ptr() + phase * img_s2 * C2 * esize)
-                _hip.check(lib.lad_f16_conv_s2_fwd(src, _hip.ptr(cs_.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]), dst, 1, Hs_S, W,
-                                                   cs_.cin, cs_.cout, cs_.taps, relu, st), "lad_f16_conv_s2_fwd " + cs_.name)
-
-            def launch_sc(b, src=src, phase=phase):
-                off = phase * img_s2 * C2 * esize
-                c1, c2 = sc_args(b)
-                _hip.check(lib.lad_f16_conv_s2_fwd_sc(src, *c1, ctypes.c_void_p(Ls[0].data_ptr() + off), *c2,
-                                                      ctypes.c_void_p(Ls[1].data_ptr() + off), 1, Hs_S, W, b.conv1.cin, b.conv1.cout, 1, st),
-                           "lad_f16_conv_s2_fwd_sc " + b.conv1.name)
-            s2_launches(bs, launch, launch_sc)
-        if not streams_ready:
-            rest_of_level(ps2, bs, Ls, 2, out_s2)
-        # the strips: the first and the last Ht2 rows of every window
-        Lt = pt2["lv"][(Ht2, W2)]
-        bt = pt2["blocks"][n1]
-
-        def launch_t(cs_, bn, slot, relu):
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped(_hip.ptr(cat), _hip.ptr(cs_.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                                      _hip.ptr(Lt[slot]), B, H, W, band, Ht, H - Ht, stream_row0, 1, 0, cat_rows, Ht2,
-                                                      cs_.cin, cs_.cout, cs_.taps, relu, st), "lad_f16_conv_s2_fwd_mapped " + cs_.name)
-
-        def launch_t_sc(b):
-            c1, c2 = sc_args(b)
-            if self.strip2_resident and (b.conv1.cin, b.conv1.cout) == (64, 32):
-                # the strips' input rows resident in LDS as parity classes instead of gathered per lane (csrc/s2strip_f16.hip, round 6)
-                rc = lib.lad_f16_conv_s2_strips_fwd(_hip.ptr(cat), *c1, _hip.ptr(Lt[0]), *c2, _hip.ptr(Lt[1]), B, H, W, band, Ht, H - Ht,
-                                                    stream_row0, cat_rows, Ht2, st)
+    def _stream_tail(self, lay, plans, bufs, d, probs_out):
+        """Everything behind the shared levels, per window: the down-sampling block that leaves them reads every window's rows from
+        the strips and the stream(s) where they lie ("shared2": from cat2, two phases; "direct": from cat), or from an assembled
+        copy of every window's level-1 output ("assembled")."""
+        half, B, H, W, n1 = lay.half, lay.B, lay.H, lay.W, lay.n1
+        pw = plans["pw"]
+        blocks = pw["blocks"]
+        fused, ride = lay.window_fused, lay.rides
+        if lay.mode == "assembled":
+            cur = pw["lv"][(H, W)][0]
+            _hip.check(self.lib().lad_assemble_windows(_hip.ptr(bufs["stream"]), _hip.ptr(bufs["strips"]), _hip.ptr(cur), B, H, W, lay.band,
+                                                       self.stem_cout * (2 if half else 4), self._st()), "lad_assemble_windows")
+            cur = self._eval_blocks(half, pw, blocks[n1:], cur, B, fused[n1:], ride[n1:])
+            return self._eval_tail(half, pw, cur, B, probs_out)
+        if lay.mode == "direct":
+            k, src = n1, bufs["cat"]
+            wmap = (B, H, W, lay.band, lay.Ht, H - lay.Ht, lay.stream_row0, 1, 0, lay.cat_rows, 0)
+        else:
+            # (d even: the phases keep their parity, the group's window 0 lies d / 2 rows down either phase stream)
+            k, src = lay.k3, bufs["cat2"]
+            wmap = (B, lay.H2, lay.W2, lay.band2, lay.Ht2, lay.shift2, lay.stream2_base + (d // 2) * (lay.W2 + 1), 2, lay.img_s2, lay.rows2, 0)
+            if lay.tail_fused:   # in ONE launch where the tail kernel covers the geometry (csrc/tail_f16.hip, round 6)
+                probs = probs_out if probs_out is not None else pw["probs"]
+                label = "tail_f16"
+                t0 = self._mark(label)
+                rc = self.lib().lad_f16_tail_fwd(_hip.ptr(src), *wmap[:-1], self._tail_params(blocks[k:]), self._head_params, pw["feat"],
+                                                 _hip.ptr(probs), self._st())
                 if rc != _hip.LAD_NOT_COVERED:
-                    _hip.check(rc, "lad_f16_conv_s2_strips_fwd " + b.conv1.name)
-                    return
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped_sc(_hip.ptr(cat), *c1, _hip.ptr(Lt[0]), *c2, _hip.ptr(Lt[1]), B, H, W, band, Ht, H - Ht,
-                                                         stream_row0, 1, 0, cat_rows, Ht2, b.conv1.cin, b.conv1.cout, 1, st),
-                       "lad_f16_conv_s2_fwd_mapped_sc " + b.conv1.name)
-        s2_launches(bt, launch_t, launch_t_sc)
-        rest_of_level(pt2, bt, Lt, n_strip2, out_t2)
-        # level 3 onwards: per window -- in ONE launch where the tail kernel covers the geometry (csrc/tail_f16.hip, round 6)
-        if self.tail_fused and self._tail_blocks_ok(blocks[k3:]):
-            probs = self._probs_out if self._probs_out is not None else pw["probs"]
-            label = "tail_f16"
-            t0 = self._mark(label)
-            rc = lib.lad_f16_tail_fwd(_hip.ptr(cat2), B, H2, W2, band2, Ht2, shift2, stream2_row0, 2, img_s2, rows2, self._tail_params(blocks[k3:]),
-                                      self._head_params, pw["feat"], _hip.ptr(probs), st)
-            if rc != _hip.LAD_NOT_COVERED:
-                _hip.check(rc, "lad_f16_tail_fwd")
-                self._mark_end(label, t0)
-                return probs
-        b3 = blocks[k3]
-        L3 = pw["lv"][(b3.conv1.h_out, b3.conv1.w_out)]
-
-        def launch_w(cs_, bn, slot, relu):
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped(_hip.ptr(cat2), _hip.ptr(cs_.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                                      _hip.ptr(L3[slot]), B, H2, W2, band2, Ht2, shift2, stream2_row0, 2, img_s2, rows2, 0,
-                                                      cs_.cin, cs_.cout, cs_.taps, relu, st), "lad_f16_conv_s2_fwd_mapped " + cs_.name)
-
-        def launch_w_sc(b):
-            c1, c2 = sc_args(b)
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped_sc(_hip.ptr(cat2), *c1, _hip.ptr(L3[0]), *c2, _hip.ptr(L3[1]), B, H2, W2, band2, Ht2,
-                                                         shift2, stream2_row0, 2, img_s2, rows2, 0, b.conv1.cin, b.conv1.cout, 1, st),
-                       "lad_f16_conv_s2_fwd_mapped_sc " + b.conv1.name)
-        s2_launches(b3, launch_w, launch_w_sc)
-        self._conv_eval_f16(b3.conv2, b3.bn2, L3[0], L3[1], L3[2], B, 1)
-        cur = self._eval_blocks(True, pw, blocks[k3 + 1:], L3[2], B)
-        return self._eval_tail(True, pw, cur, B)
+                    _hip.check(rc, "lad_f16_tail_fwd")
+                    self._mark_end(label, t0)
+                    return probs
+        b = blocks[k]
+        L = pw["lv"][(b.conv1.h_out, b.conv1.w_out)]
+        if lay.mode == "direct" and not ride[k]:   # (two launches: the entry point that needs no map)
+            def one(cs, bn, slot, relu):
+                _hip.check(self.lib().lad_f16_conv_s2_fwd_windows(_hip.ptr(src), *self._f16_args(cs, bn), _hip.ptr(L[slot]), B, H, W, lay.band,
+                                                                  cs.cin, cs.cout, cs.taps, relu, self._st()),
+                           "lad_f16_conv_s2_fwd_windows " + cs.name)
+            self._s2_entry_f16(b, one, None, False)
+        else:
+            self._s2_mapped_f16(b, src, L, wmap, ride[k])
+        self._conv_eval_f16(b.conv2, b.bn2, L[0], L[1], L[2], B, 1)
+        cur = self._eval_blocks(half, pw, blocks[k + 1:], L[2], B, fused[k + 1:], ride[k + 1:])
+        return self._eval_tail(half, pw, cur, B, probs_out)
 
     def _stream_super_cap(self, F):
         """Windows per run of shared streams that the device's free memory allows (half of it): per frame a run keeps five
@@ -1409,22 +1540,6 @@ class ResNetEngine:
         held = sum(b.numel() * b.element_size() for b in self._sup_cache.values())                  # (a run of this size replaces it)
         per_frame = 2 * (6 * (F + 1) * self.stem_cout + 5 * ((F + 1) // 2 + 1) * 32)   # (+ the stem's output at level 1, kept for the strips)
         return max(0, int(0.5 * (free + held)) // per_frame)
-
-    @staticmethod
-    def _tail_blocks_ok(tail):
-        """The layers lad_f16_tail_fwd runs: two (down-sampling block with a 1x1 shortcut, identity block) pairs, 32 -> 16 -> 16 channels."""
-        if len(tail) != 4:
-            return False
-        for k, b in enumerate(tail):
-            down = k % 2 == 0
-            cin = 32 if k == 0 else 16
-            if (b.conv1.cin, b.conv1.cout, b.conv1.taps, b.conv1.stride) != (cin, 16, 9, 2 if down else 1):
-                return False
-            if (b.conv2.cin, b.conv2.cout, b.conv2.taps, b.conv2.stride) != (16, 16, 9, 1):
-                return False
-            if down != (b.sc_conv is not None) or (down and (b.sc_conv.cin, b.sc_conv.cout, b.sc_conv.taps, b.sc_conv.stride) != (cin, 16, 1, 2)):
-                return False
-        return True
 
     def _tail_params(self, tail):
         """HOST array of the 30 device pointers lad_f16_tail_fwd takes: {fp16 weight image, folded scale, folded shift} per convolution
@@ -1469,26 +1584,22 @@ class ResNetEngine:
         direct = out.dtype == torch.float32 and out.is_contiguous() and out.device == feats.device
         # fp16: the streams of levels 1 and 2 once per RUN of groups (even group sizes: a group then starts at an even window of its run)
         use_runs = half and stream and self.stream_super and chunk % 2 == 0 and stop - start > chunk
-        sup = None
-        try:
-            while i < stop:
-                B = min(chunk, stop - i)
-                dst = out[i - start:i - start + B]
-                self._probs_out = dst if direct else None
-                if use_runs and (sup is None or i >= sup["i0"] + sup["S"]):
-                    S = min(stop - i, max(chunk, min(STREAM_SUPER_MAX, self._stream_super_cap(F)) // chunk * chunk))
-                    sup = {"i0": i, "S": S, "B_max": min(chunk, S), "base": flat.data_ptr() + 4 * i * F, "frames_avail": T - i}
-                if sup is not None:
-                    sup["d"] = i - sup["i0"]
-                if stream:
-                    probs = self._forward_eval_stream(half, flat, B, n_frames, F, frames_avail=T - i, feat_offset_floats=i * F, sup=sup)
-                else:
-                    probs = self._forward_eval_any(half, flat, B, n_frames, F, 1, frames_avail=T - i, feat_offset_floats=i * F)
-                if not direct:
-                    dst.copy_(probs[:B])
-                i += B
-        finally:
-            self._probs_out = None
+        run = None
+        while i < stop:
+            B = min(chunk, stop - i)
+            dst = out[i - start:i - start + B]
+            if use_runs and (run is None or i >= run.i0 + run.S):
+                S = min(stop - i, max(chunk, min(STREAM_SUPER_MAX, self._stream_super_cap(F)) // chunk * chunk))
+                run = _StreamRun(i, S, min(chunk, S), flat.data_ptr() + 4 * i * F, T - i)
+            if stream:
+                probs = self._forward_eval_stream(half, flat, B, n_frames, F, frames_avail=T - i, feat_offset_floats=i * F, run=run,
+                                                  d=0 if run is None else i - run.i0, probs_out=dst if direct else None)
+            else:
+                probs = self._forward_eval_any(half, flat, B, n_frames, F, 1, frames_avail=T - i, feat_offset_floats=i * F,
+                                               probs_out=dst if direct else None)
+            if not direct:
+                dst.copy_(probs[:B])
+            i += B
         return out
 
     # ------------------------------------------------------------------------------------ backward

@@ -375,3 +375,165 @@ def test_train_schedule_of_resnet_base_and_of_the_augmentation_widths():
     for bad in (dict(kind="f32", in_coef=True), dict(kind="f32", bn=True), dict(kind="b3c", bn=True), dict(kind="b3", bn=False)):
         with pytest.raises(_hip.LadHipError):
             engine.conv_wgrad_entry(**bad)
+
+
+# ------------------------------------------------------------------------------------------ the inference layout (engine.stream_layout)
+_INFER_ON = dict(stream_direct=True, stream_level2=True, stream_super=True, strip_block_fused=True, small_block_fused=True, tail_fused=True,
+                 strip2_resident=True, strip_stem_shared=True, f16_s2_shortcut_fused=True)   # ResNetEngine's defaults
+_L1 = ("n_strip", "stream_row0", "cat_rows")
+_L2 = ("shift2", "n_strip2", "h2s", "img_s2", "stream2_base", "rows2")
+# (B, H): the literal table of the shared layouts of resnet_base, fp16, every switch on, no run
+_SHARED2 = {
+    (8192, 100): (8282, 4099590, 4472866, 76, 8268, 4146, 95381, 2472132, 2662918),
+    (201, 100): (291, 144045, 157726, 76, 277, 150, 3473, 82823, 89793),
+    (64, 100): (154, 76230, 83746, 76, 140, 82, 1909, 41860, 45702),
+    (2, 100): (92, 45540, 50266, 76, 78, 51, 1196, 23322, 25738),
+    (64, 96): (150, 74250, 81586, 72, 136, 80, 1863, 40664, 44414),
+    (64, 90): (144, 71280, 78346, 66, 130, 77, 1794, 38870, 42482),
+    (64, 120): (174, 86130, 94546, 96, 160, 92, 2139, 47840, 52142),
+}
+_WITH_RUN = [((1200, 600), 600), ((1711, 600), 511)]
+
+
+def _base_layout(B, H=100, half=True, run=None, **flip):
+    import engine
+    return engine.stream_layout(engine.block_geometry(64, [64, 32, 16, 16], H, 44, True), B, H, 44, half, {**_INFER_ON, **flip}, run)
+
+
+def _all_layouts():
+    """Every layout the tests below name."""
+    import engine
+    out = [_base_layout(B, H) for B, H in _SHARED2] + [_base_layout(64, 101), _base_layout(1), _base_layout(64, half=False)]
+    out += [_base_layout(B, run=run) for run, B in _WITH_RUN]
+    out += [_base_layout(8192, **{k: False}) for k in _INFER_ON] + [_base_layout(B) for B in (165, 166, 435, 436, 511, 512)]
+    out.append(engine.stream_layout(engine.block_geometry(64, [128, 64, 32, 32], 128, 44, False), 64, 128, 44, False, _INFER_ON))
+    return out
+
+
+def test_stream_layout_of_resnet_base_as_a_literal_table():
+    """engine.stream_layout: where the strips and streams of a group of sliding windows lie, restated by hand -- group sizes from 2 to
+    8192, window lengths with every level even, an odd level 2 and an odd level 1, runs of groups with a full and a short last group,
+    fp32, the augmentation widths."""
+    import engine
+    for (B, H), want in _SHARED2.items():
+        lay = _base_layout(B, H)
+        assert lay.mode == "shared2" and lay.run is None and (lay.B, lay.H, lay.W, lay.half) == (B, H, 44, True)
+        assert tuple(getattr(lay, f) for f in _L1 + _L2) == want, (B, H)
+        assert (lay.n1, lay.band, lay.Ht, lay.img_t_rows, lay.k3, lay.band2, lay.Ht2, lay.img_t2) == (2, 5, 10, 495, 4, 6, 12, 299)
+        assert (lay.Hs, lay.stream_rows, lay.n_strip_max, lay.n_strip2_max) == (B + H - 1, B + H - 1, lay.n_strip, lay.n_strip2)
+        assert (lay.H2, lay.W2) == (H // 2, 22)
+    odd = _base_layout(64, 101)          # odd at level 1: the phases of level 2 do not exist
+    assert odd.mode == "direct" and (odd.n_strip, odd.stream_row0, odd.cat_rows) == (155, 76725, 76725 + 165 * 45 + 46)
+    assert all(getattr(odd, f) is None for f in _L2 + ("k3", "H2", "W2", "band2", "Ht2", "img_t2", "n_strip2_max"))
+    one = _base_layout(1)
+    assert one.mode == "per_window" and (one.n1, one.band) == (2, 5)
+    assert all(getattr(one, f) is None for f in _L1 + _L2 + ("Ht", "Hs", "n_strip_max", "img_t_rows"))
+    # a run of groups: the stream is the run's, the strips' room is the largest group's
+    lay = _base_layout(600, run=(1200, 600))
+    assert lay.mode == "shared2" and lay.run == (1200, 600) and lay.stream_rows == 1299 and lay.Hs == 699
+    assert (lay.stream_row0, lay.cat_rows, lay.h2s, lay.stream2_base, lay.rows2) == (341550, 400186, 650, 202124, 232094)
+    lay = _base_layout(511, run=(1711, 600))                     # the short last group
+    assert (lay.n_strip, lay.n_strip_max, lay.n_strip2, lay.n_strip2_max) == (601, 690, 587, 676)
+    assert (lay.cat_rows, lay.rows2) == (423181, 243824)
+    # a run is a feature of the fully shared path: elsewhere it comes back as None and the layout is the group's own
+    assert _base_layout(64, 101, run=(128, 64)) == odd and _base_layout(1, run=(601, 600)) == one
+    assert _base_layout(600, run=(1200, 600), stream_level2=False) == _base_layout(600, stream_level2=False)
+    assert _base_layout(600, run=(1200, 600), stream_super=False) == _base_layout(600, stream_super=False)
+    f32 = _base_layout(64, half=False)
+    assert f32.mode == "assembled" and (f32.n_strip, f32.Ht, f32.Hs, f32.stream_row0, f32.cat_rows, f32.rows2) == (154, 10, 163, None, None, None)
+    assert not any(f32.window_fused + f32.rides + f32.strip_fused + f32.stream_fused) and not (f32.stem_kept or f32.strip_stem_rows or f32.tail_fused)
+    aug = engine.stream_layout(engine.block_geometry(64, [128, 64, 32, 32], 128, 44, False), 64, 128, 44, False, _INFER_ON)
+    assert aug.mode == "per_window" and aug.n1 == 0                # (block1.0 changes the width: no identity block at full resolution)
+
+
+def test_stream_layout_launch_choices_and_switches():
+    """Which launches a layout tries: the defaults at 8192 windows, every switch of INFER_OPTIONS flipped alone (which fields move, and
+    no others), and the image-count thresholds of the fused blocks."""
+    import engine
+    F, T = False, True
+    default = _base_layout(8192)
+    assert default.window_fused == (F, F, F, T, F, T, F, T) and default.rides == (F, F, T, F, F, F, T, F)
+    assert (default.stream_fused, default.strip_fused, default.stream2_fused, default.strip2_fused) == ((F, F), (T, T), (F,), (T,))
+    assert (default.stem_kept, default.strip_stem_rows, default.strips2_resident, default.tail_fused) == (T, T, T, T)
+    none2 = dict.fromkeys(("k3", "H2", "W2", "band2", "Ht2", "shift2", "h2s", "n_strip2", "n_strip2_max", "img_t2", "img_s2", "stream2_base", "rows2"))
+    off2 = dict(none2, stream2_fused=(), strip2_fused=(), strips2_resident=F, tail_fused=F)
+    moves = {
+        "stream_direct": dict(off2, mode="assembled", stream_row0=None, cat_rows=None),
+        "stream_level2": dict(off2, mode="direct", cat_rows=4472866 - 90),       # (no spare rows for an odd phase)
+        "stream_super": {},                                                       # (moves a layout with a run only: below)
+        "strip_block_fused": dict(strip_fused=(F, F), strip_stem_rows=F),
+        "small_block_fused": dict(window_fused=(F,) * 8, strip2_fused=(F,)),
+        "tail_fused": dict(tail_fused=F),
+        "strip2_resident": dict(strips2_resident=F),
+        "strip_stem_shared": dict(stem_kept=F, strip_stem_rows=F),
+        "f16_s2_shortcut_fused": dict(rides=(F,) * 8, strips2_resident=F),
+    }
+    assert sorted(moves) == sorted(engine.ResNetEngine.INFER_OPTIONS) == sorted(_INFER_ON)
+    for flag, moved in moves.items():
+        assert _base_layout(8192, **{flag: False}) == default._replace(**moved), flag
+    with_run = _base_layout(8192, run=(16384, 8192))
+    assert with_run.run == (16384, 8192) and with_run.stream_rows == 16483 and with_run.n_strip_max == default.n_strip
+    assert _base_layout(8192, run=(16384, 8192), stream_super=False) == default
+    # 64-channel strip blocks from 256 strips on (and with them the first block with the stem inside)
+    a, b = _base_layout(165), _base_layout(166)
+    assert (a.n_strip, b.n_strip) == (255, 256)
+    assert (a.strip_fused, a.strip_stem_rows, b.strip_fused, b.strip_stem_rows) == ((F, F), F, (T, T), T) and a.stem_kept and b.stem_kept
+    # 32-channel blocks of the level-2 strips from 512 strips on
+    a, b = _base_layout(435), _base_layout(436)
+    assert (a.n_strip2, b.n_strip2) == (511, 512) and (a.strip2_fused, b.strip2_fused) == ((F,), (T,))
+    assert a.window_fused == b.window_fused == (F,) * 8
+    # 16- / 32-channel blocks of the per-window levels from 512 windows on
+    a, b = _base_layout(511), _base_layout(512)
+    assert a.window_fused == (F,) * 8 and b.window_fused == (F, F, F, T, F, T, F, T)
+    # the rules themselves
+    blocks = engine.block_geometry(64, [64, 32, 16, 16], 100, 44, True)
+    assert engine._tail_blocks_ok(blocks[4:]) and not engine._tail_blocks_ok(blocks[3:]) and not engine._tail_blocks_ok(blocks[5:])
+    assert engine._block_fits_lds(blocks[0], 256, _INFER_ON, (10, 44)) and not engine._block_fits_lds(blocks[0], 256, _INFER_ON, (11, 44))
+    assert not engine._block_fits_lds(blocks[0], 256, _INFER_ON) and not engine._block_fits_lds(blocks[2], 4096, _INFER_ON)
+    assert [engine._s2_shortcut_rides(b, _INFER_ON) for b in (blocks[2], blocks[4], blocks[6])] == [T, F, T]
+
+
+def test_stream_layout_regions_are_disjoint_and_inside_their_buffers():
+    """In every layout above: cat = [strips][W + 2 zeroed rows behind a short group's strips][stream image][spare rows] and cat2 =
+    [strips][zeroed rows][phase-0 stream][phase-1 stream][tail], in order, disjoint, inside cat_rows / rows2; and the last group of a
+    run (d = S - B) reads its windows inside the stream image(s)."""
+    seen = set()
+    for lay in _all_layouts():
+        seen.add(lay.mode)
+        if lay.cat_rows is None:
+            assert lay.mode in ("per_window", "assembled") and lay.stream_row0 is None and lay.rows2 is None
+            continue
+        Wp, (S, B_max) = lay.W + 1, lay.run or (lay.B, lay.B)
+        assert lay.n_strip <= lay.n_strip_max and lay.B <= B_max and lay.n_strip_max == B_max + lay.H - lay.Ht
+        strips_end = lay.n_strip * lay.img_t_rows
+        zero_end = strips_end + lay.W + 2                     # what the last strip reads below itself
+        stream_end = lay.stream_row0 + (lay.stream_rows + 1) * Wp + lay.W + 2   # the image with its border row and tail
+        assert lay.stream_row0 == lay.n_strip_max * lay.img_t_rows and lay.stream_rows == S + lay.H - 1
+        if lay.n_strip < lay.n_strip_max:
+            assert zero_end <= lay.stream_row0                # a short group: the zeroed rows lie in front of the stream
+        else:
+            assert strips_end == lay.stream_row0              # else they ARE the stream's border row and the first of its rows
+        spare = 2 * Wp if lay.mode == "shared2" else 0        # the odd phase reads the stream from its second row on
+        assert 0 < strips_end <= lay.stream_row0 < stream_end and stream_end + spare == lay.cat_rows
+        d = S - lay.B                                         # the run's last group: its last window's last row
+        last_row = lay.stream_row0 + (d + lay.B - 1 + lay.H - 1) * Wp
+        assert lay.stream_row0 + d * Wp + (lay.B + lay.H - 1) * Wp <= stream_end - (lay.W + 2) and last_row + Wp <= lay.cat_rows
+        if lay.mode != "shared2":
+            continue
+        Wp2 = lay.W2 + 1
+        assert lay.n_strip2 <= lay.n_strip2_max == B_max + lay.shift2 and d % 2 == 0 and lay.h2s == (lay.stream_rows + 1) // 2
+        strips2_end = lay.n_strip2 * lay.img_t2
+        assert lay.stream2_base == lay.n_strip2_max * lay.img_t2 and lay.img_s2 == (lay.h2s + 1) * Wp2
+        if lay.n_strip2 < lay.n_strip2_max:
+            assert strips2_end + lay.W2 + 2 <= lay.stream2_base
+        else:
+            assert strips2_end == lay.stream2_base
+        assert lay.stream2_base + 2 * lay.img_s2 + lay.W2 + 2 == lay.rows2
+        # window i = 2 j + phase of the group reads rows d / 2 + j .. + H2 of its phase image: the last window of either phase
+        for phase in (0, 1):
+            if lay.B > phase:
+                j = (lay.B - 1 - phase) // 2
+                assert (d // 2 + j + lay.H2) * Wp2 <= lay.img_s2
+        # the odd-phase stream is the stride-2 block on the level-1 stream from its second row on: inside cat with the spare rows
+        assert lay.stream_row0 + Wp + (lay.stream_rows + 1) * Wp + lay.W + 2 <= lay.cat_rows
+    assert seen == {"per_window", "assembled", "direct", "shared2"}

@@ -1356,7 +1356,7 @@ def test_streaming_sliding_windows_equal_the_per_window_forward(prec, tol):
 
 
 def test_sharing_the_second_level_between_windows_changes_nothing():
-    """fp16 sliding windows with level 2 shared as well (two phase streams + 9-row strips, engine._eval_level2_shared) against
+    """fp16 sliding windows with level 2 shared as well (two phase streams + 9-row strips, engine._stream_level2) against
     level 1 only and against the per-window loop: every output element is summed by the same kernels in the same order, so
     the probabilities are IDENTICAL -- even and odd chunk sizes (the two phases hold different numbers of windows), chunks
     ending at the zero-padded end of the file, a window range starting at an odd frame."""
@@ -1378,10 +1378,63 @@ def test_sharing_the_second_level_between_windows_changes_nothing():
             assert float((two - ref).abs().max()) <= 2e-3, chunk
         part = eng.predict_windows(fg, chunk=77, start=333, stop=T, precision="fp16")
         assert torch.equal(part, two[333:])
-        assert "l2cat" in eng._plans[(77, 100, 44, "eval", torch.float16)]       # (the shared path did run)
+        assert eng._plans[(77, 100, 44, "eval", torch.float16)]["layout"].mode == "shared2"       # (the shared path did run)
     finally:
         eng.stream_level2 = True
     print(f"level-2 sharing vs per-window loop: max |dp| {float((two - ref).abs().max()):.2e}")
+
+
+def test_every_stream_mode_runs_and_equals_the_per_window_loop():
+    """predict_windows in every mode of engine.stream_layout, on both sides of the image-count thresholds of the fused strip blocks (256
+    level-1 strips: groups of 165 / 166 windows; 512 level-2 strips: 435 / 436), with the streams per run of groups and per group: the
+    layout kept in the window plan has the expected mode and tried launches, the probabilities are those of the per-window loop
+    (stream=False) within this file's bars, and identical between configurations that differ by a switch only."""
+    m, sd = build_model(43)
+    m.eval()
+    eng = m.engine
+    T = 700
+    g = torch.Generator().manual_seed(16)
+    fg = (torch.randn(T, 44, generator=g) * 2.0 - 8.0).cuda()
+    ref = {p: eng.predict_windows(fg, chunk=64, precision=p, stream=False).clone() for p in ("fp32", "fp16")}
+
+    def run(prec, chunk, **switches):
+        for k, v in switches.items():
+            setattr(eng, k, v)
+        try:
+            got = eng.predict_windows(fg, chunk=chunk, precision=prec).clone()
+        finally:
+            for k in switches:
+                setattr(eng, k, True)
+        err = float((got - ref[prec]).abs().max())
+        print(f"{prec} chunk {chunk} {switches}: max |dp| vs per-window loop {err:.2e}")
+        assert err <= (2e-3 if prec == "fp16" else 2e-6), (prec, chunk, switches, err)
+        return got, eng._plans[(chunk, 100, 44, "eval", torch.float16 if prec == "fp16" else torch.float32)].get("layout")
+
+    got, lay = run("fp32", 64)
+    assert lay.mode == "assembled" and lay.run is None and not (any(lay.strip_fused) or lay.strip_stem_rows or lay.tail_fused)
+    for chunk, fused in ((165, False), (166, True)):             # 255 / 256 strips
+        got, lay = run("fp16", chunk)
+        assert (lay.mode, lay.n_strip, lay.strip_fused, lay.strip_stem_rows) == ("shared2", chunk + 90, (fused, fused), fused)
+        assert lay.run == ((T, chunk) if chunk % 2 == 0 else None)       # (odd groups: no runs)
+        assert lay.strip2_fused == (False,) and lay.tail_fused and lay.strips2_resident and lay.stem_kept
+    for chunk, fused in ((435, False), (436, True)):             # 511 / 512 level-2 strips
+        per_group, lay1 = run("fp16", chunk, stream_super=False)
+        per_run, lay = run("fp16", chunk)
+        assert torch.equal(per_group, per_run), chunk
+        assert lay1.run is None and lay.run == ((T, chunk) if chunk % 2 == 0 else None)
+        for x in (lay1, lay):
+            assert (x.mode, x.n_strip2, x.strip2_fused, x.strip_fused, x.window_fused) == ("shared2", chunk + 76, (fused,), (True, True), (False,) * 8)
+    got2, lay = run("fp16", 2)
+    assert (lay.mode, lay.run, lay.n_strip, lay.n_strip2) == ("shared2", (T, 2), 92, 78) and not any(lay.strip_fused + lay.strip2_fused)
+    got1, lay = run("fp16", 1)
+    assert lay.mode == "per_window" and lay.run is None
+    shared, lay = run("fp16", 64)
+    assert lay.mode == "shared2" and lay.run == (T, 64)
+    direct, lay = run("fp16", 64, stream_level2=False)
+    assert lay.mode == "direct" and lay.run is None and lay.rides[2] and lay.cat_rows == 154 * 495 + 164 * 45 + 46
+    assembled, lay = run("fp16", 64, stream_direct=False)
+    assert lay.mode == "assembled" and lay.cat_rows is None and lay.stem_kept
+    assert torch.equal(shared, direct) and torch.equal(shared, assembled)
 
 
 def _f16_pnhwc(x):
@@ -1851,9 +1904,8 @@ def test_shared_levels_with_other_window_lengths(n_frames):
         for chunk in (64, 127):
             got = eng.predict_windows(fg, n_frames=n_frames, chunk=chunk, precision=prec)
             assert torch.equal(got, ref), (prec, chunk, float((got - ref).abs().max()))
-    # (the level-2 buffer of the shared path: per group in the plan, or per run of groups in the engine's run cache)
-    shared = "l2cat" in eng._plans[(64, n_frames, 44, "eval", torch.float16)] or any(k[1] == "l2" for k in eng._sup_cache)
-    assert shared == (n_frames % 2 == 0)
+    # (the layout the groups of 64 windows ran: level 2 shared where level 1 is even, else the stride-2 block reads the windows in place)
+    assert eng._plans[(64, n_frames, 44, "eval", torch.float16)]["layout"].mode == ("shared2" if n_frames % 2 == 0 else "direct")
 
 
 @pytest.mark.parametrize("T", [1, 2, 37, 99, 100, 101, 190])
