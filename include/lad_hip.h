@@ -670,6 +670,35 @@ int64_t lad_resample_lds_bytes(int32_t up, int32_t down, int32_t K);
 int lad_resample(const void *x, int32_t x_dtype, int64_t n_in, const float *table, int32_t up, int32_t down, int32_t K,
                  int64_t out_first, int64_t n_out, float *y, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Zero-phase low-pass of probability tracks on the device: one biquad run forwards and backwards, float64.
+ * Replaces lowpass (laugh_segmenter.py:49-55, called from :170 and :195) for tracks in GPU memory.
+ * Convention: scipy.signal.filtfilt(b, a, x) with its defaults for len(b) == len(a) == 3, a[0] == 1: odd extension by
+ * padlen = 9 frames at both ends (ext[e] = 2 x[0] - x[9 - e], ext[T + 9 + j] = 2 x[T-1] - x[T-2-j]); direct form II transposed
+ *   y = b0 x + z0;  z0 = b1 x + z1 - a1 y;  z1 = b2 x - a2 y
+ * forwards from zi * ext[0], then over the reversed forward result from zi * (its first element); the middle T frames.
+ * The serial recurrence is parallelised as a scan of the affine maps z -> A^m z + c, A = [[-a1, 1], [-a2, 0]]: a lane runs
+ * lad_lowpass_tile_frames() frames, a wave composes its 64 lanes, one launch carries the state from wave tile to wave tile.
+ * Six launches whatever channels and frames are, no workgroup waits for another, no atomics (identical bytes on every call).
+ * ---------------------------------------------------------------------------------------------- */
+/* frames of the extended track one lane runs serially; a wave tile is 64 of them (laugh_segmenter.py:49-55 has no such notion:
+ * the tests place their edge cases from it) */
+int32_t lad_lowpass_tile_frames(void);
+/* bytes of workspace for lad_lowpass (laugh_segmenter.py:49-55); needs no GPU.  -1 and lad_last_error() for channels outside
+ * 1..65535 or frames outside 10..2^30 (scipy refuses a track of padlen = 9 frames or fewer). */
+int64_t lad_lowpass_workspace_bytes(int64_t channels, int64_t frames);
+/* out[c][0 .. lengths[c]) = filtfilt of probs[c][0 .. lengths[c]) (laugh_segmenter.py:49-55), out[c][lengths[c] .. frames) = NaN.
+ * probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype; a float32 sample is widened exactly);
+ * frames is the row stride of probs and out.  lengths_host: HOST int64[channels], each 10..frames, or NULL for `frames`
+ * everywhere (it has been copied when the call returns).  b_host, a_host: HOST double[3]; zi_host: HOST double[2], the
+ * lfilter_zi(b, a) of the caller.  out: DEVICE float64 [channels][frames].  workspace: DEVICE, lad_lowpass_workspace_bytes.
+ * LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for sizes or a length out of range, a null
+ * pointer, an unknown dtype, a[0] != 1, a non-finite coefficient, or out overlapping probs or the workspace.  The input is
+ * never written; every store is guarded by the channel's length and the row stride. */
+int lad_lowpass(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const int64_t *lengths_host,
+                const double *b_host, const double *a_host, const double *zi_host, double *out, void *workspace,
+                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,11 @@ SIGNATURES = {
     "lad_resample_max_lds_bytes": (c_i64, []),
     "lad_resample_lds_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "lad_resample": (c_int, [c_void_p, c_i32, c_i64, c_void_p, c_i32, c_i32, c_i32, c_i64, c_i64, c_void_p, c_void_p]),
+    # zero-phase low-pass of the probability track (csrc/lowpass.hip)
+    "lad_lowpass_tile_frames": (c_i32, []),
+    "lad_lowpass_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "lad_lowpass": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64)] + [ctypes.POINTER(c_double)] * 3
+                    + [c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -17,6 +17,8 @@ count over its length (segment_laughter.py:103-104) unless --fps is given.
 Writes `eval_df_per_meeting.csv` (the 14 columns of analyse.py:255-257) and `sum_stats.csv` (config.py:38-39 of the reference).
 `--scorer device` (default `host`) uploads all tracks as one NaN-padded (C, T) tensor and scores the whole sweep on the GPU
 (csrc/runs.hip + csrc/score.hip through sweep_eval.score_sweep_device); both scorers write the same bytes.
+`--lowpass CUTOFF` (default: off) smooths every track first, as the reference's lowpass (laugh_segmenter.py:49-55) does before
+its thresholds: on the host with scipy, under the device scorer on the GPU (csrc/lowpass.hip) with each track's true length.
 """
 import argparse
 import csv
@@ -62,13 +64,23 @@ def load_tracks(probs_dir, index):
     return channels, tracks
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index):
+def cutoff_arg(text):
+    """--lowpass: a cutoff of Nyquist strictly between 0 and 1 (scipy.signal.butter's range)."""
+    value = float(text)
+    if not 0.0 < value < 1.0:
+        raise argparse.ArgumentTypeError(f"the cutoff must lie strictly between 0 and 1 (of Nyquist), got {text}")
+    return value
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
     for c, t in enumerate(tracks):
         padded[c, :len(t)] = t
-    return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index)
+    lengths = [len(t) for t in tracks] if lowpass is not None else None
+    return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
+                                         lowpass=lowpass, lengths=lengths)
 
 
 def write_csv(path, columns, rows):
@@ -90,6 +102,10 @@ def build_parser():
     parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
                         help='host: laugh_segmenter.get_laughter_instances + sweep_eval.score_instances per channel; '
                              'device: the sweep and its scores on the GPU (csrc/runs.hip, csrc/score.hip)')
+    parser.add_argument('--lowpass', type=cutoff_arg, default=None, metavar='CUTOFF',
+                        help='smooth every track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards and '
+                             'backwards (laugh_segmenter.lowpass under the host scorer, csrc/lowpass.hip under the device scorer; the '
+                             "reference's own cutoff is 0.01); default: off")
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
 
@@ -104,9 +120,16 @@ def main(argv=None):
     channels, tracks = load_tracks(args.probs_dir, index)
     length = {(c["meeting_id"], c["chan"]): c["length"] for c in chans}
     fps = [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
+    if args.lowpass is not None:
+        for (meeting, chan), t in zip(channels, tracks):
+            if len(t) <= 9:
+                raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
     if args.scorer == "device":
-        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index)
+        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass)
     else:
+        if args.lowpass is not None:
+            import laugh_segmenter
+            tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
         scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index)
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index)
     os.makedirs(args.out_dir, exist_ok=True)

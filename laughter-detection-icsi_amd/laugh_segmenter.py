@@ -37,6 +37,22 @@ def cut_laughter_segments(instance_list, y, sr):
     return new_audio
 
 
+def lowpass(sig, filter_order=2, cutoff=0.01):
+    """Second-order Butterworth low-pass at `cutoff` of Nyquist, forwards and backwards (laugh_segmenter.py:49-55).  The reference
+    overwrites `filter_order` with 2 inside the function, so any `filter_order` gives the second-order filter; so does this."""
+    from scipy import signal
+    filter_order = 2
+    b, a = signal.butter(filter_order, cutoff, output='ba')
+    return signal.filtfilt(b, a, sig)
+
+
+def lowpass_device(probs, cutoff=0.01, lengths=None):
+    """`lowpass` for a (T,) or (C, T) track in GPU memory (csrc/lowpass.hip through lowpass.py): a float64 tensor of the same shape
+    that stays on the device, e.g. for get_laughter_instances_device.  No CPU fallback."""
+    import lowpass as lowpass_mod
+    return lowpass_mod.lowpass_device(probs, cutoff=cutoff, lengths=lengths)
+
+
 def fix_over_underflow(prob):
     """p > 1 -> 1; p <= 0 -> 1e-7 (so that threshold 0 still accepts the frame); else p."""
     if prob > 1:

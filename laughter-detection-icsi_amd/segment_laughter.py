@@ -20,6 +20,10 @@ probabilities are all-gathered.
 `--segmenter device` (default `host`) keeps the gathered track on the GPU and cuts it there (csrc/runs.hip through
 `laugh_segmenter.get_laughter_instances_device`: the run tables of every threshold in four launches); only the compact tables
 cross to the host, and the track itself only when `--save_probs` asks for it.  Same TextGrids and wav files, byte for byte.
+
+`--lowpass CUTOFF` (default: off) smooths the track before the sweep with the reference's `lowpass` (laugh_segmenter.py:49-55,
+which segment_laughter.py:107-108 leaves commented out): scipy on the host under `--segmenter host`, csrc/lowpass.hip under
+`--segmenter device`, where the track still never leaves the GPU.  `--save_probs` keeps writing the raw track.
 """
 import argparse
 import os
@@ -104,11 +108,12 @@ def save_audio_instances(instances, audio_path, output_dir, rate=None):
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
-                  save_audio_rate=None):
+                  save_audio_rate=None, lowpass=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
-    (None: the file's own)."""
+    (None: the file's own).  lowpass: a cutoff (of Nyquist): the track is smoothed before the sweep (segment_laughter.py:107-108), on
+    the host or on the device like the sweep itself; save_probs still gets the raw track."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if save_to_audio_files and output_dir is None:
@@ -123,6 +128,9 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
         # (not in the reference: the per-frame track, e.g. to compare a sharded run with a single-rank one)
         np.save(save_probs, probs.cpu().numpy() if segmenter == "device" else probs)
     fps = len(probs) / float(file_length)
+    if lowpass is not None and (segmenter == "host" or rank == 0):
+        probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
+            laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
     if segmenter == "host":
         instance_dict = laugh_segmenter.get_laughter_instances(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
     elif rank == 0:
@@ -152,6 +160,14 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     return time_taken, instance_dict
 
 
+def cutoff_arg(text):
+    """--lowpass: a cutoff of Nyquist strictly between 0 and 1 (scipy.signal.butter's range)."""
+    value = float(text)
+    if not 0.0 < value < 1.0:
+        raise argparse.ArgumentTypeError(f"the cutoff must lie strictly between 0 and 1 (of Nyquist), got {text}")
+    return value
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--model_path', type=str, default='checkpoints/in_use/resnet_with_augmentation')
@@ -171,6 +187,10 @@ def build_parser():
     parser.add_argument('--segmenter', type=str, default='host', choices=['host', 'device'],
                         help="(not in the reference) where the probability track is cut into instances: 'host' copies it to the host "
                              "(numpy, one pass per threshold); 'device' cuts it on the GPU, all thresholds in one pass -- same output")
+    parser.add_argument('--lowpass', type=cutoff_arg, default=None, metavar='CUTOFF',
+                        help="smooth the probability track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards "
+                             "and backwards (the reference's lowpass, cutoff 0.01, which it leaves commented out); on the host or the "
+                             "GPU as --segmenter says; default: off")
     parser.add_argument('--resample', type=str, default='False',
                         help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
                              "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
@@ -199,7 +219,8 @@ def main(argv=None):
     load_and_pred(model, args.input_audio_file, thresholds, min_lengths, args.output_dir,
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
-                  segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate)
+                  segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
+                  lowpass=args.lowpass)
 
 
 if __name__ == '__main__':

@@ -278,11 +278,13 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index):
     return out
 
 
-def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index):
+def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
     TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
-    the run tables never leave the device."""
+    the run tables never leave the device.
+    lowpass: a cutoff (of Nyquist): every track is smoothed on the device first (laugh_segmenter.lowpass_device: lad_lowpass before
+    lad_runs_count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN)."""
     import torch
 
     import _hip
@@ -302,6 +304,11 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index):
     out_shape = (C, K, L, len(FIELDS))
     if C == 0 or T == 0 or K == 0 or L == 0:
         return np.zeros(out_shape, np.int64)
+    if lowpass is not None:
+        import laugh_segmenter as ls
+        probs = ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths)
+    elif lengths is not None:
+        raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
     dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
     if dix.channels != channels or dix.device != probs.device:
