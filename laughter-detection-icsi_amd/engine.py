@@ -11,7 +11,9 @@ Memory plan.  Parameters live in ONE flat fp32 buffer in `
 (each tensor 16-byte aligned), gradients in a second flat buffer of the same shape -> one all-reduce, one
 norm, one Adam launch.  Activations are "PNHWC" with shared zero borders (csrc/lad_device.h): [batch][H+1][W+1][C] plus
 a short tail; a plan for batch size B owns every activation / gradient buffer and is reused step after
-step (no allocation inside the step).
+step (no allocation inside the step).  Everything derived from the weights -- packed MFMA images, fp16 images, eval-mode
+BatchNorm folds -- belongs to the model (_ConvParams / _BnParams, one record per layer); the layer table of an input geometry
+(_blocks_for) holds sizes and points at those records.
 """
 import ctypes
 import math
@@ -53,39 +55,86 @@ def _align4(n):
     return (n + 3) & ~3
 
 
-class _ConvSpec:
-    """One convolution: geometry + where its weights live in the flat buffers."""
+def _b3_shape(cin, cout, taps, stride):
+    """A layer shape the split-operand (bf16 x 3, f16 x 2) stride-1 kernels have instances for."""
+    return cin == cout and cin in (64, 32) and taps == 9 and stride == 1
 
-    def __init__(self, name, cin, cout, taps, stride, h_in, w_in, has_bias, base_widths=True):
+
+def _s2b3_shape(cin, cout, taps, stride):
+    """The 64 -> 32 stride-2 transition, which has a split-operand kernel of its own (with its 1x1 shortcut)."""
+    return cin == 64 and cout == 32 and taps == 9 and stride == 2
+
+
+class _ConvParams:
+    """One convolution of the MODEL: its views into the flat parameter / gradient buffers and every packed image of its weights.
+    Which images exist follows from the layer's shape alone, so the layer's _ConvSpec of every geometry points here (cs.par);
+    ResNetEngine._pack_weights / _eval_prepare keep the images current."""
+
+    def __init__(self, name, cin, cout, taps, stride, base_widths, views, lib, dev):
+        self.name, self.cin, self.cout, self.taps = name, cin, cout, taps
+        self.w, self.gw = views[name + ".weight"]
+        self.b, self.gb = views.get(name + ".bias", (None, None))   # (a 1x1 shortcut has none)
+        self.shortcut = None   # conv1 of a block with a projection shortcut: that convolution's record (the s2b3 images hold both)
+
+        def image(n, dtype):
+            return torch.zeros(int(n), device=dev, dtype=dtype)
+
+        # exact-f32 MFMA images, forward / data gradient, and the fp16 image of the half-precision inference kernels
+        self.wt_f = image(lib.lad_conv_packed_weight_floats(cout, cin, taps, 0), torch.float32)
+        self.wt_d = image(lib.lad_conv_packed_weight_floats(cout, cin, taps, 1), torch.float32)
+        self.wt_h = image(lib.lad_f16_packed_weight_halfs(cout, cin, taps), torch.float16)
+        if _b3_shape(cin, cout, taps, stride) and base_widths:
+            # split (bf16 x 3) images, forward and data gradient, and the f16 x 2 images (csrc/conv_h2.hip)
+            self.wt3_f, self.wt3_d = (image(lib.lad_conv_b3c_packed_weight_bytes(cin), torch.uint8) for _ in range(2))
+            self.wt2_f, self.wt2_d = (image(lib.lad_conv_h2_packed_weight_bytes(cin), torch.uint8) for _ in range(2))
+        if _s2b3_shape(cin, cout, taps, stride) and base_widths:
+            # ... with its shortcut: one split image per direction (3x3 + 1x1 together)
+            self.wt3_s2f = image(lib.lad_conv_s2b3_packed_weight_bytes(), torch.uint8)
+            self.wt3_s2d = image(lib.lad_conv_s2b3_dgrad_packed_weight_bytes(), torch.uint8)
+
+
+class _BnParams:
+    """One BatchNorm of the MODEL: affine parameters and their gradients (views into the flat buffers), the running statistics,
+    and the eval-mode fold (scale, shift) that ResNetEngine._eval_prepare keeps current (conv_bias: the bias of the convolution in
+    front, which the fold's shift absorbs; the head's two BatchNorm1d are applied by the head kernels and leave theirs unused)."""
+
+    def __init__(self, name, c, views, bufs, dev, conv_bias=None):
+        self.name, self.c, self.conv_bias = name, c, conv_bias
+        self.g, self.gg = views[name + ".weight"]
+        self.b, self.gb = views[name + ".bias"]
+        self.rm, self.rv = bufs[name + ".running_mean"], bufs[name + ".running_var"]
+        if not (self.rm.is_cuda and self.rm.is_contiguous() and self.rm.dtype == torch.float32):
+            raise _hip.LadHipError(f"{name}: running statistics must be contiguous float32 GPU tensors")
+        self.fold = (torch.zeros(c, device=dev), torch.zeros(c, device=dev))
+
+
+class _ConvSpec:
+    """One convolution on one input geometry: sizes and which kernels have an instance for them.  par: the layer's _ConvParams
+    (None in the tensor-free tables of block_geometry)."""
+
+    def __init__(self, name, cin, cout, taps, stride, h_in, w_in, base_widths=True):
         self.name, self.cin, self.cout, self.taps, self.stride = name, cin, cout, taps, stride
         self.h_in, self.w_in = h_in, w_in
         self.h_out = (h_in + stride - 1) // stride
         self.w_out = (w_in + stride - 1) // stride
-        self.has_bias = has_bias
         # what the split-operand kernels have instances for, at the stage widths they were validated on (shape only: whether a step
         # uses them is train_schedule's decision).  b3: forward and data gradient (64 or 32 channels); b3_full: 64 channels, where
         # the sign bits exist as well
-        self.b3 = cin == cout and cin in (64, 32) and taps == 9 and stride == 1 and w_in <= 46 and base_widths
+        self.b3 = _b3_shape(cin, cout, taps, stride) and w_in <= 46 and base_widths
         self.b3_full = self.b3 and cin == 64
         self.b3_wgrad = self.b3 and (cin == 64 or w_in <= 30)   # the 32-channel weight-gradient window holds 64 rows + 2 (W + 2)
         # the 64 -> 32 stride-2 transition with its shortcut: one split image per direction (3x3 + 1x1 together)
-        self.s2b3 = cin == 64 and cout == 32 and taps == 9 and stride == 2 and (w_in + 1) // 2 <= 45 and base_widths
-        self.w = self.b = self.gw = self.gb = None  # views into the flat param / grad buffers
-        self.wt_f = self.wt_d = None                # packed images (forward / data-gradient)
+        self.s2b3 = _s2b3_shape(cin, cout, taps, stride) and (w_in + 1) // 2 <= 45 and base_widths
+        self.par = None
 
     def rows(self, B):
         """Rows of the layer's input tensor for batch B (shared zero borders + tail)."""
         return B * (self.h_in + 1) * (self.w_in + 1) + self.w_in + 2
 
 
-class _BnSpec:
-    def __init__(self, name, c):
-        self.name, self.c = name, c
-        self.g = self.b = self.rm = self.rv = self.gg = self.gb = None
-        self.coef = None  # float[6][C] scale, shift, mean, invstd, mean_lo, invstd_lo of the last forward
-
-
 class _BlockSpec:
+    """conv1 / conv2 / sc_conv: _ConvSpec of this geometry; bn1 / bn2 / sc_bn: the model's _BnParams."""
+
     def __init__(self, name):
         self.name = name
         self.conv1 = self.bn1 = self.conv2 = self.bn2 = self.sc_conv = self.sc_bn = None
@@ -100,11 +149,11 @@ def block_geometry(stem_cout, filter_sizes, H, W, base_widths):
             name = f"block{bi}.{j}"
             stride = 2 if (j == 0 and bi > 1) else 1
             b = _BlockSpec(name)
-            b.conv1 = _ConvSpec(name + ".conv1", cin, cout, 9, stride, h, w, True, base_widths)
+            b.conv1 = _ConvSpec(name + ".conv1", cin, cout, 9, stride, h, w, base_widths)
             h, w = b.conv1.h_out, b.conv1.w_out
-            b.conv2 = _ConvSpec(name + ".conv2", cout, cout, 9, 1, h, w, True, base_widths)
+            b.conv2 = _ConvSpec(name + ".conv2", cout, cout, 9, 1, h, w, base_widths)
             if stride != 1 or cin != cout:
-                b.sc_conv = _ConvSpec(name + ".shortcut.0", cin, cout, 1, stride, b.conv1.h_in, b.conv1.w_in, False, base_widths)
+                b.sc_conv = _ConvSpec(name + ".shortcut.0", cin, cout, 1, stride, b.conv1.h_in, b.conv1.w_in, base_widths)
             blocks.append(b)
             cin = cout
     return blocks
@@ -421,8 +470,6 @@ class ResNetEngine:
         self._lib = None
         self._grad_dirty = False  # flat grad buffer holds a gradient that must be accumulated into
         self._train_forwards = 0
-        self._fold_tag = {}    # {id(layer table): state tag of its BatchNorm folds}: the sliding-window path alternates between geometries
-        self._f16_tags = {}    # ... of its half-precision weight images
         self._weights_version = 0
         # data-gradient epilogues can carry the first pass of the BatchNorm backward that follows (lad_conv_fwd_bnstat).
         # Measured at bs 512: -1.0 ms of reduce passes, +0.3 ms in the four fused conv launches, +0.3 ms in the finalize
@@ -477,7 +524,6 @@ class ResNetEngine:
         self.strip2_resident = True
         # ... and the strips have no stem launch: their inner rows ARE the stream's, the two edge rows are computed in the first block's launch
         self.strip_stem_shared = True
-        self._tail_param_cache = {}
         self._sup_cache = {}
         self._sup_plans = {}                 # {"l1" / "l2": keys of the run-long eval plans, released with the run's buffer}
         self._layouts = {}                   # {(B, H, W, half, switch values, run): _StreamLayout}
@@ -567,8 +613,6 @@ class ResNetEngine:
                 m._buffers["num_batches_tracked"] = self._nbt[i]
         self._build_specs()
         self._weights_version += 1
-        self._packed_version = {}
-        self._pack_tables = {}
         self._param_list = [p for _, p in params]
 
     def bump_num_batches_tracked(self):
@@ -587,43 +631,34 @@ class ResNetEngine:
 
     # ------------------------------------------------------------------------------------ layer table
     def _build_specs(self):
+        """The model's own records: one _ConvParams per convolution of the residual blocks and one _BnParams per BatchNorm, with
+        every buffer derived from the weights (packed images, eval folds).  Built with the flat buffers and living as long as they
+        do; the layer tables of the geometries (_blocks_for) only point here."""
         m = self.model
         bufs = dict(m.named_buffers())
+        lib, dev = self.lib(), self.device
 
-        def conv(s):
-            """Attach a convolution's parameter views and allocate its packed weight images."""
-            s.w, s.gw = self._views[s.name + ".weight"]
-            if s.has_bias:
-                s.b, s.gb = self._views[s.name + ".bias"]
-            dev = self.device
-            s.wt_f = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(s.cout, s.cin, s.taps, 0)), device=dev)
-            s.wt_d = torch.zeros(int(self.lib().lad_conv_packed_weight_floats(s.cout, s.cin, s.taps, 1)), device=dev)
-            if s.b3:  # split (bf16 x 3) weight images, forward and data gradient
-                nb = int(self.lib().lad_conv_b3c_packed_weight_bytes(s.cin))
-                s.wt3_f = torch.zeros(nb, device=dev, dtype=torch.uint8)
-                s.wt3_d = torch.zeros(nb, device=dev, dtype=torch.uint8)
-                nb2 = int(self.lib().lad_conv_h2_packed_weight_bytes(s.cin))   # ... and the f16 x 2 images (csrc/conv_h2.hip)
-                s.wt2_f = torch.zeros(nb2, device=dev, dtype=torch.uint8)
-                s.wt2_d = torch.zeros(nb2, device=dev, dtype=torch.uint8)
-            if s.s2b3:
-                s.wt3_s2f = torch.zeros(int(self.lib().lad_conv_s2b3_packed_weight_bytes()), device=dev, dtype=torch.uint8)
-                s.wt3_s2d = torch.zeros(int(self.lib().lad_conv_s2b3_dgrad_packed_weight_bytes()), device=dev, dtype=torch.uint8)
-            return s
-
-        def bn(name, c):
-            s = _BnSpec(name, c)
-            s.g, s.gg = self._views[name + ".weight"]
-            s.b, s.gb = self._views[name + ".bias"]
-            s.rm, s.rv = bufs[name + ".running_mean"], bufs[name + ".running_var"]
-            if not (s.rm.is_cuda and s.rm.is_contiguous() and s.rm.dtype == torch.float32):
-                raise _hip.LadHipError(f"{name}: running statistics must be contiguous float32 GPU tensors")
-            return s
+        def bn(name, c, conv_bias=None):
+            return _BnParams(name, c, self._views, bufs, dev, conv_bias)
 
         self.stem_w, self.stem_gw = self._views["conv1.weight"]
         self.stem_cout = self.stem_w.shape[0]
         self.stem_bn = bn("bn1", self.stem_cout)
-        self._conv_factory, self._bn_factory = conv, bn
+        self._convs, self._bns = {}, {}   # {layer name: record}, in the order of the model's layers
+        for b in block_geometry(self.stem_cout, m.filter_sizes, 1, 1, self.base_widths):   # (names and channel counts only)
+            for cs, bn_name in ((b.conv1, ".bn1"), (b.conv2, ".bn2"), (b.sc_conv, ".shortcut.1")):
+                if cs is not None:
+                    par = self._convs[cs.name] = _ConvParams(cs.name, cs.cin, cs.cout, cs.taps, cs.stride, self.base_widths, self._views, lib, dev)
+                    self._bns[b.name + bn_name] = bn(b.name + bn_name, cs.cout, par.b)
+            if b.sc_conv is not None:
+                self._convs[b.conv1.name].shortcut = self._convs[b.sc_conv.name]
         self._geom_specs = {}
+        # freshness of everything derived from the weights (_pack_weights, _eval_prepare)
+        self._packed = None       # (weights stamp, data-gradient images too, split images) of the last pack of the MFMA images
+        self._folded = None       # state tag of the BatchNorm folds
+        self._f16_packed = None   # ... of the half-precision images
+        self._pack_tables = {}    # device tables of the multi-layer pack launches: {data-gradient images too | ("h2", layer names)}
+        self._tail_ptrs = None
         self.head_bn2 = bn("bn2", m.linear_layer_size)
         self.head_bn3 = bn("bn3", 32)
         names = ["bn2.weight", "bn2.bias", None, None, "linear1.weight", "linear1.bias", "bn3.weight", "bn3.bias",
@@ -641,7 +676,8 @@ class ResNetEngine:
         self._head_grads = (_VP * 8)(*[self._views[n][1].data_ptr() for n in gnames])
 
     def _blocks_for(self, H, W, partial=False):
-        """Layer specs for an (H, W) input (geometry-dependent: packed weights are shared, sizes are not).
+        """Layer specs for an (H, W) input: sizes and kernel eligibility are the geometry's, the parameters, packed weights and
+        folds are the model's records (_build_specs), shared by every geometry.
         partial: only the leading full-resolution layers will run on this geometry (the stream / strip images of the
         sliding-window path): the pooling and classifier-size checks of a whole forward do not apply."""
         key = (H, W, partial)
@@ -649,13 +685,10 @@ class ResNetEngine:
             return self._geom_specs[key]
         blocks = block_geometry(self.stem_cout, self.model.filter_sizes, H, W, self.base_widths)
         for b in blocks:
-            self._conv_factory(b.conv1)
-            b.bn1 = self._bn_factory(b.name + ".bn1", b.conv1.cout)
-            self._conv_factory(b.conv2)
-            b.bn2 = self._bn_factory(b.name + ".bn2", b.conv1.cout)
+            b.bn1, b.bn2 = self._bns[b.name + ".bn1"], self._bns[b.name + ".bn2"]
+            b.conv1.par, b.conv2.par = self._convs[b.conv1.name], self._convs[b.conv2.name]
             if b.sc_conv is not None:
-                self._conv_factory(b.sc_conv)
-                b.sc_bn = self._bn_factory(b.name + ".shortcut.1", b.conv1.cout)
+                b.sc_conv.par, b.sc_bn = self._convs[b.sc_conv.name], self._bns[b.name + ".shortcut.1"]
         h, w = blocks[-1].conv2.h_out, blocks[-1].conv2.w_out
         if partial:
             self._geom_specs[key] = (blocks, h, w, 0)
@@ -768,51 +801,74 @@ class ResNetEngine:
         `param.data`, a broadcast): every cached derivative (packed MFMA images, BatchNorm folds, fp16 packs) is stale."""
         self._weights_version += 1
 
-    def _pack_weights(self, blocks, need_dgrad, sched=None):
-        """Refresh the packed MFMA weight images the pass about to run reads, if the parameters changed since they were packed: the
-        exact-f32 images (forward only for eval-mode callers) and the split-operand images of a training step's schedule."""
+    def _weights_stamp(self):
         # a Parameter's _version moves when torch writes it in place (optimizer.step, load_state_dict, init; after
         # `p.data = view` the Parameter keeps its OWN counter, the flat buffer's does not move);
         # _weights_version moves when our own Adam kernel writes the flat buffer
-        ver = (self._weights_version, sum(p._version for p in self._param_list))
+        return (self._weights_version, sum(p._version for p in self._param_list))
+
+    def _state_tag(self):
+        bufs = sum(b._version for b in self.model.buffers())
+        return self._weights_stamp() + (bufs, self._train_forwards)
+
+    def _pack_weights(self, need_dgrad, sched=None):
+        """Refresh the packed MFMA weight images the pass about to run reads, if the parameters changed since they were packed: the
+        exact-f32 images (forward only for eval-mode callers) and the split-operand images of a training step's schedule."""
+        ver = self._weights_stamp()
         want = sched.images if sched is not None else frozenset()
-        have = self._packed_version.get(id(blocks))   # (parameter version, data-gradient images too, split images) of the last pack
+        have = self._packed
         fresh = have is not None and have[0] == ver
         if fresh and have[1] >= need_dgrad and want <= have[2]:
             return
         lib, st = self.lib(), self._st()
         if not (fresh and have[1] >= need_dgrad):
-            key = (id(blocks), need_dgrad)
-            table = self._pack_tables.get(key)
+            table = self._pack_tables.get(need_dgrad)
             if table is None:  # device table of {w, wt, cout, cin, taps, mode} records: pointers never move
-                recs = [struct.pack("<QQiiii", cs.w.data_ptr(), (cs.wt_f if mode == 0 else cs.wt_d).data_ptr(), cs.cout, cs.cin, cs.taps, mode)
-                        for blk in blocks for cs in (blk.conv1, blk.conv2, blk.sc_conv) if cs is not None
-                        for mode in ((0, 1) if need_dgrad else (0,))]
-                table = self._pack_tables[key] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
+                recs = [struct.pack("<QQiiii", par.w.data_ptr(), (par.wt_f if mode == 0 else par.wt_d).data_ptr(), par.cout, par.cin, par.taps, mode)
+                        for par in self._convs.values() for mode in ((0, 1) if need_dgrad else (0,))]
+                table = self._pack_tables[need_dgrad] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
             _hip.check(lib.lad_conv_pack_weights_multi(_hip.ptr(table[0]), table[1], st), "lad_conv_pack_weights_multi")
-        shortcut = {blk.conv1.name: blk.sc_conv for blk in blocks}
-        convs = {cs.name: cs for blk in blocks for cs in (blk.conv1, blk.conv2)}
         h2 = []
         for kind, name in sorted(want - have[2] if fresh else want):   # (a training step: both directions of every image)
-            cs = convs[name]
+            par = self._convs[name]
             if kind == "s2b3":   # both images in one launch
-                _hip.check(lib.lad_conv_s2b3_pack_weights_pair(_hip.ptr(cs.w), _hip.ptr(shortcut[name].w), _hip.ptr(cs.wt3_s2f),
-                                                               _hip.ptr(cs.wt3_s2d), st), "lad_conv_s2b3_pack_weights_pair")
+                _hip.check(lib.lad_conv_s2b3_pack_weights_pair(_hip.ptr(par.w), _hip.ptr(par.shortcut.w), _hip.ptr(par.wt3_s2f),
+                                                               _hip.ptr(par.wt3_s2d), st), "lad_conv_s2b3_pack_weights_pair")
             elif kind == "b3c":
-                for mode, wt in ((0, cs.wt3_f), (1, cs.wt3_d)):
-                    _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(cs.w), mode, _hip.ptr(wt), cs.cin, st), "lad_conv_b3c_pack_weights")
+                for mode, wt in ((0, par.wt3_f), (1, par.wt3_d)):
+                    _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(par.w), mode, _hip.ptr(wt), par.cin, st), "lad_conv_b3c_pack_weights")
             else:
-                h2.append(cs)
+                h2.append(par)
         if h2:
             # the f16 x 2 images: ONE launch packs every layer and direction of both channel counts (a record names its own; 16 workgroups
             # per image).  The table is cached under the layers it lists: which ones run on f16 x 2 depends on the flags
-            hkey = (id(blocks), "h2", tuple(cs.name for cs in h2))
+            hkey = ("h2",) + tuple(par.name for par in h2)
             htab = self._pack_tables.get(hkey)
             if htab is None:
-                recs = [struct.pack("<QQii", cs.w.data_ptr(), wt.data_ptr(), mode, cs.cin) for cs in h2 for mode, wt in ((0, cs.wt2_f), (1, cs.wt2_d))]
+                recs = [struct.pack("<QQii", par.w.data_ptr(), wt.data_ptr(), mode, par.cin) for par in h2
+                        for mode, wt in ((0, par.wt2_f), (1, par.wt2_d))]
                 htab = self._pack_tables[hkey] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
             _hip.check(lib.lad_conv_h2_pack_weights_multi(_hip.ptr(htab[0]), htab[1], 0, st), "lad_conv_h2_pack_weights_multi")
-        self._packed_version[id(blocks)] = (ver, need_dgrad or have[1], want | have[2]) if fresh else (ver, need_dgrad, want)
+        self._packed = (ver, need_dgrad or have[1], want | have[2]) if fresh else (ver, need_dgrad, want)
+
+    def _eval_prepare(self, half):
+        """What an eval-mode pass reads of the model, refreshed if parameters or running statistics changed since: the exact-f32
+        forward images (fp32), the per-channel (scale, shift) of every BatchNorm that follows a convolution, folded from the
+        running statistics (eval mode of models.py:110-115,224), and the half-precision images, refreshed with the folds (fp16)."""
+        if not half:
+            self._pack_weights(need_dgrad=False)
+        tag = self._state_tag()
+        lib, st = self.lib(), self._st()
+        if self._folded != tag:
+            for bn in (self.stem_bn, *self._bns.values()):
+                _hip.check(lib.lad_bn_fold(_hip.ptr(bn.g), _hip.ptr(bn.b), _hip.ptr(bn.rm), _hip.ptr(bn.rv), _hip.ptr(bn.conv_bias),
+                                           bn.c, _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]), st), "lad_bn_fold " + bn.name)
+            self._folded = tag
+        if half and self._f16_packed != tag:
+            for par in self._convs.values():
+                _hip.check(lib.lad_f16_pack_weights(_hip.ptr(par.w), par.cout, par.cin, par.taps, _hip.ptr(par.wt_h), st),
+                           "lad_f16_pack_weights " + par.name)
+            self._f16_packed = tag
 
     def _mark(self, label):
         """HIP event on the launch stream (torch's current stream) when bench.py asked for per-kernel timing."""
@@ -847,7 +903,7 @@ class ResNetEngine:
         fn = conv_s1_entry(arith, cs.cin, in_coef is not None, abits is not None,
                            None if bn is None else "x" if bmask is None else "bits" if bmask.dtype == torch.int64 else "y")
         P, fwd, h, w = _hip.ptr, direction == "fwd", cs.h_in, cs.w_in
-        wt = P(getattr(cs, {"h2": "wt2_", "b3": "wt3_", "f32": "wt_"}[arith] + ("f" if fwd else "d")))
+        wt = P(getattr(cs.par, {"h2": "wt2_", "b3": "wt3_", "f32": "wt_"}[arith] + ("f" if fwd else "d")))
         cio = (cs.cin, cs.cout) if fwd else (cs.cout, cs.cin)
         if fn == "lad_conv_h2":
             args = (P(x), P(in_coef), wt, P(bias), P(addend), P(abits), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w, cs.cin)
@@ -872,10 +928,10 @@ class ResNetEngine:
     def _conv_fwd(self, cs, ch, x, out, partials, B, in_coef=None):
         """Forward convolution with bias; `partials` receives the per-tile sums of the BatchNorm that follows."""
         if cs.stride == 1:
-            self._conv_s1(cs, ch.arith, "fwd", x, out, B, ch.label_fwd, in_coef=in_coef, bias=cs.b, partials=partials)
+            self._conv_s1(cs, ch.arith, "fwd", x, out, B, ch.label_fwd, in_coef=in_coef, bias=cs.par.b, partials=partials)
             return
         t0 = self._mark(ch.label_fwd)
-        _hip.check(self.lib().lad_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(cs.b), _hip.ptr(out), _hip.ptr(partials),
+        _hip.check(self.lib().lad_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(cs.par.b), _hip.ptr(out), _hip.ptr(partials),
                                               B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, self._st()), "lad_conv_s2_fwd " + cs.name)
         self._mark_end(ch.label_fwd, t0)
 
@@ -885,7 +941,6 @@ class ResNetEngine:
         _hip.check(lib.lad_bn_finalize(_hip.ptr(partials), n_tiles, bn.c, B * h * w, _hip.ptr(bn.g), _hip.ptr(bn.b),
                                        _hip.ptr(bn.rm), _hip.ptr(bn.rv), 0.1, _hip.ptr(coef), st),
                    "lad_bn_finalize " + bn.name)
-        bn.coef = coef
 
     def _bn_coef_pair(self, bn_a, coef_a, part_a, bn_b, coef_b, part_b, B, h, w):
         """_bn_coef for a stride-2 block's bn1 and its shortcut BatchNorm (sums of one shape, left by one launch) in one launch."""
@@ -895,8 +950,6 @@ class ResNetEngine:
                                             _hip.ptr(bn_a.g), _hip.ptr(bn_a.b), _hip.ptr(bn_a.rm), _hip.ptr(bn_a.rv), _hip.ptr(coef_a),
                                             _hip.ptr(bn_b.g), _hip.ptr(bn_b.b), _hip.ptr(bn_b.rm), _hip.ptr(bn_b.rv), _hip.ptr(coef_b),
                                             0.1, st), "lad_bn_finalize_pair " + bn_a.name)
-        bn_a.coef = coef_a
-        bn_b.coef = coef_b
 
     def _bn_act(self, x, coef, res, rcoef, y, B, h, w, c, relu=1):
         _hip.check(self.lib().lad_bn_act(_hip.ptr(x), _hip.ptr(coef), _hip.ptr(res), _hip.ptr(rcoef), _hip.ptr(y), B, h, w, c,
@@ -934,7 +987,7 @@ class ResNetEngine:
         # the kernel choices of this pass and of its backward, which reads them from the plan (virtual activations that were never
         # written, sign bits that exist or not, packed weight images), whatever happens to the flags in between
         sched = p["schedule"] = self._schedule(B, H, W)
-        self._pack_weights(blocks, need_dgrad=True, sched=sched)
+        self._pack_weights(need_dgrad=True, sched=sched)
         part = p["partials"]
         # stem (models.py:224)
         # The stem convolution (K = 9) is cheaper to recompute than to store: a statistics-only pass, then conv + BatchNorm +
@@ -947,7 +1000,6 @@ class ResNetEngine:
             _hip.check(lib.lad_stem_bn_stats(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(bn.g), _hip.ptr(bn.b), _hip.ptr(bn.rm), _hip.ptr(bn.rv),
                                              0.1, _hip.ptr(p["stem_coef"]), _hip.ptr(p["stem_mom"]), _hip.ptr(p["stem_mom_ws"]), B, H, W,
                                              self.stem_cout, st), "lad_stem_bn_stats")
-            bn.coef = p["stem_coef"]
         else:
             _hip.check(lib.lad_stem_fwd(_hip.ptr(x), _hip.ptr(self.stem_w), None, _hip.ptr(part), B, H, W, self.stem_cout, st),
                        "lad_stem_fwd")
@@ -965,11 +1017,11 @@ class ResNetEngine:
             else:
                 t0 = self._mark(ch.conv1.label_fwd)
                 if ch.entry == "s2b3":   # conv1 and the 1x1 shortcut on the split-operand path (csrc/conv_b3.hip, conv_s2b3_kernel)
-                    _hip.check(lib.lad_conv_s2b3_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.wt3_s2f), _hip.ptr(b.conv1.b), _hip.ptr(a["c1"]), _hip.ptr(part),
+                    _hip.check(lib.lad_conv_s2b3_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.par.wt3_s2f), _hip.ptr(b.conv1.par.b), _hip.ptr(a["c1"]), _hip.ptr(part),
                                                      _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]), B, b.conv1.h_in, b.conv1.w_in, st),
                                "lad_conv_s2b3_fwd " + b.conv1.name)
                 else:   # ... in one launch of the exact-f32 kernel (csrc/conv_mfma.hip, conv_s2_kernel<SC>)
-                    _hip.check(lib.lad_conv_s2_fwd_fused(_hip.ptr(cur), _hip.ptr(b.conv1.wt_f), _hip.ptr(b.conv1.b), _hip.ptr(b.sc_conv.wt_f),
+                    _hip.check(lib.lad_conv_s2_fwd_fused(_hip.ptr(cur), _hip.ptr(b.conv1.par.wt_f), _hip.ptr(b.conv1.par.b), _hip.ptr(b.sc_conv.par.wt_f),
                                                          _hip.ptr(a["c1"]), _hip.ptr(part), _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]),
                                                          B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, b.conv1.cout, st),
                                "lad_conv_s2_fwd_fused " + b.conv1.name)
@@ -1036,51 +1088,6 @@ class ResNetEngine:
         return p["probs"]
 
     # ------------------------------------------------------------------------------------ eval (inference) path
-    def _state_tag(self):
-        bufs = sum(b._version for b in self.model.buffers())
-        return (self._weights_version, sum(p._version for p in self._param_list), bufs, self._train_forwards)
-
-    def _fold_eval(self, blocks):
-        """Per-channel (scale, shift) of every BatchNorm that follows a convolution, from the running statistics
-        (eval mode of models.py:110-115,224), refreshed only when parameters or statistics changed."""
-        tags = self._fold_tag
-        tag = self._state_tag()
-        if tags.get(id(blocks)) == tag:
-            return
-        lib, st, dev = self.lib(), self._st(), self.device
-
-        def fold(bn, conv_bias):
-            if getattr(bn, "fold", None) is None:
-                bn.fold = (torch.zeros(bn.c, device=dev), torch.zeros(bn.c, device=dev))
-            _hip.check(lib.lad_bn_fold(_hip.ptr(bn.g), _hip.ptr(bn.b), _hip.ptr(bn.rm), _hip.ptr(bn.rv), _hip.ptr(conv_bias),
-                                       bn.c, _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]), st), "lad_bn_fold " + bn.name)
-
-        fold(self.stem_bn, None)
-        for b in blocks:
-            fold(b.bn1, b.conv1.b)
-            fold(b.bn2, b.conv2.b)
-            if b.sc_conv is not None:
-                fold(b.sc_bn, None)
-        tags[id(blocks)] = tag
-
-    def _pack_f16(self, blocks):
-        """Half-precision weight images for the fp16 inference kernels (refreshed with the folds)."""
-        tags = self._f16_tags
-        tag = self._state_tag()
-        if tags.get(id(blocks)) == tag:
-            return
-        lib, st, dev = self.lib(), self._st(), self.device
-        for b in blocks:
-            for cs in (b.conv1, b.conv2, b.sc_conv):
-                if cs is None:
-                    continue
-                if getattr(cs, "wt_h", None) is None:
-                    cs.wt_h = torch.zeros(int(lib.lad_f16_packed_weight_halfs(cs.cout, cs.cin, cs.taps)), device=dev,
-                                          dtype=torch.float16)
-                _hip.check(lib.lad_f16_pack_weights(_hip.ptr(cs.w), cs.cout, cs.cin, cs.taps, _hip.ptr(cs.wt_h), st),
-                           "lad_f16_pack_weights " + cs.name)
-        tags[id(blocks)] = tag
-
     def _plan_eval(self, B, H, W, dtype=torch.float32, partial=False, owner=None):
         """owner: the run buffer ("l1" / "l2", _sup_buffer) this plan lives and dies with."""
         key = (B, H, W, "eval", dtype) + (("partial",) if partial else ())
@@ -1111,13 +1118,13 @@ class ResNetEngine:
         label = f"conv_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
         t0 = self._mark(label)
         if cs.stride == 1:
-            _hip.check(lib.lad_conv_fwd_eval(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
+            _hip.check(lib.lad_conv_fwd_eval(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
                                              _hip.ptr(addend), _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
                        "lad_conv_fwd_eval " + cs.name)
         else:
             if addend is not None:
                 raise _hip.LadHipError("stride-2 eval convolution takes no residual")
-            _hip.check(lib.lad_conv_s2_fwd_eval(_hip.ptr(x), _hip.ptr(cs.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
+            _hip.check(lib.lad_conv_s2_fwd_eval(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
                                                 _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
                        "lad_conv_s2_fwd_eval " + cs.name)
         self._mark_end(label, t0)
@@ -1127,24 +1134,16 @@ class ResNetEngine:
         label = f"conv_f16_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
         t0 = self._mark(label)
         if cs.stride == 1:
-            _hip.check(lib.lad_f16_conv_fwd(_hip.ptr(x), _hip.ptr(cs.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
+            _hip.check(lib.lad_f16_conv_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
                                             _hip.ptr(addend), _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
                        "lad_f16_conv_fwd " + cs.name)
         else:
-            _hip.check(lib.lad_f16_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
+            _hip.check(lib.lad_f16_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
                                                _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
                        "lad_f16_conv_s2_fwd " + cs.name)
         self._mark_end(label, t0)
 
     # ---- the eval forward in pieces (shared by the plain and the streaming sliding-window paths) ------------------------------
-    def _eval_prepare(self, blocks, half):
-        if half:
-            self._fold_eval(blocks)
-            self._pack_f16(blocks)
-        else:
-            self._pack_weights(blocks, need_dgrad=False)
-            self._fold_eval(blocks)
-
     def _eval_stem(self, half, fptr, out, out_byte_offset, B, H, W, frame_stride, frames_avail):
         lib, st = self.lib(), self._st()
         optr = ctypes.c_void_p(out.data_ptr() + out_byte_offset)
@@ -1196,7 +1195,7 @@ class ResNetEngine:
     @staticmethod
     def _f16_args(cs, bn):
         """{fp16 weight image, folded scale, folded shift} of one convolution, as the half-precision entry points take them."""
-        return _hip.ptr(cs.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1])
+        return _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1])
 
     def _s2_entry_f16(self, b, launch_one, launch_sc, rides):
         """conv1 (-> slot 0) and the 1x1 shortcut (-> slot 1) of the down-sampling block b in half precision: ONE launch
@@ -1285,7 +1284,7 @@ class ResNetEngine:
         p = self._plan_eval(B, H, W, torch.float16 if half else torch.float32)
         blocks = p["blocks"]
         lay = self._layout(blocks, B, H, W, half)
-        self._eval_prepare(blocks, half)
+        self._eval_prepare(half)
         cur = p["lv"][(H, W)][0]
         fptr = ctypes.c_void_p(feat_flat.data_ptr() + 4 * feat_offset_floats)
         self._eval_stem(half, fptr, cur, 0, B, H, W, frame_stride, frames_avail)
@@ -1313,8 +1312,7 @@ class ResNetEngine:
             run, d = None, 0
         plans = {"pw": pw, "ps": self._plan_eval(1, lay.Hs, W, dtype, partial=True),
                  "pt": self._plan_eval(lay.n_strip, lay.Ht, W, dtype, partial=True)}
-        for p in plans.values():
-            self._eval_prepare(p["blocks"], half)
+        self._eval_prepare(half)
         bufs = {}
         src = (feat_flat.data_ptr() + 4 * feat_offset_floats, frames_avail)   # the group's first frame, frames from there on
         self._stream_level1(lay, plans, bufs, run, src)
@@ -1337,7 +1335,6 @@ class ResNetEngine:
                 key = (run.S, run.B_max, lay.H, W)
                 bufs["cat"] = run.cat = self._sup_buffer("l1", lay.cat_rows * C, dtype, key)
                 psS = self._plan_eval(1, rows, W, dtype, partial=True, owner="l1")
-                self._eval_prepare(psS["blocks"], half)
                 if lay.stem_kept:
                     # the run's stem output is KEPT (2 GB for a 60-minute channel): the strips' first block reads its inner rows from it
                     cS = run.stem = self._sup_buffer("l0", int(self.lib().lad_act_rows(1, rows, W)) * C, dtype, key)
@@ -1419,20 +1416,13 @@ class ResNetEngine:
         return buf
 
     def _release_plan(self, key):
-        """Forget an eval plan and, when no other plan shares its layer table, everything cached per table (geometry specs with their
-        packed images, fold / pack tags -- keyed by id(), which a later table may reuse)."""
+        """Forget an eval plan, and its geometry's layer table when no other plan uses it (nothing of the weights goes with it: images
+        and folds are the model's)."""
         p = self._plans.pop(key, None)
-        if p is None:
+        if p is None or any(q.get("blocks") is p["blocks"] for q in self._plans.values()):
             return
-        blocks = p["blocks"]
-        if any(q.get("blocks") is blocks for q in self._plans.values()):
-            return
-        for gk in [gk for gk, gv in self._geom_specs.items() if gv[0] is blocks]:
+        for gk in [gk for gk, gv in self._geom_specs.items() if gv[0] is p["blocks"]]:
             del self._geom_specs[gk]
-        for tags in (self._fold_tag, self._f16_tags, self._packed_version):
-            tags.pop(id(blocks), None)
-        for k in [k for k in self._pack_tables if k[0] == id(blocks)]:
-            del self._pack_tables[k]
 
     def _stream_level2(self, lay, plans, bufs, run, d):
         """fp16 sliding windows, second resolution level.  Row r of window i at level 2 looks at level-1 rows 2r - 1 .. 2r + 1 of the
@@ -1449,8 +1439,6 @@ class ResNetEngine:
         C1, C2 = nb.conv1.cin, nb.conv1.cout
         ps2 = self._plan_eval(2, 2 * h2s, W, dtype, partial=True)
         pt2 = self._plan_eval(lay.n_strip2, 2 * Ht2, W, dtype, partial=True)
-        for p in (ps2, pt2):
-            self._eval_prepare(p["blocks"], True)
         streams_ready = False
         if run is None:
             cat2 = pw.get("l2cat")
@@ -1461,7 +1449,6 @@ class ResNetEngine:
         else:
             cat2 = run.cat2 = self._sup_buffer("l2", lay.rows2 * C2, dtype, (run.S, run.B_max, H, W))
             ps2 = self._plan_eval(2, 2 * h2s, W, dtype, partial=True, owner="l2")   # (a replaced buffer took the old run's plans with it)
-            self._eval_prepare(ps2["blocks"], True)
         bufs["cat2"] = cat2
         out_t2 = cat2[:(lay.n_strip2 * lay.img_t2 + W2 + 2) * C2]
         if lay.n_strip2 < lay.n_strip2_max:
@@ -1543,16 +1530,14 @@ class ResNetEngine:
 
     def _tail_params(self, tail):
         """HOST array of the 30 device pointers lad_f16_tail_fwd takes: {fp16 weight image, folded scale, folded shift} per convolution
-        (the tensors are created once per layer table by _fold_eval / _pack_f16 and refreshed in place: the pointers never move)."""
-        key = id(tail[0])
-        cached = self._tail_param_cache.get(key)
-        ptrs = []
-        for b in tail:
-            for cs, bn in ((b.conv1, b.bn1),) + (((b.sc_conv, b.sc_bn),) if b.sc_conv is not None else ()) + ((b.conv2, b.bn2),):
-                ptrs += [cs.wt_h.data_ptr(), bn.fold[0].data_ptr(), bn.fold[1].data_ptr()]
-        if cached is None or cached[0] != ptrs:
-            cached = self._tail_param_cache[key] = (ptrs, (_VP * len(ptrs))(*ptrs))
-        return cached[1]
+        of the blocks behind level 2 (the model's buffers, refreshed in place: built once)."""
+        if self._tail_ptrs is None:
+            ptrs = []
+            for b in tail:
+                for cs, bn in ((b.conv1, b.bn1),) + (((b.sc_conv, b.sc_bn),) if b.sc_conv is not None else ()) + ((b.conv2, b.bn2),):
+                    ptrs += [cs.par.wt_h.data_ptr(), bn.fold[0].data_ptr(), bn.fold[1].data_ptr()]
+            self._tail_ptrs = (_VP * len(ptrs))(*ptrs)
+        return self._tail_ptrs
 
     def predict_windows(self, feats, n_frames=100, chunk=None, start=0, stop=None, out=None, precision="fp32", stream=True):
         """Probabilities of the stride-one-frame windows of a whole-file feature matrix (the loop of
@@ -1670,13 +1655,13 @@ class ResNetEngine:
         lib, P, h, w, ws = self.lib(), _hip.ptr, cs.h_in, cs.w_in, self._wg_ws(p, cs)
         if bn is not None:
             dy, bx, bits, coef = bn
-            _hip.check(lib.lad_conv_wgrad_h2_bnbwd(P(x), P(in_coef), P(dy), P(bx), P(bits), P(coef), P(p["bcoef"]), P(dout), P(ws), P(cs.gw),
-                                                   P(cs.gb), B, h, w, cs.cin, self._st()), f"{fn} {cs.name}")
+            _hip.check(lib.lad_conv_wgrad_h2_bnbwd(P(x), P(in_coef), P(dy), P(bx), P(bits), P(coef), P(p["bcoef"]), P(dout), P(ws), P(cs.par.gw),
+                                                   P(cs.par.gb), B, h, w, cs.cin, self._st()), f"{fn} {cs.name}")
         elif kind == "f32":
-            self._on_side(lambda st: _hip.check(lib.lad_conv_wgrad(P(x), P(dout), P(ws), P(cs.gw), P(cs.gb), B, h, w, cs.cin, cs.cout, cs.taps, st),
+            self._on_side(lambda st: _hip.check(lib.lad_conv_wgrad(P(x), P(dout), P(ws), P(cs.par.gw), P(cs.par.gb), B, h, w, cs.cin, cs.cout, cs.taps, st),
                                                 f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
         else:   # same split arithmetic as the forward / data-gradient launches of this layer (csrc/wgrad_mfma.hip)
-            self._on_side(lambda st: _hip.check(getattr(lib, fn)(P(x), P(in_coef), P(dout), P(ws), P(cs.gw), P(cs.gb), B, h, w, cs.cin, st),
+            self._on_side(lambda st: _hip.check(getattr(lib, fn)(P(x), P(in_coef), P(dout), P(ws), P(cs.par.gw), P(cs.par.gb), B, h, w, cs.cin, st),
                                                 f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
 
     def backward(self, dprobs=None):
@@ -1780,13 +1765,13 @@ class ResNetEngine:
 
                 def s2_wgrad(cs, dout, xin=a["x"]):   # one convolution's weight gradient in a launch of its own
                     self._on_side(lambda sst: _hip.check(lib.lad_conv_s2_wgrad(
-                        _hip.ptr(xin), _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)), _hip.ptr(cs.gw), _hip.ptr(cs.gb), B, hi, wi, cs.cin, cs.cout,
+                        _hip.ptr(xin), _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)), _hip.ptr(cs.par.gw), _hip.ptr(cs.par.gb), B, hi, wi, cs.cin, cs.cout,
                         cs.taps, sst), "lad_conv_s2_wgrad " + cs.name), dout, small=cs.cin <= 32)
 
                 if ch.sc_wgrad_fused:   # conv1's and the shortcut's weight gradients in one launch (same input rows; csrc/conv_s2_bwd.hip)
                     self._on_side(lambda sst, c1s=c1s, sc=sc, dc1=dc1, aux=aux, xin=a["x"]: _hip.check(lib.lad_conv_s2_wgrad_fused(
-                        _hip.ptr(xin), _hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.gw), _hip.ptr(c1s.gb),
-                        _hip.ptr(sc.gw), B, hi, wi, c1s.cin, c1s.cout, sst), "lad_conv_s2_wgrad_fused " + c1s.name), dc1, small=c1s.cin <= 32)
+                        _hip.ptr(xin), _hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.par.gw), _hip.ptr(c1s.par.gb),
+                        _hip.ptr(sc.par.gw), B, hi, wi, c1s.cin, c1s.cout, sst), "lad_conv_s2_wgrad_fused " + c1s.name), dc1, small=c1s.cin <= 32)
                     if dc1.data_ptr() in self._side_readers:   # (it ran on the side stream) the launch reads aux as well
                         self._side_readers[aux.data_ptr()] = self._side_readers[dc1.data_ptr()]
                 else:
@@ -1798,27 +1783,27 @@ class ResNetEngine:
                     # both data gradients on the split-operand path, parity class by parity class (dgrad_s2b3_kernel)
                     n_part = int(lib.lad_conv_s2b3_dgrad_partials(B, hi, wi))
                     assert not ch.dgrad1_bn or n_part * 2 * 64 <= p["partials"].numel()
-                    _hip.check(lib.lad_conv_s2b3_dgrad(_hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(c1s.wt3_s2d), _hip.ptr(dx),
+                    _hip.check(lib.lad_conv_s2b3_dgrad(_hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(c1s.par.wt3_s2d), _hip.ptr(dx),
                                                        _hip.ptr(p["partials"]) if ch.dgrad1_bn else None, _hip.ptr(stat[0]), _hip.ptr(stat[1]),
                                                        _hip.ptr(stat[2]), B, hi, wi, st), "lad_conv_s2b3_dgrad " + c1s.name)
                 elif ch.entry == "s2_fused" and ch.dgrad1_bn:
                     n_part = int(lib.lad_conv_s2_dgrad_partials(B, hi, wi))
                     assert n_part * 2 * 64 <= p["partials"].numel()
-                    _hip.check(lib.lad_conv_s2_dgrad_fused_bnstat(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx),
+                    _hip.check(lib.lad_conv_s2_dgrad_fused_bnstat(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx),
                                                                   _hip.ptr(p["partials"]), _hip.ptr(stat[0]), _hip.ptr(stat[1]),
                                                                   _hip.ptr(stat[2]), B, hi, wi, c1s.cin, c1s.cout, st),
                                "lad_conv_s2_dgrad_fused_bnstat " + c1s.name)
                 elif ch.entry == "s2_fused":   # both data gradients in one launch, dx written once
-                    _hip.check(lib.lad_conv_s2_dgrad_fused(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx),
+                    _hip.check(lib.lad_conv_s2_dgrad_fused(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx),
                                                            B, hi, wi, c1s.cin, c1s.cout, st), "lad_conv_s2_dgrad_fused " + c1s.name)
                 else:
-                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(dc1), _hip.ptr(c1s.wt_d), _hip.ptr(dx), B, hi, wi, c1s.cin, c1s.cout, 9, 0,
+                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(dx), B, hi, wi, c1s.cin, c1s.cout, 9, 0,
                                                      st), "lad_conv_s2_dgrad " + c1s.name)
                 pre2, pre2_tiles = ch.dgrad1_bn is not None, n_part
                 if not ch.sc_wgrad_fused:
                     s2_wgrad(sc, aux)
                 if ch.entry == "plain":
-                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(aux), _hip.ptr(sc.wt_d), _hip.ptr(dx), B, hi, wi, sc.cin, sc.cout, 1, 1, st),
+                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx), B, hi, wi, sc.cin, sc.cout, 1, 1, st),
                                "lad_conv_s2_dgrad " + sc.name)
             dy = dx
         # stem: bn1 + conv1 weight gradient.  The input needs no gradient and the convolution is recomputed from the features:

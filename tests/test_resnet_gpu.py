@@ -2596,6 +2596,133 @@ def test_init_weights_after_a_forward_invalidates_the_packed_weights():
     np.testing.assert_allclose(after.cpu().numpy(), ref.numpy(), atol=P_TOL)
 
 
+# ---- buffers derived from the weights belong to the model, not to a geometry ---------------------------------------------
+def _stream_features(T, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(T, 44, generator=g) * 2.0 - 8.0).cuda()
+
+
+def _layer_buffers(eng):
+    """{layer name: set of (fp16 image, exact-f32 forward image, fold scale, fold shift) addresses over every plan's layer table},
+    and the number of distinct layer tables walked."""
+    seen, tables = {}, set()
+    for p in eng._plans.values():
+        tables.add(id(p["blocks"]))
+        for b in p["blocks"]:
+            for cs, bn in ((b.conv1, b.bn1), (b.conv2, b.bn2)) + (((b.sc_conv, b.sc_bn),) if b.sc_conv is not None else ()):
+                seen.setdefault(cs.name, set()).add((cs.par.wt_h.data_ptr(), cs.par.wt_f.data_ptr(), bn.fold[0].data_ptr(),
+                                                     bn.fold[1].data_ptr()))
+    return seen, len(tables)
+
+
+def test_every_geometry_reads_one_buffer_per_layer():
+    """An fp16 predict_windows on the fully shared path with runs works on five or six geometries (windows, stream, run-long stream,
+    strips, level-2 phase streams, level-2 strips): every plan's layer table names the SAME fp16 image, exact-f32 forward image and
+    BatchNorm fold per layer -- and so do the plans of an fp32 call afterwards."""
+    m, _ = build_model(61)
+    m.eval()
+    eng = m.engine
+    fg = _stream_features(200, 21)
+    chunk = 64                                   # groups of 64, 64, 64, 8 windows: one run of 200
+    eng.predict_windows(fg, chunk=chunk, precision="fp16")
+    lay = eng._plans[(chunk, 100, 44, "eval", torch.float16)]["layout"]
+    assert lay.mode == "shared2" and lay.run == (200, chunk)
+    seen, n_tables = _layer_buffers(eng)
+    assert n_tables >= 5 and len(seen) == 19
+    assert all(len(v) == 1 for v in seen.values()), {k: v for k, v in seen.items() if len(v) != 1}
+    eng.predict_windows(fg, chunk=chunk, precision="fp32")
+    assert eng._plans[(chunk, 100, 44, "eval", torch.float32)]["layout"].mode == "assembled"
+    seen32, n_tables32 = _layer_buffers(eng)
+    assert n_tables32 >= n_tables and seen32 == seen
+
+
+class _CountingLib:
+    """Forwards every call to the library and counts it by entry point."""
+
+    def __init__(self, lib):
+        import collections
+        self._lib, self.calls = lib, collections.Counter()
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            self.calls[name] += 1
+            return fn(*args)
+        return call
+
+
+def test_weight_derived_buffers_are_refreshed_once_per_model():
+    """After notify_weights_changed() an fp16 predict_windows over several groups folds every BatchNorm that follows a convolution
+    ONCE and packs every residual-block convolution's fp16 image ONCE (20 and 19 launches at resnet_base), whatever the number of
+    geometries it runs on; the same call again issues none; an fp32 call packs the exact-f32 forward images in one launch, then
+    none.  (Before the packed images and folds moved from the per-geometry layer tables to the model, the first fp16 call of this
+    test issued each once per geometry -- seven of them: 140 folds and 133 packs -- and the first fp32 call four pack launches.)"""
+    m, _ = build_model(62)
+    m.eval()
+    eng = m.engine
+    n_bn = sum(isinstance(x, torch.nn.BatchNorm2d) for x in m.modules())                       # (the head's two are BatchNorm1d)
+    n_conv = sum(isinstance(x, torch.nn.Conv2d) and x is not m.conv1 for x in m.modules())     # (the stem reads its f32 weights)
+    assert (n_bn, n_conv) == (20, 19)
+    fg = _stream_features(200, 22)
+    eng.ensure_flat()
+    lib = eng._lib = _CountingLib(eng.lib())
+    try:
+        eng.notify_weights_changed()
+        first = eng.predict_windows(fg, chunk=64, precision="fp16").clone()
+        assert eng._plans[(64, 100, 44, "eval", torch.float16)]["layout"].run == (200, 64)
+        assert (lib.calls["lad_bn_fold"], lib.calls["lad_f16_pack_weights"]) == (n_bn, n_conv), lib.calls
+        lib.calls.clear()
+        again = eng.predict_windows(fg, chunk=64, precision="fp16")
+        assert (lib.calls["lad_bn_fold"], lib.calls["lad_f16_pack_weights"]) == (0, 0), lib.calls
+        assert torch.equal(first, again)
+        lib.calls.clear()
+        eng.predict_windows(fg, chunk=64, precision="fp32")
+        assert lib.calls["lad_conv_pack_weights_multi"] == 1, lib.calls
+        lib.calls.clear()
+        eng.predict_windows(fg, chunk=64, precision="fp32")
+        assert lib.calls["lad_conv_pack_weights_multi"] == 0, lib.calls
+    finally:
+        eng._lib = lib._lib
+
+
+def test_replacing_a_runs_buffers_leaves_nothing_stale():
+    """One engine predicts files of A, B and A frames (fp16, runs on): each new run length replaces the run's buffers and releases the
+    run-long plans of the one before (engine._sup_buffer).  Every result equals that of an engine that never predicted anything else,
+    with a training step between the two A calls, so that folds and images are refreshed after a release."""
+    A, B, chunk, seed = 150, 170, 64, 63          # just above two groups of 64 windows
+    fa, fb = _stream_features(A, 23), _stream_features(B, 24)
+    x = torch.from_numpy(recipe.make_features(64, 16)).cuda()
+    t = torch.from_numpy(recipe.make_labels(74, 16)).cuda()
+
+    def run_plan(T):    # the run-long stream plan of a file of T frames
+        return (1, T + 99, 44, "eval", torch.float16, "partial")
+
+    def fresh():
+        model, _ = build_model(seed)
+        model.eval()
+        return model
+
+    m = fresh()
+    eng = m.engine
+    got_a = eng.predict_windows(fa, chunk=chunk, precision="fp16").clone()
+    assert run_plan(A) in eng._plans
+    assert torch.equal(got_a, fresh().engine.predict_windows(fa, chunk=chunk, precision="fp16"))
+    got_b = eng.predict_windows(fb, chunk=chunk, precision="fp16").clone()
+    assert run_plan(B) in eng._plans and run_plan(A) not in eng._plans
+    assert torch.equal(got_b, fresh().engine.predict_windows(fb, chunk=chunk, precision="fp16"))
+    twin = fresh()
+    for model in (m, twin):
+        model.train()
+        model.engine.reset_optimizer()
+        model.train_step(x, t, drop_masks=None)
+        model.eval()
+    got_a2 = eng.predict_windows(fa, chunk=chunk, precision="fp16").clone()
+    assert run_plan(A) in eng._plans and run_plan(B) not in eng._plans
+    assert torch.equal(got_a2, twin.engine.predict_windows(fa, chunk=chunk, precision="fp16"))
+    assert not torch.equal(got_a2, got_a)         # (the step did move the weights)
+
+
 def test_errors_are_loud():
     import _hip
     import models
