@@ -98,6 +98,67 @@ int lad_gather_segments(const float *const *chan_ptr, const int64_t *chan_frames
                         const int64_t *first, const int32_t *count, int64_t n_seg, int32_t n_frames, int32_t F, float pad,
                         float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Train-time augmentation: lad_gather_segments with SpecAugment and a noise mix on the way (csrc/augment.hip).
+ * Modelled on what Lhotse does to precomputed features -- SpecAugment (time warp, frame masks, feature masks, mean fill) and
+ * the feature-domain mixer behind MixedCut, log(exp(a) + gain * exp(b)) with the gain taken from an SNR over summed energies.
+ * Parity with Lhotse is [UPSTREAM-UNVERIFIED]; the text below IS the specification (tests/_augment_model.py is a second
+ * implementation of it, in numpy).
+ *
+ * Inputs.  Per segment b: chan[b], first[b], count[b] as for lad_gather_segments; T = n_frames, F, pad.
+ *
+ * Random words.  Philox4x32-10 (csrc/lad_philox.h) with key (seed & 0xffffffff, seed >> 32).  Block k of segment b is
+ *   philox(counter = (first[b] & 0xffffffff, chan[b], epoch, k)) -> words r0..r3.
+ * A segment's augmentation is a pure function of (seed, epoch, channel, first frame): not of its position in the batch, the
+ * batch size, the rank or the world size.  The caller keeps 0 <= first[b] < 2^32.
+ *   mulhi(u, n) = (u * n) >> 32         (an integer in [0, n))
+ *   unit(u)     = float(u >> 8) * 2^-24 (exact in fp32; the dropout mask's rule)
+ * p, mix_p and the four range ends are fp32 (the struct's fields); the gates compare in fp32.
+ *
+ * Block 0.   spec gate: unit(r0) < p.    mix gate: unit(r1) < mix_p.
+ *            snr_db = snr_lo + (snr_hi - snr_lo) * unit(r2).    gain_db = gain_lo + (gain_hi - gain_lo) * unit(r3).
+ * Block 1.   noise channel j = noise_list[mulhi(r0, n_noise)];  noise first frame = mulhi(r1, frames[j] - T + 1);
+ *            warp centre c = W + mulhi(r2, T - 2 W);  warp shift w = mulhi(r3, 2 W - 1) - (W - 1);  c' = c + w.
+ *            (W <= c <= T - W - 1 and |w| <= W - 1, so 1 <= c' <= T - 2.)
+ * Block 2+m, for m < max(n_time, n_freq).
+ *            time mask m (m < n_time):     width = mulhi(r0, Wt + 1), start = mulhi(r1, T - width + 1);
+ *            feature mask m (m < n_freq):  width = mulhi(r2, Wf + 1), start = mulhi(r3, F - width + 1).
+ *
+ * Stages, in this order.
+ *  1. Gather.  As lad_gather_segments, `pad` rows included: x[T][F].
+ *  2. Mix / gain.  Runs only if (the mix gate passed and n_noise > 0) or the gain range is not (0, 0); otherwise the values stay
+ *     bit-identical copies.  a = the gathered segment, b = frames [noise first frame, + T) of channel j.
+ *       Ea = sum of exp(a) over all T * F entries;  Eb = sum of exp(b) over the T * F entries of the excerpt;
+ *       G = 10^(gain_db / 10);  k = G * Ea / (10^(snr_db / 10) * Eb), or 0 without mix;
+ *       x = log(max(1e-10, G * exp(a) + k * exp(b))).          (accurate expf / logf / powf, fp32 sums)
+ *  3. Time warp.  Only if the spec gate passed and W > 0.  Output row t < c' reads position t * c / c' of x; output row t >= c'
+ *     reads position c + (t - c') * (T - c) / (T - c').  With q and rem the integer quotient and remainder of that fraction, den
+ *     its denominator and base = 0 or c:  i0 = base + q,  i1 = min(i0 + 1, T - 1),  frac = float(rem) / float(den) (fp32), and the
+ *     row is x[i0] + frac * (x[i1] - x[i0]) (one subtraction, one fused multiply-add).  Rows with rem = 0 are copies of x[i0].
+ *  4. Masks.  Only if the spec gate passed.  The fill value is the mean over all T * F entries after stage 3; every entry of a
+ *     row in a time mask or of a filter in a feature mask becomes that value.
+ * A segment none of whose stages fire is a copy: its bits are those lad_gather_segments writes.
+ *
+ * noise_list: DEVICE array of n_noise channel indices (into chan_ptr / chan_frames), or NULL with n_noise = 0 (no mixing);
+ * min_noise_frames: the smallest frame count among those channels, as the caller knows it on the host.
+ * Refused with LAD_ERR_INVALID before anything is launched: F % 4 != 0; T <= 2 W; Wt > T; Wf > F; more than 16 masks of a kind;
+ * a probability outside [0, 1]; lo > hi; min_noise_frames < T; a segment pair (2 * T * F * 4 bytes + scratch) past the 160 KB
+ * of LDS of a CU. */
+typedef struct lad_augment_params {
+    uint64_t seed;
+    uint32_t epoch;
+    float p, mix_p;            /* SpecAugment gate, mix gate */
+    float snr_lo, snr_hi;      /* dB */
+    float gain_lo, gain_hi;    /* dB */
+    int32_t W;                 /* time warp: the centre moves by less than W frames (0: no warp) */
+    int32_t n_time, Wt;        /* time masks: how many, widest */
+    int32_t n_freq, Wf;        /* feature masks: how many, widest */
+} lad_augment_params;
+int lad_gather_segments_aug(const float *const *chan_ptr, const int64_t *chan_frames, const int32_t *chan,
+                            const int64_t *first, const int32_t *count, int64_t n_seg, int32_t n_frames, int32_t F, float pad,
+                            const lad_augment_params *params, const int32_t *noise_list, int32_t n_noise,
+                            int64_t min_noise_frames, float *out, void *stream);
+
 /* Sliding-window inference (segment_laughter.py:90-101): windows at a stride of one frame share 99 % of their input, and the
  * full-resolution layers (stem + the stride-1 blocks) see that overlap unchanged outside `band` rows of a window's top and
  * bottom (band = 3x3 convolutions on the way).  lad_assemble_windows builds the activation of n_windows windows of H rows from

@@ -31,6 +31,14 @@ class FbankCfg(ctypes.Structure):
                 ("log_floor", ctypes.c_float)]
 
 
+class AugmentParams(ctypes.Structure):
+    """lad_augment_params of include/lad_hip.h (the convention is written out there)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("epoch", ctypes.c_uint32), ("p", ctypes.c_float), ("mix_p", ctypes.c_float),
+                ("snr_lo", ctypes.c_float), ("snr_hi", ctypes.c_float), ("gain_lo", ctypes.c_float), ("gain_hi", ctypes.c_float),
+                ("W", ctypes.c_int32), ("n_time", ctypes.c_int32), ("Wt", ctypes.c_int32), ("n_freq", ctypes.c_int32),
+                ("Wf", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lad_hip.h must be listed here
 # (tests/test_cabi.py cross-checks this table against the header and the built library).
 SIGNATURES = {
@@ -45,6 +53,8 @@ SIGNATURES = {
     "lad_fbank_forward": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
     "lad_fbank_forward_long": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "lad_gather_segments": (c_int, [c_void_p] * 5 + [c_i64, c_i32, c_i32, c_float, c_void_p, c_void_p]),
+    "lad_gather_segments_aug": (c_int, [c_void_p] * 5 + [c_i64, c_i32, c_i32, c_float, ctypes.POINTER(AugmentParams), c_void_p, c_i32, c_i64,
+                                        c_void_p, c_void_p]),
     "lad_assemble_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "lad_act_rows": (c_i64, [c_i64, c_i32, c_i32]),
     "lad_conv_packed_weight_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),

@@ -42,3 +42,23 @@ FEAT = {
     "num_samples": 100,
     "num_filters": 44
 }
+
+# Train-time augmentation presets (augment.AugmentConfig fields; the convention is in include/lad_hip.h next to
+# lad_gather_segments_aug).  The reference has none -- its 'resnet_with_augmentation' names a model, not a data path; the values are
+# SpecAugment's usual ones scaled to one-second segments of 100 frames x 44 filters.
+AUGMENT = {}
+
+AUGMENT['spec'] = {
+    'p': 0.9,
+    'W': 5,                     # time warp: the centre frame moves by at most 4 frames
+    'n_time': 2, 'Wt': 20,      # two frame masks of 0..20 frames
+    'n_freq': 2, 'Wf': 8,       # two feature masks of 0..8 filters
+}
+
+AUGMENT['mix'] = {
+    'mix_p': 0.5,
+    'snr_lo': 5.0, 'snr_hi': 20.0,     # dB
+    'gain_lo': -6.0, 'gain_hi': 6.0,   # dB
+}
+
+AUGMENT['spec+mix'] = {**AUGMENT['spec'], **AUGMENT['mix']}

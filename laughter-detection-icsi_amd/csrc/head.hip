@@ -9,6 +9,7 @@
 // Dropout masks (already scaled by 1/(1-p)) are supplied by the caller so the host keeps control of the RNG.
 #include "lad_common.h"
 #include "lad_device.h"
+#include "lad_philox.h"
 
 namespace {
 using namespace lad;
@@ -45,22 +46,6 @@ struct HeadArgs {
     int n_nbt;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11): four 32-bit words from a 128-bit counter and a 64-bit key -- a counter-based generator needs no
-// state, so a mask element's value is a pure function of (seed, draw number, element index) and a hipGraph replay draws fresh masks
-struct U4 {
-    unsigned x, y, z, w;
-};
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 // inverted-dropout mask values (0 or 1 / keep) for elements 4 g .. 4 g + 3 of mask `which` at draw `draw`
 __device__ __forceinline__ float4 dropout_mask4(unsigned long long seed, long long draw, int which, unsigned g, float keep) {
     const U4 r = philox4x32_10(U4{g, (unsigned)which, (unsigned)draw, (unsigned)((unsigned long long)draw >> 32)}, (unsigned)seed,

@@ -73,12 +73,74 @@ def gather_segments(store, chan, first, count, n_frames, pad, out=None):
     return out
 
 
-class LadDataset(torch.utils.data.Dataset):
-    """Laugh-activity-detection dataset: indexing with a batch of segment ids returns the reference's batch dict."""
+class NoiseChannels:
+    """The channels of a store that segments may be mixed with (augment.AugmentConfig.mix_p): their indices on the device for the
+    kernel, their frame counts on the host for the validation.  channels: store indices or keys."""
 
-    def __init__(self, store, table, pad_value=LOG_EPSILON):
+    def __init__(self, store, channels):
+        idx = [store.index_of(c) if isinstance(c, str) else int(c) for c in channels]
+        if any(not 0 <= i < len(store.mats) for i in idx):
+            raise ValueError(f"noise channel index outside the store's {len(store.mats)} channels")
+        self.store = store
+        self.index = torch.tensor(idx, dtype=torch.int32, device=store.device)
+        self.frames = [int(store.mats[i].shape[0]) for i in idx]
+
+    def __len__(self):
+        return len(self.frames)
+
+
+def gather_segments_augmented(store, chan, first, count, n_frames, pad, cfg, epoch, noise, out=None, check_first=True):
+    """gather_segments with train-time augmentation in the same launch (csrc/augment.hip; the convention: include/lad_hip.h).
+    cfg: augment.AugmentConfig; epoch: part of the random counter, so an epoch's batches differ from the last one's; noise: a
+    NoiseChannels, a list of store indices / keys, or None (no mixing).  Refusals are ValueErrors raised before the launch.
+    check_first: read first.min() / .max() back to check 0 <= first < 2^32 (the counter holds 32 bits of it) -- a device
+    synchronisation; LadDataset checks its table once instead."""
+    if noise is not None and not isinstance(noise, NoiseChannels):
+        noise = NoiseChannels(store, noise)
+    if noise is not None and len(noise) == 0:
+        noise = None
+    F = store.num_filters
+    cfg.validate_for(n_frames, F, noise.frames if noise is not None else None)
+    params = cfg.params(epoch)
+    n = int(chan.shape[0])
+    if check_first and n and not (int(first.min()) >= 0 and int(first.max()) < 2 ** 32):
+        raise ValueError("augmented segments need 0 <= first frame < 2^32")
+    ptrs, frames = store.tables()
+    if out is None:
+        out = torch.empty((n, n_frames, F), device=store.device, dtype=torch.float32)
+    _hip.check(_hip.lib().lad_gather_segments_aug(_hip.ptr(ptrs), _hip.ptr(frames), _hip.ptr(chan), _hip.ptr(first), _hip.ptr(count), n,
+                                                  n_frames, F, float(pad), ctypes.byref(params),
+                                                  _hip.ptr(noise.index if noise is not None else None), len(noise) if noise is not None else 0,
+                                                  min(noise.frames) if noise is not None else 0, _hip.ptr(out),
+                                                  _hip.stream_handle(store.device)),
+               "lad_gather_segments_aug")
+    return out
+
+
+class LadDataset(torch.utils.data.Dataset):
+    """Laugh-activity-detection dataset: indexing with a batch of segment ids returns the reference's batch dict.
+
+    augment: an augment.AugmentConfig -- the batches are augmented in the gather launch, differently in every epoch
+    (`set_epoch`); None: the plain gather.  noise: what mixing draws from -- 'self' (the channels this table names that hold at
+    least a segment's frames: other speech, no extra data, and never a channel that only another split sharing the store uses), a
+    list of store keys / indices, or a NoiseChannels."""
+
+    def __init__(self, store, table, pad_value=LOG_EPSILON, augment=None, noise=None):
         super().__init__()
         self.store, self.table, self.pad_value = store, table, pad_value
+        self.augment, self.noise, self.epoch = augment, None, 0
+        if augment is not None:
+            T = table.frames_per_segment
+            if isinstance(noise, str):
+                if noise != 'self':
+                    raise ValueError(f"noise must be 'self', a list of channels or a NoiseChannels, got {noise!r}")
+                noise = [i for i in sorted({store.index_of(k) for k in table.channels}) if store.mats[i].shape[0] >= T]
+            if noise is not None and not isinstance(noise, NoiseChannels):
+                noise = NoiseChannels(store, noise)
+            self.noise = noise if noise is not None and len(noise) else None
+            augment.validate_for(T, store.num_filters, self.noise.frames if self.noise is not None else None)
+            if len(table) and not (int(table.first_frame.min()) >= 0 and int(table.first_frame.max()) < 2 ** 32):
+                raise ValueError("augmented segments need 0 <= first frame < 2^32")
         remap = np.asarray([store.index_of(k) for k in table.channels], np.int32)
         dev = store.device
         self._chan = torch.from_numpy(remap[table.channel]).to(dev)
@@ -89,10 +151,18 @@ class LadDataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.table)
 
+    def set_epoch(self, epoch):
+        """The epoch number of the batches to come (augmentation only: part of the random counter)."""
+        self.epoch = int(epoch)
+
     def __getitem__(self, cuts):
         idx = torch.as_tensor(cuts, dtype=torch.int64, device=self.store.device).view(-1)
         chan, first, count = self._chan[idx].contiguous(), self._first[idx].contiguous(), self._count[idx].contiguous()
-        inputs = gather_segments(self.store, chan, first, count, self.table.frames_per_segment, self.pad_value)
+        if self.augment is None:
+            inputs = gather_segments(self.store, chan, first, count, self.table.frames_per_segment, self.pad_value)
+        else:
+            inputs = gather_segments_augmented(self.store, chan, first, count, self.table.frames_per_segment, self.pad_value,
+                                               self.augment, self.epoch, self.noise, check_first=False)
         return {"inputs": inputs, "input_lens": count, "is_laugh": self._label[idx].contiguous(), "cut": cuts}
 
 

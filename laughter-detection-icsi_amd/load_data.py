@@ -191,7 +191,8 @@ def _stored_features(manifest, path, num_filters, extractor=None):
 
 
 def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, audio_root=None, seed=None, rank=0,
-                               world=1, store=None, index_seed=INDEX_SHUFFLE_SEED, feats_manifest=None, resample=False):
+                               world=1, store=None, index_seed=INDEX_SHUFFLE_SEED, feats_manifest=None, resample=False,
+                               augment=None, noise=None):
     '''
     Create a dataloader for the provided split
         - split needs to be one of 'train', 'dev' and 'test'
@@ -208,7 +209,14 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
           datasets.py:56 read them).  The stored matrices are the extractor's raw float32 output (no lilcom stage), so the
           batches are bit-equal to those of the audio path; channels the manifest does not list fall back to their audio.
         - resample: audio files at another rate than 16 kHz are converted on the GPU (load_audio_device) instead of refused
+        - augment: an augment.AugmentConfig -- the batches are augmented inside the gather launch (csrc/augment.hip); the loop
+          calls `loader.dataset.set_epoch(e)` before each epoch.  None (the default): today's batches, bit for bit.
+        - noise: what augment.mix_p mixes in.  'self': the channels of this split that hold at least a segment's frames (other
+          speech, no extra data); a directory or a list of audio / .npy paths: featurised into the same store under the keys
+          `noise:<file name without extension>`
     '''
+    if noise is not None and augment is None:
+        raise ValueError("noise channels without an augmentation config: pass augment=")
     table = load_segment_table(cutset_dir, split, shuffle=shuffle, seed=seed, world=world, index_seed=index_seed)
     if store is None:
         extractor = get_feat_extractor(num_samples=cfg.FEAT['num_samples'], num_filters=cfg.FEAT['num_filters'])
@@ -230,10 +238,38 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
                 store.add_audio(key, load_audio_device(path, device=store.device, resample=True))
             else:
                 store.add_audio(key, load_audio(path))
-    dataset = LadDataset(store, table)
+    if augment is None:
+        dataset = LadDataset(store, table)
+    else:
+        dataset = LadDataset(store, table, augment=augment, noise=_noise_channels(store, noise, resample))
     # train-mode BatchNorm needs two segments per batch on every rank: a shorter ragged tail is dropped on all ranks alike
     return SegmentLoader(dataset, SegmentSampler(len(table), max_cuts=batch_size, rank=rank, world=world,
                                                  min_batch=2 if split == 'train' else 1))
+
+
+def _noise_channels(store, noise, resample=False):
+    """`noise` of create_training_dataloader -> what LadDataset takes: 'self' as it is, files featurised into the store."""
+    if noise is None or noise == 'self':
+        return noise
+    if isinstance(noise, (str, os.PathLike)):
+        d = os.fspath(noise)
+        if not os.path.isdir(d):
+            raise ValueError(f"noise: {d} is neither 'self' nor a directory")
+        paths = sorted(os.path.join(d, f) for f in os.listdir(d) if os.path.splitext(f)[1].lower() in ('.wav', '.npy'))
+        if not paths:
+            raise ValueError(f"noise: no .wav / .npy files in {d}")
+    else:
+        paths = [os.fspath(p) for p in noise]
+    keys = []
+    for path in paths:
+        key = 'noise:' + os.path.splitext(os.path.basename(path))[0]
+        if key not in store.keys:
+            if resample:
+                store.add_audio(key, load_audio_device(path, device=store.device, resample=True))
+            else:
+                store.add_audio(key, load_audio(path))
+        keys.append(key)
+    return keys
 
 
 class InferenceLoader:

@@ -26,6 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import config as config_mod  # noqa: E402
+import augment as augment_mod  # noqa: E402
 import load_data  # noqa: E402
 import parallel  # noqa: E402
 import torch_utils  # noqa: E402
@@ -182,7 +183,7 @@ def find_feats_manifests(args):
     return found
 
 
-def main(argv=None):
+def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--config', type=str, required=True)
     parser.add_argument('--checkpoint_dir', type=str, required=True)
@@ -206,8 +207,33 @@ def main(argv=None):
                         help='directory with the {split}_feats.jsonl manifests compute_features.py wrote: train from the stored '
                              'feature matrices instead of re-featurising audio (default: <data_root>/<lhotse_dir>/cutsets if it '
                              'holds such manifests, as the reference reads its stored features from --lhotse_dir)')
+    parser.add_argument('--augment', type=str, default='none', choices=['none'] + list(config_mod.AUGMENT),
+                        help='train-time augmentation preset (config.AUGMENT): SpecAugment and / or a noise mix inside the gather '
+                             'launch; the dev batches are never augmented')
+    parser.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed); the same on every rank')
+    parser.add_argument('--noise', type=str, default=None,
+                        help="what --augment mix / spec+mix mixes in: 'self' (the other training channels) or a directory of .wav / .npy files")
+    return parser
+
+
+def augment_from_args(args):
+    """(augment.AugmentConfig or None, noise) of the parsed flags; a contradiction between them is a ValueError."""
+    cfg = augment_mod.from_preset(args.augment, seed=args.seed if args.augment_seed is None else args.augment_seed)
+    if cfg is None and args.noise is not None:
+        raise ValueError("--noise without --augment mix / spec+mix")
+    if cfg is not None and cfg.mixes and args.noise is None:
+        raise ValueError(f"--augment {args.augment} mixes noise in: give --noise self or --noise <directory>")
+    return cfg, (args.noise if cfg is not None and cfg.mixes else None)
+
+
+def main(argv=None):
+    parser = make_parser()
     args = parser.parse_args(argv)
     warn_ignored_flags(args, parser)
+    try:
+        augment_cfg, noise = augment_from_args(args)
+    except ValueError as e:
+        raise SystemExit(f"train.py: {e}")
 
     config = config_mod.MODEL_MAP[args.config]
     batch_size = int(args.batch_size or config['batch_size'])
@@ -250,7 +276,10 @@ def main(argv=None):
                                                       audio_root=args.data_root, feats_manifest=manifests.get('dev'))
     train_loader = load_data.create_training_dataloader(data_dir, 'train', batch_size=batch_size, audio_root=args.data_root,
                                                         rank=rank, world=world, store=dev_loader.dataset.store,
-                                                        feats_manifest=manifests.get('train'))
+                                                        feats_manifest=manifests.get('train'), augment=augment_cfg, noise=noise)
+    if rank == 0 and augment_cfg is not None:
+        n_noise = len(train_loader.dataset.noise) if train_loader.dataset.noise is not None else 0
+        print(f"Augmentation: {args.augment} (seed {augment_cfg.seed}, {n_noise} noise channels) on the training batches")
     if rank == 0:
         with open(os.path.join(args.checkpoint_dir, 'train_params.csv'), 'w', newline='') as f:
             w = csv.writer(f)
@@ -260,6 +289,7 @@ def main(argv=None):
     start = time.time()
     for epoch in range(args.num_epochs):
         t0 = time.time()
+        train_loader.dataset.set_epoch(model.epoch)   # (augmentation only: every epoch draws its own; model.epoch survives a restart)
         loss = run_epoch(model, train_loader, dev_loader, args.checkpoint_dir, log_frequency, batch_size, rows, reducer,
                          rank=rank, max_steps=args.max_steps, grad_accum=grad_accum)
         torch.cuda.synchronize()
