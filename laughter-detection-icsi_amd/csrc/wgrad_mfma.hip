@@ -678,8 +678,9 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__re
 // Round 4: the 64 x 64 x 9 weight gradient on TWO f16 planes per operand, "wgrad_h2" (arithmetic: conv_h2.hip).
 //
 // wgrad_b3x_kernel with half the matrix instructions: K = 32 = the 32-row tile, a wave's 32 x 32 (ci, co) share of a tap is
-// 2 x 2 tiles x 3 plane products (a1 b2, a2 b1, a1 b1) = 12 MFMAs.  Same circular window, same transposing reads, same row
-// dealing and swizzle, same slabs.
+// 2 x 2 tiles x 3 plane products (a1 b2, a2 b1, a1 b1) = 12 MFMAs.  Same transposing reads, same row dealing, same slabs; the
+// dout tile keeps wgrad_b3x's swizzle, the circular input window is laid out at a fixed pitch with guard slots (H2_WIN_* below),
+// so that a fragment address is one per-lane base plus a wave-uniform slot offset.
 //
 // Scales.  K is the ROW index here and the input window persists from tile to tile, so an operand's power-of-two scale must
 // hold for every row of a wave's MFMA: a workgroup keeps ONE running exponent per operand over its contiguous row range
@@ -730,6 +731,12 @@ struct WgBnBwd {
     float *dc;                        // out: the BatchNorm's input gradient
 };
 
+// The input window of wgrad_h2_kernel: B3_WIN slots of one tensor row each at a fixed pitch, unswizzled, plus 16 guard slots
+// that mirror slots 0 .. 15.  The pitch is the smallest 128 + 8 k at which the transposing reads (per half-wave 8 consecutive
+// rows x 32 bytes, banks of 256 bytes) and the 8-byte stores (16 lanes x 8 bytes of one row, banks of 128 bytes) meet no bank
+// conflict at any start slot: tests/test_wgrad_window_cpu.py searches it.
+constexpr int H2_WIN_GUARD = 16, H2_WIN_SLOTS = B3_WIN + H2_WIN_GUARD, H2_WIN_PITCH = 160;
+
 template <bool INBN, int DOBN>
 __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__restrict__ in, const float *__restrict__ dout,
                                                              float *__restrict__ slabs, float *__restrict__ bias_slabs, Geom g,
@@ -737,12 +744,12 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
                                                              WgBnBwd bb) {
     constexpr int TAPS = 9, CH = 64, TK = 32, ROWB = CH * 2;
     constexpr int NCF = 11;   // coefficient rows kept in LDS: scale, shift, mean, istd, mean_lo, istd_lo, k1, k2, k3, k2_lo, k3_lo
-    constexpr int PLANE_IN = B3_WIN * ROWB, PLANE_DO = TK * ROWB, LPR = CH / 4, RPP = THREADS / LPR;
+    constexpr int PLANE_IN = H2_WIN_SLOTS * H2_WIN_PITCH, PLANE_DO = TK * ROWB, LPR = CH / 4, RPP = THREADS / LPR;
     constexpr int HEAD_IN = 3, HEAD_DO = 1;                                 // binades of headroom kept when an exponent is (re)chosen
     constexpr int NWR = (2 * 47 + RPP - 1) / RPP;                           // passes that cover the window's 2 x halo older rows (W <= 46)
     static_assert(2 * RPP == TK, "a thread stages two pieces of each tensor per tile");
     extern __shared__ __attribute__((aligned(128))) unsigned char smem_w[];
-    unsigned char *in_s = smem_w;                        // [2 planes][B3_WIN rows][64 f16]
+    unsigned char *in_s = smem_w;                        // [2 planes][H2_WIN_SLOTS slots][H2_WIN_PITCH bytes]: 64 f16 + padding
     unsigned char *do_s = in_s + 2 * PLANE_IN;           // [2 planes][32 rows][64 f16]
     float *bred_s = reinterpret_cast<float *>(do_s + 2 * PLANE_DO);   // [RPP][64]
     float *smx = bred_s + RPP * CH;                      // [3][4]: the waves' maxima (new input rows, dout rows, window rows)
@@ -780,14 +787,34 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
         return;
     }
 
-    auto put = [&](unsigned char *plane0, int plane_bytes, int slot, int c4, u32x4 v, float scl) {
+    auto split = [&](u32x4 v, float scl, u32x2 &h1, u32x2 &h2) {
         const float4 f = as_f4(v);
         unsigned a1, a2, b1, b2;
         split2_pair_w(f.x * scl, f.y * scl, a1, a2);
         split2_pair_w(f.z * scl, f.w * scl, b1, b2);
-        unsigned char *dst = plane0 + slot * ROWB + ((c4 * 8) ^ b3x_swz(slot));
-        *reinterpret_cast<u32x2 *>(dst) = u32x2{a1, b1};
-        *reinterpret_cast<u32x2 *>(dst + plane_bytes) = u32x2{a2, b2};
+        h1 = u32x2{a1, b1};
+        h2 = u32x2{a2, b2};
+    };
+    auto put_do = [&](int slot, int c4, u32x4 v, float scl) {   // the dout tile: 128-byte rows, swizzled
+        u32x2 h1, h2;
+        split(v, scl, h1, h2);
+        unsigned char *dst = do_s + slot * ROWB + ((c4 * 8) ^ b3x_swz(slot));
+        *reinterpret_cast<u32x2 *>(dst) = h1;
+        *reinterpret_cast<u32x2 *>(dst + PLANE_DO) = h2;
+    };
+    // The input window: tensor row r lives in slot r mod B3_WIN at a fixed pitch, no swizzle; slots B3_WIN .. B3_WIN + 15 mirror
+    // slots 0 .. 15 (a row whose slot is below 16 is written twice), so 16 consecutive rows from ANY slot are 16 consecutive slots.
+    auto put_in = [&](int row, int c4, u32x4 v, float scl) {
+        u32x2 h1, h2;
+        split(v, scl, h1, h2);
+        const int slot = row & (B3_WIN - 1);
+        unsigned char *dst = in_s + slot * H2_WIN_PITCH + c4 * 8;
+        *reinterpret_cast<u32x2 *>(dst) = h1;
+        *reinterpret_cast<u32x2 *>(dst + PLANE_IN) = h2;
+        if (slot < H2_WIN_GUARD) {
+            *reinterpret_cast<u32x2 *>(dst + B3_WIN * H2_WIN_PITCH) = h1;
+            *reinterpret_cast<u32x2 *>(dst + B3_WIN * H2_WIN_PITCH + PLANE_IN) = h2;
+        }
     };
     const int prow = tid / LPR, pc4 = tid % LPR;
     auto activate = [&](u32x4 v, int row) {
@@ -913,8 +940,9 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
 
     const int gr = lane >> 4, w16 = lane & 15;
     const unsigned lrow = 4 * gr + (w16 >> 2), colb = (w16 & 3) * 8;
-    const unsigned a_col = mtw * 64 + colb, b_col = ntw * 64 + colb;
-    const unsigned a_base = lds_addr(in_s), b_base = lds_addr(do_s);
+    const unsigned b_col = ntw * 64 + colb;
+    const unsigned b_base = lds_addr(do_s);
+    const unsigned a_lane = lds_addr(in_s) + lrow * H2_WIN_PITCH + mtw * 64 + colb;   // + (start slot) * pitch: a fragment address
     const unsigned b_lo = b_base + lrow * ROWB + (b_col ^ b3x_swz(lrow));
     const unsigned b_hi = b_base + (lrow + 16) * ROWB + (b_col ^ b3x_swz(lrow + 16));
 
@@ -966,7 +994,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
 #pragma unroll
             for (int u = 0; u < NWR; ++u) {
                 const int r = prow + RPP * u;
-                if (r < 2 * halo) put(in_s, PLANE_IN, (int)((q0 - halo + r) & (B3_WIN - 1)), pc4, wr[u], scl);
+                if (r < 2 * halo) put_in(q0 - halo + r, pc4, wr[u], scl);
             }
         }
         if (!have || scale_exp_w(m_do) < e_do) {
@@ -990,8 +1018,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int row = q0 + halo + prow + RPP * u;
-                put(in_s, PLANE_IN, (int)(row & (B3_WIN - 1)), pc4, pin[u], s_in);
-                put(do_s, PLANE_DO, prow + RPP * u, pc4, pdo[u], s_do);
+                put_in(row, pc4, pin[u], s_in);
+                put_do(prow + RPP * u, pc4, pdo[u], s_do);
                 bsum += __builtin_bit_cast(f32x4, pdo[u]);
             }
         }
@@ -1002,14 +1030,14 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int p = 0; p < 2; ++p) b[nt][p] = read_tr_frag_h(b_lo ^ (nt * 32), b_hi ^ (nt * 32), p * PLANE_DO);
-        const unsigned s0 = (unsigned)q0 + lrow + B3_WIN;
+        // a tap's two 16-row groups start at wave-uniform slots (scalar unit); neither wraps, thanks to the guard slots
         auto a_frags = [&](int tap, int mt, f16x8 (&a)[2]) {
-            const int sh = (tap / 3 - 1) * g.Wp + (tap % 3 - 1);
-            const unsigned slot_lo = (s0 + (unsigned)sh) & (B3_WIN - 1), slot_hi = (slot_lo + 16) & (B3_WIN - 1);
-            const unsigned cs = (a_col ^ b3x_swz(slot_lo)) ^ (mt * 32);
-            const unsigned a_lo = a_base + ((slot_lo << 7) | cs), a_hi = a_base + ((slot_hi << 7) | cs);
+            const int sh = q0 + (tap / 3 - 1) * g.Wp + (tap % 3 - 1);
+            const unsigned s_lo = __builtin_amdgcn_readfirstlane((unsigned)(sh & (B3_WIN - 1)) * H2_WIN_PITCH);
+            const unsigned s_hi = __builtin_amdgcn_readfirstlane((unsigned)((sh + 16) & (B3_WIN - 1)) * H2_WIN_PITCH);
+            const unsigned a_lo = a_lane + s_lo, a_hi = a_lane + s_hi;
 #pragma unroll
-            for (int p = 0; p < 2; ++p) a[p] = read_tr_frag_h(a_lo, a_hi, p * PLANE_IN);
+            for (int p = 0; p < 2; ++p) a[p] = read_tr_frag_h(a_lo, a_hi, p * PLANE_IN + mt * 32);
         };
         auto mfmas = [&](int tap, int mt, const f16x8 (&a)[2]) {   // smallest terms first: a1 b2, a2 b1, a1 b1
 #define LAD_WH2_TERM(pa, pb) \
@@ -1077,11 +1105,12 @@ int launch_wgrad_h2(const float *in, const float *in_coef, const float *dout, fl
     const int64_t n_tiles = lad::ceil_div(g.rows, TK);
     const int groups = groups_for(n_tiles);
     const int tiles_per_wg = (int)lad::ceil_div(n_tiles, groups);
-    const size_t lds = 2 * B3_WIN * ROWB + 2 * TK * ROWB + (THREADS / (CH / 4)) * CH * sizeof(float) + 12 * sizeof(float) +
+    // 46,080 bytes of window: 58,928 in all without DOBN, 79,408 with it -- two workgroups fit a CU's 160 KiB
+    const size_t lds = 2 * H2_WIN_SLOTS * H2_WIN_PITCH + 2 * TK * ROWB + (THREADS / (CH / 4)) * CH * sizeof(float) + 12 * sizeof(float) +
                        (2 + (DOBN != 0 ? 11 : 0)) * CH * sizeof(float) + (DOBN != 0 ? 256 + 2 * 8192 + 4 * 256 : 0);
     float *slabs = ws;
     float *bias_slabs = ws + (int64_t)MAX_GROUPS * TAPS * CH * CH;
-    static lad::DeviceOnce attr_set;   // (the DOBN variants ask for 66 KB of dynamic LDS: past the 64 KB a kernel gets without opting in)
+    static lad::DeviceOnce attr_set;   // (the DOBN variants ask for 78 KB of dynamic LDS: past the 64 KB a kernel gets without opting in)
     if (!attr_set) {
         LAD_HIP_CHECK(hipFuncSetAttribute((const void *)wgrad_h2_kernel<INBN, DOBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         attr_set = true;
