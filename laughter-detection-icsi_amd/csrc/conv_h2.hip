@@ -169,8 +169,16 @@ __device__ unsigned long long lad_dbg_h2[16 * 16384];
 // no weight ring, eight waves per workgroup, and the diagnostic builds without MFMAs / loads / epilogue / split -- lives in
 // tools/experiments/retired/conv_h2_variants.hip (tools/exp_h2.sh builds it into a library of its own); all of them run in
 // 0.49-0.57 ms per launch at batch 512 (profiles/r04_conv_h2_experiments.log, profiles/r05_conv_h2_8waves.log).
+//
+// EPI: the epilogue options of the launch as compile-time constants (h2_epi(...): h2_epilogue of lad_b3_tile.h, one instantiation
+// per form the training engine launches -- the LAD_H2_FORM list of launch_h2_rb), or H2_EPI_ANY: the shared b3_epilogue with its run-time null tests, for
+// every other combination of arguments lad_conv_h2 accepts.  Same bits either way.
 constexpr int NSLOT = 3;   // ring slots: the LDS-DMA runs two taps ahead of the MFMAs
-template <int C, int RB, bool STAT, bool INBN>
+constexpr int H2_EPI_ANY = -1;
+constexpr int h2_epi(bool bias, int addend, bool partials, bool from_bits) {
+    return (bias ? 1 : 0) | (addend << 1) | (partials ? 8 : 0) | (from_bits ? 16 : 0);
+}
+template <int C, int RB, bool STAT, bool INBN, int EPI>
 __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_h2_kernel(const float *__restrict__ in, const unsigned char *__restrict__ wt,
                                                              const float *__restrict__ bias, const float *addend,
                                                              const unsigned long long *__restrict__ abits, float *out,
@@ -199,14 +207,16 @@ __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_h2_kernel(const
     if (q0 >= g.rows) return;
 
     LAD_H2_STAMP(0)
-    const int nw_tap = dma_per_tap<TAP_BYTES>(wave);
+    // a tap is a whole number of THREADS x 16 bytes: every wave issues the same NW_TAP DMAs per tap, whatever its number, and the
+    // counted waits below are immediates
+    constexpr int NW_TAP = TAP_BYTES / (THREADS * 16);
+    static_assert(TAP_BYTES % (THREADS * 16) == 0 && NW_TAP >= 1, "the DMA count per tap must not depend on the wave");
     auto issue_tap = [&](int tap, int stage, int slot) {
         const unsigned char *src = wt + (int64_t)(tap * NSTAGE + stage) * TAP_BYTES;
         unsigned char *dst = b_s + slot * TAP_BYTES;
 #pragma unroll
-        for (int r = 0; r * THREADS * 16 < TAP_BYTES; ++r)
-            if ((r * THREADS + wave * 64) * 16 < TAP_BYTES)   // wave-uniform
-                dma16(src + (r * THREADS + tid) * 16, lds_addr(dst + (r * THREADS + wave * 64) * 16));
+        for (int r = 0; r < NW_TAP; ++r)
+            dma16(src + (r * THREADS + tid) * 16, lds_addr(dst + (r * THREADS + wave * 64) * 16));
     };
     const int *wexp = reinterpret_cast<const int *>(wt + K::IMG_BYTES);
 
@@ -303,7 +313,9 @@ __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_h2_kernel(const
 #pragma unroll
         for (int c = 0; c < NCT; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#pragma unroll 1
+    // The stages are straight-line code (NSTAGE is 2 or 1): `last` and the tap's wait are constants in every unrolled tap, where a
+    // rolled loop tested them at run time (about 100 scalar branches between the first and the last MFMA of a stage).
+#pragma unroll
     for (int stage = 0; stage < NSTAGE; ++stage) {
         const bool last = stage + 1 == NSTAGE;
 #pragma unroll
@@ -314,11 +326,11 @@ __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_h2_kernel(const
                 // tap kc has landed (this wave's part), then everybody's; the slot of tap kc - 1 is free
                 constexpr int YOUNGER = NSLOT - 2;
                 if (!last) {
-                    if (kc > KP && kc <= KP + NSLOT - 1) wait_dma<YOUNGER, NPRE>(nw_tap);   // + the requested rows
-                    else wait_dma<YOUNGER, 0>(nw_tap);
+                    if (kc > KP && kc <= KP + NSLOT - 1) wait_dma_fixed<YOUNGER, NPRE, NW_TAP>();   // + the requested rows
+                    else wait_dma_fixed<YOUNGER, 0, NW_TAP>();
                 } else {
-                    if (CPS - 1 - kc >= YOUNGER) wait_dma<YOUNGER, 0>(nw_tap);
-                    else wait_dma<0, 0>(nw_tap);
+                    if (CPS - 1 - kc >= YOUNGER) wait_dma_fixed<YOUNGER, 0, NW_TAP>();
+                    else wait_dma_fixed<0, 0, NW_TAP>();
                 }
                 __syncthreads();
                 const int kn = kc + NSLOT - 1;
@@ -397,7 +409,11 @@ __global__ __launch_bounds__(THREADS, RB == 1 ? 3 : 2) void conv_h2_kernel(const
                     for (int j = 0; j < 4; ++j)
                         my[(rr * 16 + (lane >> 4) * 4 + j) * (C + 4) + c * 16 + m] = __builtin_ldexpf(acc[rb * 2 + rr][c][j], -ktot);
         };
-        b3_epilogue<C, STAT>(store_acc, bias, addend, abits, out, partials, mask_s + rb * TM, reinterpret_cast<float *>(smem_b), qs, g.rows, bst);
+        if constexpr (EPI == H2_EPI_ANY)
+            b3_epilogue<C, STAT>(store_acc, bias, addend, abits, out, partials, mask_s + rb * TM, reinterpret_cast<float *>(smem_b), qs, g.rows, bst);
+        else
+            h2_epilogue<C, STAT, (EPI & 1) != 0, (EPI >> 1) & 3, (EPI & 8) != 0, (EPI & 16) != 0>(
+                store_acc, bias, addend, abits, out, partials, mask_s + rb * TM, reinterpret_cast<float *>(smem_b), qs, g.rows, bst);
     }
     LAD_H2_STAMP(12)
 }
@@ -438,27 +454,66 @@ bool g_h2_ws = h2_ws_from_env();   // (experiment builds: LAD_H2_WS=0 keeps the 
 
 #endif
 
+struct H2Args {
+    const float *in, *in_coef;
+    const unsigned char *wt;
+    const float *bias, *addend;
+    const unsigned long long *abits;
+    float *out, *partials;
+    B3Stat bst;
+    Geom g;
+    hipStream_t stream;
+};
+
+template <int C, int RB, bool STAT, bool INBN, int EPI>
+int launch_h2_form(const H2Args &a) {
+    static lad::DeviceOnce attr_set;
+    if (!attr_set) {
+        LAD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_h2_kernel<C, RB, STAT, INBN, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_set = true;
+    }
+    const int64_t tiles = ceil_div(a.g.rows, TM * RB);
+    hipLaunchKernelGGL((conv_h2_kernel<C, RB, STAT, INBN, EPI>), dim3((unsigned)(ceil_div(tiles, 8) * 8)), dim3(THREADS), (h2_lds_bytes<C, RB>(a.g)),
+                       a.stream, a.in, a.wt, a.bias, a.addend, a.abits, a.out, a.partials, a.g, a.bst, a.in_coef);
+    return check_launch("conv_h2_kernel");
+}
+
+// The forms with an epilogue of their own = what the training engine launches (engine.py, _conv_s1):
+//   forward: bias + partials (+ addend), with or without the input BatchNorm;
+//   data gradient: nothing, a plain addend, a gated addend;
+//   data gradient with the BatchNorm sums: mask from x, mask from sign bits with a gated addend.
+// Everything else lad_conv_h2 accepts runs the shared epilogue (H2_EPI_ANY): same bits, with its run-time tests -- a form the engine
+// starts to launch wants a line here (engine.py has the matching note at _conv_s1).
+template <int C, int RB, bool STAT, bool INBN>
+int launch_h2_rb(const H2Args &a) {
+    const int form = h2_epi(a.bias != nullptr, a.addend == nullptr ? H2_ADD_NONE : a.abits == nullptr ? H2_ADD_PLAIN : H2_ADD_GATED,
+                            a.partials != nullptr, STAT && a.bst.bits != nullptr);
+#define LAD_H2_FORM(...)                                                                                                           \
+    if (form == h2_epi(__VA_ARGS__)) return launch_h2_form<C, RB, STAT, INBN, h2_epi(__VA_ARGS__)>(a);
+    if constexpr (STAT) {
+        LAD_H2_FORM(false, H2_ADD_NONE, true, false)
+        LAD_H2_FORM(false, H2_ADD_GATED, true, true)
+    } else {
+        LAD_H2_FORM(true, H2_ADD_NONE, true, false)
+        LAD_H2_FORM(true, H2_ADD_PLAIN, true, false)
+        if constexpr (!INBN) {
+            LAD_H2_FORM(false, H2_ADD_NONE, false, false)
+            LAD_H2_FORM(false, H2_ADD_PLAIN, false, false)
+            LAD_H2_FORM(false, H2_ADD_GATED, false, false)
+        }
+    }
+#undef LAD_H2_FORM
+    return launch_h2_form<C, RB, STAT, INBN, H2_EPI_ANY>(a);
+}
+
 template <int C, bool STAT, bool INBN>
 int launch_h2(const float *in, const float *in_coef, const void *wt, const float *bias, const float *addend, const uint64_t *abits,
               float *out, float *partials, const B3Stat &bst, int64_t batch, int32_t H, int32_t W, void *stream, const char *who) {
     const Geom g = make_geom(batch, H, W);
     LAD_REQUIRE(g.rows < ((int64_t)1 << 31) && g.img < (1 << 20), "%s: more than 2^31 rows, or an image of more than 2^20 positions", who);
     LAD_REQUIRE(W <= 46, "%s: image too wide for the tile (W = %d)", who, W);
-#define LAD_H2_LAUNCH(RB)                                                                                                          \
-    {                                                                                                                              \
-        static lad::DeviceOnce attr_set;                                                                                              \
-        if (!attr_set) {                                                                                                           \
-            LAD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_h2_kernel<C, RB, STAT, INBN>,                                     \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                             \
-            attr_set = true;                                                                                                       \
-        }                                                                                                                          \
-        const int64_t tiles = ceil_div(g.rows, TM * RB);                                                                           \
-        hipLaunchKernelGGL((conv_h2_kernel<C, RB, STAT, INBN>), dim3((unsigned)(ceil_div(tiles, 8) * 8)), dim3(THREADS),           \
-                           (h2_lds_bytes<C, RB>(g)), (hipStream_t)stream, in, (const unsigned char *)wt, bias, addend,             \
-                           (const unsigned long long *)abits, out, partials, g, bst, in_coef);                                    \
-        return check_launch("conv_h2_kernel");                                                                                     \
-    }
-    if (ceil_div(g.rows, TM * 2) < h2_two_rounds()) LAD_H2_LAUNCH(1)
+    const H2Args a{in, in_coef, (const unsigned char *)wt, bias, addend, (const unsigned long long *)abits, out, partials, bst, g, (hipStream_t)stream};
+    if (ceil_div(g.rows, TM * 2) < h2_two_rounds()) return launch_h2_rb<C, 1, STAT, INBN>(a);
 #ifdef LAD_H2_WS_BUILD
     if constexpr (C == 64) {
         if (g_h2_ws) {   // wave-specialised persistent workgroups, one per CU (conv_h2w_kernel)
@@ -475,8 +530,7 @@ int launch_h2(const float *in, const float *in_coef, const void *wt, const float
         }
     }
 #endif
-    LAD_H2_LAUNCH(2)
-#undef LAD_H2_LAUNCH
+    return launch_h2_rb<C, 2, STAT, INBN>(a);
 }
 }  // namespace
 

@@ -161,6 +161,131 @@ __device__ __forceinline__ void b3_epilogue(StoreAcc store_acc, const float *__r
     }
 }
 
+// conv_h2.hip's own entry: b3_epilogue without SCATTER / ASMBAR and with the options a launch was given as template parameters
+// instead of run-time null tests inside the unrolled row loops (ISA of conv_h2_kernel<64, 2, false, false>: about 200 branches
+// after the last MFMA, most of them these tests).  The arithmetic, its order and the LDS traffic are those of b3_epilogue, line
+// for line -- `+ bias` without a bias still adds +0 (it turns a -0 accumulator into +0, as the shared entry does) -- so `out` and
+// `partials` keep their bits (tests/test_conv_h2_epilogue_gpu.py).
+// ADDEND: H2_ADD_NONE, H2_ADD_PLAIN (out = ... + addend), H2_ADD_GATED (... + addend * [sign bit]).  FROM_BITS (STAT only): the
+// consuming BatchNorm's ReLU decisions come from B3Stat::bits.
+enum : int { H2_ADD_NONE = 0, H2_ADD_PLAIN = 1, H2_ADD_GATED = 2 };
+template <int C, bool STAT, bool HAS_BIAS, int ADDEND, bool HAS_PARTIALS, bool FROM_BITS, class StoreAcc>
+__device__ __forceinline__ void h2_epilogue(StoreAcc store_acc, const float *__restrict__ bias, const float *addend,
+                                            const unsigned long long *__restrict__ abits, float *out, float *__restrict__ partials,
+                                            const unsigned char *mask_tile, float *out_s, int64_t q0, int64_t rows, const B3Stat &bst) {
+    static_assert(!FROM_BITS || STAT, "sign bits of the consuming BatchNorm: STAT launches only");
+    static_assert(!STAT || HAS_PARTIALS, "the BatchNorm sums need partials");
+    constexpr int LDO = C + 4, LPR = C / 4, RPI = 64 / LPR, ITER = 32 / RPI, STEP = RPI * C * 4;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float *my = out_s + wave * 32 * LDO;
+    store_acc(my);   // the wave's 32 x C tile, row-major with leading dimension LDO
+    const int c4 = lane % LPR, rsub = lane / LPR;
+    const int64_t tile_rows = rows - q0;
+    const int64_t tile_bytes = tile_rows * (C * 4);
+    const int voff = ((wave * 32 + rsub) * C + c4 * 4) * 4;
+    const int woff = (wave * 32 + rsub) * 8;   // sign-bit words: 8 bytes per row
+    const __amdgpu_buffer_rsrc_t out_r = make_rsrc(out + q0 * C, tile_bytes);
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (HAS_BIAS) bv = *reinterpret_cast<const f32x4 *>(bias + c4 * 4);
+    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
+    f32x4 fsc = s1, fsh = s1, mu = s1, is = s1, mul = s1, isl = s1;
+    if constexpr (STAT) {
+        if constexpr (!FROM_BITS) {
+            fsc = *reinterpret_cast<const f32x4 *>(bst.coef + 0 * C + c4 * 4);
+            fsh = *reinterpret_cast<const f32x4 *>(bst.coef + 1 * C + c4 * 4);
+        }
+        mu = *reinterpret_cast<const f32x4 *>(bst.coef + 2 * C + c4 * 4);
+        is = *reinterpret_cast<const f32x4 *>(bst.coef + 3 * C + c4 * 4);
+        mul = *reinterpret_cast<const f32x4 *>(bst.coef + 4 * C + c4 * 4);
+        isl = *reinterpret_cast<const f32x4 *>(bst.coef + 5 * C + c4 * 4);
+    }
+    auto gate = [&](u32x4 v, u32x2 w) {   // v * [sign bit of its channel] (lad_bn_math.h: mask_from_bits)
+        const unsigned lo = w.x >> c4, hi = w.y >> c4;
+        v.x = (lo & 1u) ? v.x : 0u;
+        v.y = (lo & 0x10000u) ? v.y : 0u;
+        v.z = (hi & 1u) ? v.z : 0u;
+        v.w = (hi & 0x10000u) ? v.w : 0u;
+        return v;
+    };
+    // chunks of NI wave-instructions, as in b3_epilogue: two chunks for STAT (168 registers at three workgroups per CU) -- and for a
+    // gated addend, whose 16 + 8 bytes per row in flight next to the second pass's accumulators would spill otherwise (with the
+    // options known, the compiler requests the chunk's tensors under the last MFMAs).  The rows keep their order.
+    constexpr int NI = (STAT || ADDEND == H2_ADD_GATED) ? ITER / 2 : ITER;
+#pragma unroll
+    for (int i0 = 0; i0 < ITER; i0 += NI) {
+        u32x4 adv[ADDEND != H2_ADD_NONE ? NI : 1], bx[STAT ? NI : 1];
+        u32x2 wv[ADDEND == H2_ADD_GATED ? NI : 1], bw[FROM_BITS ? NI : 1];
+        if constexpr (ADDEND != H2_ADD_NONE) {
+            const __amdgpu_buffer_rsrc_t add_r = make_rsrc(addend + q0 * C, tile_bytes);
+#pragma unroll
+            for (int u = 0; u < NI; ++u) adv[u] = buf_load16(add_r, voff + (i0 + u) * STEP);
+            if constexpr (ADDEND == H2_ADD_GATED) {
+                const __amdgpu_buffer_rsrc_t bits_r = make_rsrc(abits + q0, tile_rows * 8);
+#pragma unroll
+                for (int u = 0; u < NI; ++u) wv[u] = buf_load8(bits_r, woff + (i0 + u) * RPI * 8);
+            }
+        }
+        if constexpr (STAT) {
+            const __amdgpu_buffer_rsrc_t x_r = make_rsrc(bst.x + q0 * C, tile_bytes);
+#pragma unroll
+            for (int u = 0; u < NI; ++u) bx[u] = buf_load16(x_r, voff + (i0 + u) * STEP);
+            if constexpr (FROM_BITS) {
+                const __amdgpu_buffer_rsrc_t w_r = make_rsrc(bst.bits + q0, tile_rows * 8);
+#pragma unroll
+                for (int u = 0; u < NI; ++u) bw[u] = buf_load8(w_r, woff + (i0 + u) * RPI * 8);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NI; ++u) {
+            const int it = i0 + u;
+            const int row = it * RPI + rsub;
+            const float keep = (float)mask_tile[wave * 32 + row];   // 1 on interior rows, 0 on border rows
+            f32x4 t = *reinterpret_cast<const f32x4 *>(my + row * LDO + c4 * 4);
+            t += bv;
+            if constexpr (ADDEND == H2_ADD_GATED) t += __builtin_bit_cast(f32x4, gate(adv[u], wv[u]));
+            else if constexpr (ADDEND == H2_ADD_PLAIN) t += __builtin_bit_cast(f32x4, adv[u]);
+            t *= keep;
+            buf_store16(__builtin_bit_cast(u32x4, t), out_r, voff + it * STEP);
+            if constexpr (!STAT) {   // (sum, sum of squares) of the output
+                if constexpr (HAS_PARTIALS) {
+                    s1 += t;
+                    s2 = __builtin_elementwise_fma(t, t, s2);
+                }
+            } else {                 // the arithmetic of bn_bwd_reduce_kernel (bn.hip)
+                const f32x4 xv = __builtin_bit_cast(f32x4, bx[u]);
+                f32x4 d;
+                if constexpr (FROM_BITS) {
+                    d = __builtin_bit_cast(f32x4, gate(__builtin_bit_cast(u32x4, t), bw[u]));
+                } else {
+                    const f32x4 yv = __builtin_elementwise_fma(xv, fsc, fsh);   // the fmaf the forward pass evaluated (mask_from_x)
+                    d.x = yv.x > 0.f ? t.x : 0.f;
+                    d.y = yv.y > 0.f ? t.y : 0.f;
+                    d.z = yv.z > 0.f ? t.z : 0.f;
+                    d.w = yv.w > 0.f ? t.w : 0.f;
+                }
+                const f32x4 tx = (xv - mu) - mul;
+                const f32x4 xh = __builtin_elementwise_fma(tx, is, tx * isl);   // xhat1 (lad_bn_math.h)
+                s1 += d;
+                s2 = __builtin_elementwise_fma(d, xh, s2);
+            }
+        }
+    }
+    if constexpr (HAS_PARTIALS) {
+        *reinterpret_cast<f32x4 *>(my + (rsub * 2 + 0) * C + c4 * 4) = s1;
+        *reinterpret_cast<f32x4 *>(my + (rsub * 2 + 1) * C + c4 * 4) = s2;
+        __syncthreads();
+        if (tid < 2 * C) {
+            const int k = tid / C, co = tid - k * C;
+            float s = 0.0f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int rs = 0; rs < RPI; ++rs) s += out_s[w * 32 * LDO + (rs * 2 + k) * C + co];
+            partials[(q0 / TM * 2 + k) * C + co] = s;
+        }
+    }
+}
+
 // LDS-DMA wave-instructions this wave issues per tap (issue_tap below): wave-uniform
 template <int TAP_BYTES>
 __device__ __forceinline__ int dma_per_tap(int wave) {
@@ -177,6 +302,12 @@ __device__ __forceinline__ void wait_dma(int nw_tap) {
     if (nw_tap == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TAPS_YOUNGER + EXTRA) : "memory");
     else if (nw_tap == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TAPS_YOUNGER + EXTRA) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EXTRA) : "memory");
+}
+// the same wait where every wave issues the same NW_TAP DMAs per tap (a tap is a whole number of THREADS x 16 bytes): no branch
+template <int TAPS_YOUNGER, int EXTRA, int NW_TAP>
+__device__ __forceinline__ void wait_dma_fixed() {
+    static_assert(NW_TAP * TAPS_YOUNGER + EXTRA <= 63, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW_TAP * TAPS_YOUNGER + EXTRA) : "memory");
 }
 
 }  // namespace b3t

@@ -898,7 +898,9 @@ class ResNetEngine:
         with the flipped / transposed image (GEMM K = cout, N = cin).  in_coef: BatchNorm + ReLU of the input, applied while staging;
         addend (+ abits: gated by sign bits) is added to the result; bn = (x, mask, coef) of the BatchNorm whose backward consumes
         `out`: its first pass rides in the epilogue and leaves per-tile sums in `partials` (mask None: ReLU decisions recomputed from
-        x; int64: sign bits; float: the BatchNorm's output y)."""
+        x; int64: sign bits; float: the BatchNorm's output y).
+        lad_conv_h2 has an epilogue compiled for each combination of options launched from here (csrc/conv_h2.hip, the LAD_H2_FORM list of
+        launch_h2_rb); any other combination runs the shared epilogue with run-time tests -- same results, slower: a new form wants a line there."""
         bx, bmask, bcoef = bn if bn is not None else (None, None, None)
         fn = conv_s1_entry(arith, cs.cin, in_coef is not None, abits is not None,
                            None if bn is None else "x" if bmask is None else "bits" if bmask.dtype == torch.int64 else "y")
