@@ -9,18 +9,19 @@
 // scaling is needed for gradients of 1e-8).  A product is then a1 b1 + a1 b2 + a2 b1 + a1 b3 + a2 b2 + a3 b1 (+ terms
 // below 2^-24 of it, dropped): six v_mfma_f32_32x32x16_bf16 with f32 accumulation, each product exact in f32.  Measured
 // against float64 this is as accurate as the fmaf chain of the f32 MFMA (2.9e-7 vs 4.4e-7 of the largest output over
-// K = 576), at 6 / 16 of its matrix-core time.  Tensors arrive pre-split ("split3": [C/16 groups][rows][plane][16 bf16],
-// 6 bytes per element, lad_split3), weights are split when they are packed.
+// K = 576), at 6 / 16 of its matrix-core time.  Tensors are the fp32 tensors of the f32 kernels: their rows are split while
+// they are staged; weights are split when they are packed.
 //
-// Structure = conv_s1_kernel (conv_mfma.hip): a workgroup owns 128 consecutive output rows and all 64 output channels;
-// the input rows it needs (+ a halo of W+2 either side) are staged into LDS 32 channels (x 3 planes) at a time through a
-// buffer resource; the packed weight image streams chunk by chunk (one tap x 32 channels x 3 planes = 12 KB) through a
-// two-slot LDS ring by LDS-DMA, one chunk ahead of the MFMAs.  Epilogue: bias, optional addend, zero border rows,
+// Structure = conv_s1_kernel (conv_mfma.hip): a workgroup owns 256 consecutive output rows and all 64 output channels;
+// the input rows it needs (+ a halo of W+2 either side) are staged into LDS 16 channels (x 3 planes) at a time through a
+// buffer resource; the packed weight image streams tap by tap (one tap x 16 channels x 3 planes = 6 KB) through a
+// two-slot LDS ring by LDS-DMA, one tap ahead of the MFMAs.  Epilogue: bias, optional addend, zero border rows,
 // per-tile (sum, sum of squares) for the train-mode BatchNorm -- the same f32 output tensor as the f32 kernel.
 #include "lad_common.h"
 #include "lad_device.h"
 #include "lad_b3.h"
 #include "lad_b3_tile.h"
+#include "lad_bn_math.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -31,7 +32,6 @@ using namespace lad;
 // C = input = output channels: 64 (block1, the kernel this file was written for) or 32 (block2's stride-1 convolutions) -- a
 // template parameter of everything below; the comments quote the 64-channel figures.
 using namespace lad::b3t;   // TAPS, TM, THREADS, B3Stat, B3Scatter, b3_epilogue, dma_per_tap, wait_dma: lad_b3_tile.h
-constexpr int GROW_B = 3 * 16 * 2;          // bytes of one row of one 16-channel group in HBM: [plane][16 bf16]
 template <int C>
 struct Ch {
     static constexpr int NT = C / 32;                          // 32-column output tiles per wavefront
@@ -39,22 +39,8 @@ struct Ch {
     static constexpr int IMG_BYTES = TAPS * (C / 16) * G16_BYTES;   // packed weight image: [tap][c16 group][...]
 };
 
-// KC = input channels per stage (resident in LDS at a time) = channels per weight chunk.  16: 37 KB of LDS, four
-// workgroups per CU; 32: 73 KB, two.
-template <int C, int KC, int RB = 1>
-struct Cfg {
-    static constexpr int NSTAGE = C / KC;
-    static constexpr int NG = KC / 16;                    // 16-channel groups per chunk
-    static constexpr int ROWB_L = 3 * KC * 2 + 16;        // bytes per staged row in LDS: 3 planes x KC bf16 + 16 (conflict-free b128)
-    static constexpr int PIECES = 3 * KC * 2 / 16;        // 16-byte pieces per staged row
-    static constexpr int CHUNK_BYTES = NG * Ch<C>::G16_BYTES;
-    static constexpr int NCHUNK = TAPS * NSTAGE;
-    static constexpr int TMW = TM * RB;                   // output rows per workgroup: RB row blocks of 32 per wavefront
-    static constexpr int PRE = ((TMW + 2 * 47) * PIECES + THREADS - 1) / THREADS;   // registers for one stage at the widest image (W = 46)
-};
-
 // ---- weights: (cout, cin, 3, 3) fp32 -> [tap][16-channel group][plane][ntile][k half g][n][8 bf16] ----------------------
-// (a chunk of the kernel = KC / 16 consecutive groups of one tap.)
+// (a chunk of the kernel = one 16-channel group of one tap.)
 // mode 0: forward, GEMM K = cin, N = cout.  mode 1: data gradient, K = cout, N = cin, taps flipped (as repack_kernel).
 template <int C>
 __global__ void pack_b3_kernel(const float *__restrict__ w, unsigned short *__restrict__ wt, int mode) {
@@ -84,37 +70,24 @@ __global__ void pack_b3_kernel(const float *__restrict__ w, unsigned short *__re
 }
 
 // ---- the convolution ----------------------------------------------------------------------------------------------
-template <int C, int KC>
-__device__ __forceinline__ void issue_chunk(const unsigned char *__restrict__ wt, unsigned char *slot, int tap, int stage, int tid, int wave) {
-    using K = Cfg<C, KC>;
-    const unsigned char *src = wt + (int64_t)(tap * (C / 16) + stage * K::NG) * Ch<C>::G16_BYTES;
-    static_assert(K::CHUNK_BYTES % (64 * 16) == 0, "whole wave-instructions");
-#pragma unroll
-    for (int r = 0; r * THREADS * 16 < K::CHUNK_BYTES; ++r)
-        if ((r * THREADS + wave * 64) * 16 < K::CHUNK_BYTES)   // wave-uniform
-            dma16(src + (r * THREADS + tid) * 16, lds_addr(slot + (r * THREADS + wave * 64) * 16));
-}
-
-// (The round-2 kernel conv_b3_kernel -- v_mfma_f32_32x32x16_bf16, rolled taps, 16-channel stages -- and the ring / chunk variants of
-// conv_b3x_kernel below other than (1 tap per chunk, 2 slots) are in tools/experiments/retired/conv_b3_variants.hip: round 5.)
-template <int C, int TPC, int NSLOT>
+// `in`: fp32 rows [rows][C] (layout: lad_device.h), staged 16 channels at a time and split into the three planes on the way to
+// LDS.  The packed weights stream one tap x 16 channels (6 KB) at a time through a two-slot LDS ring, one tap ahead of the MFMAs.
+// (The round-2 kernel conv_b3_kernel -- v_mfma_f32_32x32x16_bf16, rolled taps, pre-split input tensors -- and the other ring / chunk
+// geometries of this kernel are in tools/experiments/retired/conv_b3_variants.hip: round 5.)
+template <int C>
 struct CfgX {
     static constexpr int RB = 2, KC = 16;
+    static constexpr int NSLOT = 2;                           // ring slots
+    static constexpr int TPC = 1;                             // taps requested per barrier (see the loops over it in the kernel)
     static constexpr int NSTAGE = C / KC;
     static constexpr int NCT = C / 16;                        // 16-column tiles
     static constexpr int ROWB = 3 * KC * 2;                   // bytes per staged row: [plane][16 bf16]
-    static constexpr int PIECES = ROWB / 16;
     static constexpr int TAP_BYTES = Ch<C>::G16_BYTES;        // weights of one tap x 16 channels: [plane][ntile][k half][n][8 bf16]
     static constexpr int PLANE_B = Ch<C>::NT * 1024;          // bytes per plane of it
-    static constexpr int CHUNK_BYTES = TPC * TAP_BYTES;
-    static constexpr int CPS = TAPS / TPC;                    // chunks per stage
-    static constexpr int NCH = NSTAGE * CPS;
     static constexpr int TMW = TM * RB;
-    static constexpr int KP = (CPS - NSLOT) < CPS / 2 ? (CPS - NSLOT) : CPS / 2;   // chunk boundary after which the next stage's rows are requested
-    static_assert(TAPS % TPC == 0 && NSLOT >= 2 && NSLOT <= CPS && KP >= 0, "ring geometry");
-    static constexpr int FPIECES = KC * 4 / 16;
-    static constexpr int PRE = ((TMW + 2 * 47) * PIECES + THREADS - 1) / THREADS;
-    static constexpr int PREF = ((TMW + 2 * 47) * FPIECES + THREADS - 1) / THREADS;
+    static constexpr int KP = TAPS / 2;                       // tap after whose barrier the next stage's rows are requested
+    static constexpr int FPIECES = KC * 4 / 16;               // 16-byte pieces (4 fp32 channels) per row and stage
+    static constexpr int NPRE = ((TMW + 2 * 47) * FPIECES + THREADS - 1) / THREADS;   // registers for one stage at the widest image (W = 46)
 };
 
 #ifdef LAD_STAMP
@@ -126,61 +99,54 @@ __device__ unsigned long long lad_dbg_b3x[16 * 16384];
 #define LAD_B3X_STAMP(k)
 #endif
 
-// (a chunk of three taps needs 70 KB of LDS = two workgroups per CU anyway: that variant may use 256 registers)
-template <int C, bool F32IN, bool STAT, bool INBN, int TPC, int NSLOT>
-__global__ __launch_bounds__(THREADS, TPC == 3 ? 2 : 3) void conv_b3x_kernel(const unsigned char *__restrict__ in, const unsigned char *__restrict__ wt,
+template <int C, bool STAT, bool INBN>
+__global__ __launch_bounds__(THREADS, 3) void conv_b3x_kernel(const float *__restrict__ in, const unsigned char *__restrict__ wt,
                                                               const float *__restrict__ bias, const float *addend,
                                                               const unsigned long long *__restrict__ abits, float *out,
                                                               float *__restrict__ partials, Geom g, B3Stat bst,
                                                               const float *__restrict__ in_coef) {
-    static_assert(!INBN || F32IN, "the input BatchNorm is applied to fp32 rows");
-    using K = CfgX<C, TPC, NSLOT>;
-    constexpr int ROWB = K::ROWB, PIECES = K::PIECES, NSTAGE = K::NSTAGE, NCT = K::NCT, KC = K::KC, TMW = K::TMW;
-    constexpr int TAP_BYTES = K::TAP_BYTES, CHUNK_BYTES = K::CHUNK_BYTES, CPS = K::CPS, PLANE_B = K::PLANE_B;
-    constexpr int FPIECES = K::FPIECES, NPRE = F32IN ? K::PREF : K::PRE;
-    constexpr bool STATIC_SLOT = (CPS % NSLOT) == 0;   // a stage starts in slot 0: every slot index is a compile-time number
+    using K = CfgX<C>;
+    constexpr int ROWB = K::ROWB, NSTAGE = K::NSTAGE, NCT = K::NCT, KC = K::KC, TMW = K::TMW, NSLOT = K::NSLOT, TPC = K::TPC;
+    constexpr int TAP_BYTES = K::TAP_BYTES, PLANE_B = K::PLANE_B, FPIECES = K::FPIECES, NPRE = K::NPRE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int halo = g.Wp + 1;
     const int nrows = TMW + 2 * halo;
-    const int main_bytes = max(NSLOT * CHUNK_BYTES + nrows * ROWB, TM * (C + 4) * 4);
-    unsigned char *b_s = smem_b;                          // [NSLOT][CHUNK_BYTES]
-    unsigned char *a_s = b_s + NSLOT * CHUNK_BYTES;       // [nrows][ROWB]
+    const int main_bytes = max(NSLOT * TAP_BYTES + nrows * ROWB, TM * (C + 4) * 4);
+    unsigned char *b_s = smem_b;                          // [NSLOT][TAP_BYTES]
+    unsigned char *a_s = b_s + NSLOT * TAP_BYTES;         // [nrows][ROWB]
     unsigned char *mask_s = smem_b + main_bytes;          // [TMW] (bytes: with a float mask the third ring slot would cost the third workgroup per CU)
-    // XCD-aware tile order (see conv_b3_kernel)
+    // XCD-aware tile order: workgroups are dealt to the 8 XCDs round-robin (workgroup w runs on XCD w % 8) and neighbouring tiles
+    // share halo rows -- and every 128-byte line of the fp32 rows is wanted by two channel stages.  XCD x therefore takes the
+    // contiguous tile range [x * per_x, (x + 1) * per_x): what one of its workgroups fetched is in ITS L2 when the neighbour asks.
     const unsigned per_x = (gridDim.x + 7u) / 8u;
     const unsigned tile_id = (blockIdx.x % 8u) * per_x + blockIdx.x / 8u;
     const int64_t q0 = (int64_t)tile_id * TMW;
-    if (q0 >= g.rows) return;
+    if (q0 >= g.rows) return;   // (the grid is rounded up to a multiple of 8: whole-workgroup exit)
 
     LAD_B3X_STAMP(0)
     const int nw_tap = dma_per_tap<TAP_BYTES>(wave);
-    // weights of (tap, stage) -> ring slot `slot`, sub-chunk tap % TPC
+    // weights of (tap, stage) -> ring slot `slot`
     auto issue_tap = [&](int tap, int stage, int slot) {
         const unsigned char *src = wt + (int64_t)(tap * (C / 16) + stage) * TAP_BYTES;
-        unsigned char *dst = b_s + slot * CHUNK_BYTES + (tap % TPC) * TAP_BYTES;
+        unsigned char *dst = b_s + slot * TAP_BYTES;
 #pragma unroll
         for (int r = 0; r * THREADS * 16 < TAP_BYTES; ++r)
             if ((r * THREADS + wave * 64) * 16 < TAP_BYTES)   // wave-uniform
                 dma16(src + (r * THREADS + tid) * 16, lds_addr(dst + (r * THREADS + wave * 64) * 16));
     };
 
-    // ---- staging of the input rows (as conv_b3_kernel; rows of 96 bytes) ------------------------------------------------
+    // ---- staging: piece idx = u * THREADS + tid = 16 bytes (4 channels) of row idx >> 2 of the stage's 64 bytes; LDS rows of 96 bytes
     const int64_t start = q0 - halo;
     const int64_t first = start < 0 ? 0 : start;
     const int row_lo = (int)(first - start);
     const int64_t span_rows = min(g.rows - first, (int64_t)(nrows - row_lo));
-    const int64_t span_bytes = span_rows * GROW_B;
-    const int64_t group_bytes = g.rows * GROW_B;
-    const int vbase = tid * 16 - row_lo * GROW_B;
-    auto voff = [&](int u) { return (u * THREADS + tid) < nrows * PIECES ? vbase + u * THREADS * 16 : -1; };
-    auto voff_f = [&](int u) {
+    auto voff = [&](int u) {
         const int idx = u * THREADS + tid;
         return idx < nrows * FPIECES ? ((idx >> 2) - row_lo) * (C * 4) + (idx & 3) * 16 : -1;
     };
     auto stage_rsrc = [&](int stage) {
-        return F32IN ? make_rsrc(in + first * (C * 4) + stage * (KC * 4), span_rows * (C * 4) - stage * (KC * 4))
-                     : make_rsrc(in + stage * group_bytes + first * GROW_B, span_bytes);
+        return make_rsrc(reinterpret_cast<const unsigned char *>(in) + first * (C * 4) + stage * (KC * 4), span_rows * (C * 4) - stage * (KC * 4));
     };
     unsigned keep_bits = 0;
     f32x4 bn_sc = {0.f, 0.f, 0.f, 0.f}, bn_sh = bn_sc;
@@ -192,41 +158,31 @@ __global__ __launch_bounds__(THREADS, TPC == 3 ? 2 : 3) void conv_b3x_kernel(con
     };
     auto put = [&](int u, u32x4 v) {
         const int idx = u * THREADS + tid;
-        if (F32IN) {
-            if (idx < nrows * FPIECES) {
-                unsigned char *dst = a_s + (idx >> 2) * ROWB + (idx & 3) * 8;
-                unsigned a1, a2, a3, b1, b2, b3;
-                float4 f = as_f4(v);
-                if (INBN) {
-                    const bool keep = (keep_bits >> u) & 1u;
-                    f.x = keep ? fmaxf(fmaf(f.x, bn_sc.x, bn_sh.x), 0.f) : 0.f;
-                    f.y = keep ? fmaxf(fmaf(f.y, bn_sc.y, bn_sh.y), 0.f) : 0.f;
-                    f.z = keep ? fmaxf(fmaf(f.z, bn_sc.z, bn_sh.z), 0.f) : 0.f;
-                    f.w = keep ? fmaxf(fmaf(f.w, bn_sc.w, bn_sh.w), 0.f) : 0.f;
-                }
-                split_pair(f.x, f.y, a1, a2, a3);
-                split_pair(f.z, f.w, b1, b2, b3);
-                *reinterpret_cast<u32x2 *>(dst + 0 * (KC * 2)) = u32x2{a1, b1};
-                *reinterpret_cast<u32x2 *>(dst + 1 * (KC * 2)) = u32x2{a2, b2};
-                *reinterpret_cast<u32x2 *>(dst + 2 * (KC * 2)) = u32x2{a3, b3};
-            }
-        } else {
-            if (idx < nrows * PIECES) *reinterpret_cast<u32x4 *>(a_s + idx * 16) = v;   // (unpadded rows: the span is copied as it is)
+        if (idx < nrows * FPIECES) {
+            unsigned char *dst = a_s + (idx >> 2) * ROWB + (idx & 3) * 8;
+            unsigned a1, a2, a3, b1, b2, b3;
+            if (INBN) v = bn_relu_piece(v, bn_sc, bn_sh, (keep_bits >> u) & 1u);
+            const float4 f = as_f4(v);
+            split_pair(f.x, f.y, a1, a2, a3);
+            split_pair(f.z, f.w, b1, b2, b3);
+            *reinterpret_cast<u32x2 *>(dst + 0 * (KC * 2)) = u32x2{a1, b1};
+            *reinterpret_cast<u32x2 *>(dst + 1 * (KC * 2)) = u32x2{a2, b2};
+            *reinterpret_cast<u32x2 *>(dst + 2 * (KC * 2)) = u32x2{a3, b3};
         }
     };
 
-    // ---- prologue: the first stage's rows are requested first (HBM), then the first NSLOT - 1 weight chunks (L2) ---------
+    // ---- prologue: the first stage's rows are requested first (HBM), then the first tap of weights (L2) -------------------
     u32x4 pre[NPRE];
     {
         const __amdgpu_buffer_rsrc_t in_r = stage_rsrc(0);
 #pragma unroll
-        for (int u = 0; u < NPRE; ++u) pre[u] = buf_load16(in_r, F32IN ? voff_f(u) : voff(u));
+        for (int u = 0; u < NPRE; ++u) pre[u] = buf_load16(in_r, voff(u));
         load_in_coef(0);
     }
+    // (the one-iteration loops over TPC here and in the tap loop stay: without them the compiler schedules the kernel differently,
+    // and this kernel is held to the instruction stream of profiles/split_family_isa.log)
 #pragma unroll
-    for (int k = 0; k < NSLOT - 1; ++k)
-#pragma unroll
-        for (int t = 0; t < TPC; ++t) issue_tap(k * TPC + t, 0, k);
+    for (int t = 0; t < TPC; ++t) issue_tap(t, 0, 0);
     for (int j = tid; j < TMW; j += THREADS) mask_s[j] = interior_row32((uint32_t)q0 + (uint32_t)j, g) ? 1 : 0;
     if (INBN) {
 #pragma unroll
@@ -259,42 +215,38 @@ __global__ __launch_bounds__(THREADS, TPC == 3 ? 2 : 3) void conv_b3x_kernel(con
 #pragma unroll
         for (int c = 0; c < NCT; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    int slot0 = 0;   // ring slot of the current stage's first chunk (always 0 when STATIC_SLOT)
+    int slot0 = 0;   // ring slot of the current stage's first tap (nine taps in two slots: it alternates)
 #pragma unroll 1
     for (int stage = 0; stage < NSTAGE; ++stage) {
         const bool last = stage + 1 == NSTAGE;
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
-            const int kc = tap / TPC;   // chunk of the stage
-            const int slot = STATIC_SLOT ? kc % NSLOT : (slot0 + kc) % NSLOT;
-            if (tap % TPC == 0) {
-                // chunk kc has landed (this wave's part), then everybody's; the slot of chunk kc - 1 is free
-                constexpr int YOUNGER = NSLOT - 2;
-                if (!last) {
-                    if (kc > K::KP && kc <= K::KP + NSLOT - 1) wait_dma<YOUNGER * TPC, NPRE>(nw_tap);   // + the requested rows
-                    else wait_dma<YOUNGER * TPC, 0>(nw_tap);
-                } else {
-                    if (CPS - 1 - kc >= YOUNGER) wait_dma<YOUNGER * TPC, 0>(nw_tap);
-                    else wait_dma<0, 0>(nw_tap);   // (NSLOT <= 3: at most one chunk is missing at the end)
-                }
-                __syncthreads();
-                const int kn = kc + NSLOT - 1;   // the chunk to request now
-                const int slot_n = STATIC_SLOT ? kn % NSLOT : (slot0 + kn) % NSLOT;
-                if (kn < CPS) {
+            const int slot = (slot0 + tap) % NSLOT;
+            // this tap's weights have landed (this wave's part), then everybody's; the other slot is free for the next tap.  (One tap
+            // after the next stage's rows were requested, those NPRE loads are younger than the weights and stay in flight.  The
+            // branches are written out per stage kind: merged, the compiler emits another instruction stream.)
+            if (!last) {
+                if (tap == K::KP + 1) wait_dma<0, NPRE>(nw_tap);
+                else wait_dma<0, 0>(nw_tap);
+            } else {
+                wait_dma<0, 0>(nw_tap);
+            }
+            __syncthreads();
+            const int slot_n = (slot0 + (tap + 1)) % NSLOT;   // the other slot takes the next tap
+            if (tap + 1 < TAPS) {
 #pragma unroll
-                    for (int t = 0; t < TPC; ++t) issue_tap(kn * TPC + t, stage, slot_n);
-                } else if (!last) {
+                for (int t = 0; t < TPC; ++t) issue_tap((tap + 1) * TPC + t, stage, slot_n);
+            } else if (!last) {
 #pragma unroll
-                    for (int t = 0; t < TPC; ++t) issue_tap((kn - CPS) * TPC + t, stage + 1, slot_n);
-                }
-                if (kc == K::KP && !last) {
-                    const __amdgpu_buffer_rsrc_t in_r = stage_rsrc(stage + 1);
+                for (int t = 0; t < TPC; ++t) issue_tap(t, stage + 1, slot_n);
+            }
+            if (tap == K::KP && !last) {
+                const __amdgpu_buffer_rsrc_t in_r = stage_rsrc(stage + 1);
 #pragma unroll
-                    for (int u = 0; u < NPRE; ++u) pre[u] = buf_load16(in_r, F32IN ? voff_f(u) : voff(u));
-                }
+                for (int u = 0; u < NPRE; ++u) pre[u] = buf_load16(in_r, voff(u));
             }
             const int off = (tap / 3 - 1) * wrow + (tap % 3) * ROWB;
-            const int boff = slot * CHUNK_BYTES + (tap % TPC) * TAP_BYTES;
+            const int boff = slot * TAP_BYTES;
             bf16x8 ap[4], aq[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -316,7 +268,7 @@ __global__ __launch_bounds__(THREADS, TPC == 3 ? 2 : 3) void conv_b3x_kernel(con
                 for (int r = 0; r < 4; ++r) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[r], bv, acc[r][c], 0, 0, 0);
             }
         }
-        if (!STATIC_SLOT) slot0 = (slot0 + CPS) % NSLOT;
+        slot0 = (slot0 + TAPS) % NSLOT;
 #ifdef LAD_STAMP
         if (threadIdx.x == 0 && blockIdx.x < 16384) lad_dbg_b3x[blockIdx.x * 16 + 3 + 2 * stage] = __builtin_amdgcn_s_memtime();
 #endif
@@ -352,11 +304,11 @@ __global__ __launch_bounds__(THREADS, TPC == 3 ? 2 : 3) void conv_b3x_kernel(con
     LAD_B3X_STAMP(12)
 }
 
-template <int C, int TPC, int NSLOT>
+template <int C>
 size_t b3x_lds_bytes(const Geom &g) {
-    using K = CfgX<C, TPC, NSLOT>;
+    using K = CfgX<C>;
     const int nrows = K::TMW + 2 * (g.Wp + 1);
-    const size_t main_bytes = std::max<size_t>(NSLOT * K::CHUNK_BYTES + (size_t)nrows * K::ROWB, (size_t)TM * (C + 4) * 4);
+    const size_t main_bytes = std::max<size_t>(K::NSLOT * K::TAP_BYTES + (size_t)nrows * K::ROWB, (size_t)TM * (C + 4) * 4);
     return main_bytes + K::TMW;   // + the row mask (bytes)
 }
 
@@ -879,8 +831,8 @@ extern "C" int lad_conv_b3c_pack_weights(const float *w, int32_t mode, void *wt,
 }
 
 namespace {
-template <int C, bool F32IN, bool STAT = false, bool INBN = false>
-int launch_b3(const void *in, const void *wt, const float *bias, const float *addend, const uint64_t *abits, float *out,
+template <int C, bool STAT = false, bool INBN = false>
+int launch_b3(const float *in, const void *wt, const float *bias, const float *addend, const uint64_t *abits, float *out,
               float *partials, int64_t batch, int32_t H, int32_t W, void *stream, const char *who, B3Stat bst = B3Stat{nullptr, nullptr, nullptr},
               const float *in_coef = nullptr) {
     using namespace lad;
@@ -895,31 +847,28 @@ int launch_b3(const void *in, const void *wt, const float *bias, const float *ad
     LAD_REQUIRE(W <= 46, "%s: image too wide for the tile (W = %d)", who, W);
     const int64_t tiles = ceil_div(g.rows, TM * 2);
     const dim3 grid((unsigned)(ceil_div(tiles, 8) * 8));
-    constexpr int TPC = 1, NSLOT = 2;   // one tap per ring chunk, two slots (the other combinations: tools/experiments/retired/)
     static lad::DeviceOnce attr_set;
     if (!attr_set) {
-        LAD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_b3x_kernel<C, F32IN, STAT, INBN, TPC, NSLOT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        LAD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_b3x_kernel<C, STAT, INBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_b3x_kernel<C, F32IN, STAT, INBN, TPC, NSLOT>), grid, dim3(THREADS), (b3x_lds_bytes<C, TPC, NSLOT>(g)),
-                       (hipStream_t)stream, (const unsigned char *)in, (const unsigned char *)wt, bias, addend,
-                       (const unsigned long long *)abits, out, partials, g, bst, in_coef);
+    hipLaunchKernelGGL((conv_b3x_kernel<C, STAT, INBN>), grid, dim3(THREADS), (b3x_lds_bytes<C>(g)), (hipStream_t)stream, in,
+                       (const unsigned char *)wt, bias, addend, (const unsigned long long *)abits, out, partials, g, bst, in_coef);
     return check_launch("conv_b3x_kernel");
 }
 }  // namespace
 
 extern "C" int lad_conv_b3_fwd_f32(const float *in, const void *wt, const float *bias, const float *addend, float *out,
                                    float *partials, int64_t batch, int32_t H, int32_t W, void *stream) {
-    return launch_b3<64, true>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32");
+    return launch_b3<64>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32");
 }
 
 // the same for `channels` = 64 or 32 input = output channels (32: block2's stride-1 convolutions)
 extern "C" int lad_conv_b3c_fwd_f32(const float *in, const void *wt, const float *bias, const float *addend, float *out,
                                     float *partials, int64_t batch, int32_t H, int32_t W, int32_t channels, void *stream) {
     using namespace lad;
-    if (channels == 64) return launch_b3<64, true>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32");
-    if (channels == 32) return launch_b3<32, true>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32");
+    if (channels == 64) return launch_b3<64>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32");
+    if (channels == 32) return launch_b3<32>(in, wt, bias, addend, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32");
     return fail(LAD_ERR_INVALID, "lad_conv_b3c_fwd_f32: 64 or 32 channels (got %d)", channels);
 }
 
@@ -930,7 +879,7 @@ extern "C" int lad_conv_b3_fwd_f32_gated(const float *in, const void *wt, const 
                                          int32_t W, void *stream) {
     using namespace lad;
     LAD_REQUIRE(addend && addend_bits, "lad_conv_b3_fwd_f32_gated: null addend / sign bits");
-    return launch_b3<64, true>(in, wt, bias, addend, addend_bits, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32_gated");
+    return launch_b3<64>(in, wt, bias, addend, addend_bits, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32_gated");
 }
 
 // Data gradient (no bias) fused with the first pass of the BatchNorm backward that consumes it: stat_partials receives, per
@@ -942,7 +891,7 @@ extern "C" int lad_conv_b3_dgrad_bnstat(const float *in, const void *wt, const f
                                         const float *bn_coef, int64_t batch, int32_t H, int32_t W, void *stream) {
     using namespace lad;
     LAD_REQUIRE(stat_partials && bn_x && bn_coef, "lad_conv_b3_dgrad_bnstat: null buffer");
-    return launch_b3<64, true, true>(in, wt, nullptr, addend, addend_bits, out, stat_partials, batch, H, W, stream,
+    return launch_b3<64, true>(in, wt, nullptr, addend, addend_bits, out, stat_partials, batch, H, W, stream,
                                      "lad_conv_b3_dgrad_bnstat", B3Stat{bn_x, (const unsigned long long *)bn_bits, bn_coef});
 }
 
@@ -953,8 +902,8 @@ extern "C" int lad_conv_b3c_dgrad_bnstat(const float *in, const void *wt, const 
     using namespace lad;
     LAD_REQUIRE(stat_partials && bn_x && bn_coef, "lad_conv_b3c_dgrad_bnstat: null buffer");
     const B3Stat bst{bn_x, nullptr, bn_coef};
-    if (channels == 64) return launch_b3<64, true, true>(in, wt, nullptr, addend, nullptr, out, stat_partials, batch, H, W, stream, "lad_conv_b3c_dgrad_bnstat", bst);
-    if (channels == 32) return launch_b3<32, true, true>(in, wt, nullptr, addend, nullptr, out, stat_partials, batch, H, W, stream, "lad_conv_b3c_dgrad_bnstat", bst);
+    if (channels == 64) return launch_b3<64, true>(in, wt, nullptr, addend, nullptr, out, stat_partials, batch, H, W, stream, "lad_conv_b3c_dgrad_bnstat", bst);
+    if (channels == 32) return launch_b3<32, true>(in, wt, nullptr, addend, nullptr, out, stat_partials, batch, H, W, stream, "lad_conv_b3c_dgrad_bnstat", bst);
     return fail(LAD_ERR_INVALID, "lad_conv_b3c_dgrad_bnstat: 64 or 32 channels (got %d)", channels);
 }
 
@@ -965,7 +914,7 @@ extern "C" int lad_conv_b3_fwd_f32_bnrelu(const float *in, const float *in_coef,
                                           float *partials, int64_t batch, int32_t H, int32_t W, void *stream) {
     using namespace lad;
     LAD_REQUIRE(in_coef, "lad_conv_b3_fwd_f32_bnrelu: null coefficients");
-    return launch_b3<64, true, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32_bnrelu",
+    return launch_b3<64, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3_fwd_f32_bnrelu",
                                             B3Stat{nullptr, nullptr, nullptr}, in_coef);
 }
 
@@ -976,9 +925,9 @@ extern "C" int lad_conv_b3c_fwd_f32_bnrelu(const float *in, const float *in_coef
     LAD_REQUIRE(in_coef, "lad_conv_b3c_fwd_f32_bnrelu: null coefficients");
     const B3Stat none{nullptr, nullptr, nullptr};
     if (channels == 64)
-        return launch_b3<64, true, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32_bnrelu", none, in_coef);
+        return launch_b3<64, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32_bnrelu", none, in_coef);
     if (channels == 32)
-        return launch_b3<32, true, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32_bnrelu", none, in_coef);
+        return launch_b3<32, false, true>(in, wt, bias, nullptr, nullptr, out, partials, batch, H, W, stream, "lad_conv_b3c_fwd_f32_bnrelu", none, in_coef);
     return fail(LAD_ERR_INVALID, "lad_conv_b3c_fwd_f32_bnrelu: 64 or 32 channels (got %d)", channels);
 }
 

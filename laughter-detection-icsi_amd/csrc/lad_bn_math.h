@@ -1,7 +1,10 @@
-// Element-wise arithmetic of the BatchNorm backward pass, shared by bn.hip and the kernels that apply it on the fly
-// (stem.hip: the stem's weight gradient consumes dz without it ever being written).
+// Element-wise arithmetic of the BatchNorm passes, shared by bn.hip and the kernels that apply it on the fly
+// (stem.hip: the stem's weight gradient consumes dz without it ever being written; the split-operand convolutions and weight
+// gradients: BatchNorm + ReLU of the previous layer's output while its rows are staged).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "lad_device.h"
 
 namespace lad {
 
@@ -49,6 +52,16 @@ __device__ __forceinline__ float4 mask_from_bits(float4 d, unsigned long long wo
     d.z = (hi & 1u) ? d.z : 0.f;
     d.w = (hi & 0x10000u) ? d.w : 0.f;
     return d;
+}
+// A staged 16-byte piece (4 fp32 channels) of a convolution's raw output -> the activation the next layer sees:
+// relu(x * scale + shift), the fmaf / max of bn_act_kernel, and 0 on border rows (keep = false), whatever the piece holds there.
+__device__ __forceinline__ u32x4 bn_relu_piece(u32x4 v, f32x4 scale, f32x4 shift, bool keep) {
+    float4 f = as_f4(v);
+    f.x = keep ? fmaxf(fmaf(f.x, scale.x, shift.x), 0.f) : 0.f;
+    f.y = keep ? fmaxf(fmaf(f.y, scale.y, shift.y), 0.f) : 0.f;
+    f.z = keep ? fmaxf(fmaf(f.z, scale.z, shift.z), 0.f) : 0.f;
+    f.w = keep ? fmaxf(fmaf(f.w, scale.w, shift.w), 0.f) : 0.f;
+    return as_u4(f);
 }
 // dx = k1 * (((d - k2_hi) - k2_lo) - xhat * k3_hi - xhat * k3_lo)
 __device__ __forceinline__ float bn_dx1(float d, float xh, float k1, float k2, float k2l, float k3, float k3l) {

@@ -14,6 +14,7 @@
 #include "lad_device.h"
 #include "lad_b3.h"
 #include "lad_bn_math.h"
+#include "lad_h2.h"
 
 #include <cstdlib>
 
@@ -213,44 +214,39 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(const float *__restri
 int groups_for(int64_t n_tiles) { return (int)std::max<int64_t>(1, std::min<int64_t>(MAX_GROUPS, n_tiles)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 64 x 64 x 9 weight gradient on the bf16 matrix cores with three-way split operands (lad_b3.h): the same sum
+// Weight gradients on the bf16 matrix cores with three-way split operands (lad_b3.h): the same sum
 //   dW[tap][ci][co] = sum_q in[q + shift(tap)][ci] * dout[q][co]
 // with K = rows.  Both MFMA operands are indexed [k][...] here (A[m = ci][k = row], B[k = row][n = co]) while the tensors
 // are [row][channel]: the fragments come out of LDS through the transposing read ds_read_b64_tr_b16 (a group of 16 lanes
 // reads 4 rows x 16 columns of 16-bit elements and receives them column-major: lane i gets column i of the 4 rows).
 //
-// A workgroup owns a CONTIGUOUS range of 32-row tiles and keeps a circular window of 128 input rows (32 + 2 x 46 halo
-// fits) in LDS as three bf16 planes: per tile only the 32 new rows of `in` and the 32 rows of `dout` are loaded (fp32,
-// 16-byte loads, one tile ahead, in registers during the MFMAs), split on the way to LDS -- the f32 kernel above re-stages
-// 156 rows per 64.  Wave w owns the (ci tile, co tile) pair w and all nine taps: 9 accumulators of 32 x 32 in registers
-// across all its tiles; per 16-row chunk a dout fragment (3 planes) feeds 9 x 6 MFMAs.  Slabs and their reduction are the
-// f32 kernel's.
+// A workgroup owns a CONTIGUOUS range of tiles and keeps a circular window of 128 input rows (a tile + 2 x halo must fit) in LDS
+// as three bf16 planes: per tile only the new rows of `in` and the rows of `dout` are loaded (fp32, 16-byte loads, one tile
+// ahead, in registers during the MFMAs), split on the way to LDS -- the f32 kernel above re-stages 156 rows per 64.  Nine
+// accumulators of 32 x 32 (one per tap) stay in registers across all the workgroup's tiles; per 16-row chunk a dout fragment
+// (3 planes) feeds 9 x 6 MFMAs.  Slabs and their reduction are the f32 kernel's.
 constexpr int B3_WIN = 128;   // rows of the circular input window (>= rows per tile + 2 * (W + 2))
-// CH = 64: a tile is 32 rows and the four waves are the 2 x 2 tiles of 32 x 32 (ci, co) outputs.  CH = 32 (block2): one
-// 32 x 32 output tile, so the four waves split K instead -- a tile is 64 rows, wave w takes rows 16 w .. 16 w + 15 -- and
-// the four partial sums meet in LDS at the end (one slab per workgroup either way).
-template <int CH>
-struct WB3 {
-    static constexpr int TK = CH == 64 ? 32 : 64;          // rows per tile
-    static constexpr int ROWB = CH * 2;                    // bytes per row of a bf16 plane
-    static constexpr int KPARTS = CH == 64 ? 1 : 4;        // waves that split the rows of a tile
-    static constexpr int PLANE_IN = B3_WIN * ROWB;         // bytes of one plane of the window: [row][CH bf16]
-    static constexpr int PLANE_DO = TK * ROWB;
-    static constexpr int LPR = CH / 4;                     // threads per fp32 row (16-byte pieces)
-    static constexpr int RPP = THREADS / LPR;              // rows one pass of the workgroup's threads covers
-};
+// wgrad_b3_kernel below is the 32-channel kernel of this family (block2's 32 x 32 x 9 gradients): one 32 x 32 output tile per tap, so
+// the four waves split K -- a tile is 64 rows, wave w takes rows 16 w .. 16 w + 15 -- and the four partial sums meet in LDS at the end
+// (one slab per workgroup).  64 channels run wgrad_b3x_kernel (further down; its round-2 form on this MFMA shape:
+// tools/experiments/retired/wgrad_mfma_variants.hip).
+namespace wb3 {
+constexpr int CH = 32;
+constexpr int TK = 64;                      // rows per tile
+constexpr int ROWB = CH * 2;                // bytes per row of a bf16 plane
+constexpr int PLANE_IN = B3_WIN * ROWB;     // bytes of one plane of the window: [row][32 bf16]
+constexpr int PLANE_DO = TK * ROWB;
+constexpr int LPR = CH / 4;                 // threads per fp32 row (16-byte pieces)
+constexpr int RPP = THREADS / LPR;          // rows one pass of the workgroup's threads covers
+constexpr size_t LDS_BYTES = 3 * PLANE_IN + 3 * PLANE_DO + RPP * CH * sizeof(float);
+}  // namespace wb3
 
 // The transposing read has no builtin: it is issued through inline asm, which the compiler's wait-count pass does not see.
 // Reads are therefore issued in groups (read_frags) and waited for by hand (wait_frags: LDS operations of a wave return in
 // order, so "at most N outstanding" retires everything issued before the last N); the wait statement takes the fragment
 // registers as in/out operands so that no consumer can be scheduled above it.
-// Bank swizzle of the [row][64 bf16] planes: a transposing read takes, per half-wave, 64 bytes of each of 4 consecutive rows;
-// at 128 bytes per row, rows r and r + 2 sit on the same 64 banks (PMC: 45% of the LDS cycles of the first version were bank
-// conflicts).  Swapping the two 64-byte halves of every other PAIR of rows puts any 4 consecutive rows on four different
-// quarters of the banks; writers and readers apply the same XOR, pieces of 8 bytes stay whole.
-// (64-byte rows -- 32 channels -- need none: four consecutive rows are 256 contiguous bytes.)
-template <int CH>
-__device__ __forceinline__ unsigned b3_swz(unsigned row) { return CH == 64 ? (row & 2u) << 5 : 0u; }
+// (No bank swizzle: a transposing read takes, per half-wave, 64 bytes of each of 4 consecutive rows, and at 64 bytes per row four
+// consecutive rows are 256 contiguous bytes.)
 
 struct Frags {
     u32x2 lo[3], hi[3];   // planes 0..2: k = 8h + 0..3 | 8h + 4..7
@@ -277,13 +273,12 @@ __device__ __forceinline__ bf16x8 frag_of(const Frags &f, int p) {
 // the activation relu(in * scale + shift) (0 on border rows) is formed while the rows are staged, bit for bit what
 // bn_act_kernel would have written (conv_b3.hip applies the same to the forward convolution: the activation tensor
 // never exists).
-template <int CH, bool INBN>
+template <bool INBN>
 __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__restrict__ in, const float *__restrict__ dout,
                                                              float *__restrict__ slabs, float *__restrict__ bias_slabs, Geom g,
                                                              int64_t n_tiles, int tiles_per_wg, const float *__restrict__ in_coef) {
     constexpr int TAPS = 9;
-    using K = WB3<CH>;
-    constexpr int B3_TK = K::TK, ROWB = K::ROWB, B3_PLANE_IN = K::PLANE_IN, B3_PLANE_DO = K::PLANE_DO, LPR = K::LPR, RPP = K::RPP;
+    constexpr int CH = wb3::CH, B3_TK = wb3::TK, ROWB = wb3::ROWB, B3_PLANE_IN = wb3::PLANE_IN, B3_PLANE_DO = wb3::PLANE_DO, LPR = wb3::LPR, RPP = wb3::RPP;
     static_assert(2 * RPP == B3_TK, "a thread stages two pieces of each tensor per tile");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_w[];
     unsigned char *in_s = smem_w;                        // [3 planes][B3_WIN rows][CH bf16]
@@ -291,8 +286,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
     float *bred_s = reinterpret_cast<float *>(do_s + 3 * B3_PLANE_DO);   // [RPP][CH]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int halo = g.Wp + 1;
-    const int mt = CH == 64 ? wave >> 1 : 0, nt = CH == 64 ? wave & 1 : 0;
-    const int kpart = CH == 64 ? 0 : wave;               // which 16 rows of the tile this wave multiplies (CH = 32)
+    const int kpart = wave;                              // which 16 rows of the tile this wave multiplies
 
     f32x16 acc[TAPS];
 #pragma unroll
@@ -310,7 +304,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
         unsigned a1, a2, a3, b1, b2, b3;
         split_pair(f.x, f.y, a1, a2, a3);
         split_pair(f.z, f.w, b1, b2, b3);
-        unsigned char *dst = plane0 + slot * ROWB + ((c4 * 8) ^ b3_swz<CH>(slot));
+        unsigned char *dst = plane0 + slot * ROWB + c4 * 8;
         *reinterpret_cast<u32x2 *>(dst) = u32x2{a1, b1};
         *reinterpret_cast<u32x2 *>(dst + plane_bytes) = u32x2{a2, b2};
         *reinterpret_cast<u32x2 *>(dst + 2 * plane_bytes) = u32x2{a3, b3};
@@ -324,13 +318,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
     }
     auto activate = [&](u32x4 v, int64_t row) {   // input piece of tensor row `row` -> the activation the convolution saw
         if (!INBN) return v;
-        const bool keep = interior_row32((uint32_t)row, g);   // (a row before the tensor wraps to a huge index: not interior)
-        float4 f = as_f4(v);
-        f.x = keep ? fmaxf(fmaf(f.x, bn_sc.x, bn_sh.x), 0.f) : 0.f;
-        f.y = keep ? fmaxf(fmaf(f.y, bn_sc.y, bn_sh.y), 0.f) : 0.f;
-        f.z = keep ? fmaxf(fmaf(f.z, bn_sc.z, bn_sh.z), 0.f) : 0.f;
-        f.w = keep ? fmaxf(fmaf(f.w, bn_sc.w, bn_sh.w), 0.f) : 0.f;
-        return as_u4(f);
+        return bn_relu_piece(v, bn_sc, bn_sh, interior_row32((uint32_t)row, g));   // (a row before the tensor wraps to a huge index: not interior)
     };
     const __amdgpu_buffer_rsrc_t in_r = make_rsrc(in, g.rows * (CH * 4));
     const __amdgpu_buffer_rsrc_t do_r = make_rsrc(dout, g.rows * (CH * 4));
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
     };
 
     if (t_begin < t_end) {
-        // ---- the window of the first tile: rows [q0 - halo, q0 + 32 + halo) ---------------------------------------------
+        // ---- the window of the first tile: rows [q0 - halo, q0 + 64 + halo) ---------------------------------------------
         const int64_t q0 = t_begin * B3_TK;
         for (int r = prow; r < B3_TK + 2 * halo; r += RPP) {
             const int64_t row = q0 - halo + r;
@@ -347,7 +335,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
         }
     }
     u32x4 pin[2], pdo[2];
-    auto fetch = [&](int64_t tile) {   // the 32 NEW input rows of `tile` (the top of its window) and its 32 dout rows
+    auto fetch = [&](int64_t tile) {   // the 64 NEW input rows of `tile` (the top of its window) and its 64 dout rows
         const int64_t q0 = tile * B3_TK;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -369,10 +357,10 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
     const int grp = lane >> 4, w16 = lane & 15;
     const int kh = grp >> 1;                                   // k = 8 kh + (0..3 | 4..7)
     const int qrow = w16 >> 2, colb = (w16 & 3) * 8;
-    const unsigned a_col = (mt * 32 + (grp & 1) * 16) * 2 + colb;     // byte within a row of ROWB bytes
-    const unsigned b_col = (nt * 32 + (grp & 1) * 16) * 2 + colb;
-    // (dout rows of a fragment: kc * 16 + 8 kh + 4 blk + qrow -- the swizzle bit is bit 1 of qrow)
-    const unsigned b_lane = lds_addr(do_s) + (8 * kh + qrow) * ROWB + (b_col ^ b3_swz<CH>(qrow));
+    const unsigned a_col = (grp & 1) * 16 * 2 + colb;     // byte within a row of ROWB bytes
+    const unsigned b_col = a_col;
+    // (dout rows of a fragment: kc * 16 + 8 kh + 4 blk + qrow)
+    const unsigned b_lane = lds_addr(do_s) + (8 * kh + qrow) * ROWB + b_col;
     const unsigned a_plane0 = lds_addr(in_s);
 
     for (int64_t tile = t_begin; tile < t_end; ++tile) {
@@ -387,17 +375,18 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
         }
         __syncthreads();
         if (tile + 1 < t_end) fetch(tile + 1);
-        // row slot (x 128 bytes) of this lane's first A row for tap offset 0 and chunk 0: q0 + 8 kh + qrow
+        // row slot (x 64 bytes) of this lane's first A row for tap offset 0 and chunk 0: q0 + 8 kh + qrow
         const unsigned a_row0 = (unsigned)((q0 + 8 * kh + qrow) & (B3_WIN - 1));
-        // 16-row chunks of the tile this wave multiplies: all of them (CH = 64), or chunk `kpart` only (CH = 32)
-        constexpr int NKC = (B3_TK / 16) / K::KPARTS;
+        // the one 16-row chunk of the tile this wave multiplies.  (A loop of one iteration: without it the compiler schedules the
+        // fragment reads differently, and the kernel is held to the instruction stream of profiles/split_family_isa.log.)
+        constexpr int NKC = (B3_TK / 16) / NWAVES;
 #pragma unroll
         for (int kci = 0; kci < NKC; ++kci) {
-            const int kc = K::KPARTS == 1 ? kci : kpart;
+            const int kc = kpart;
             auto a_addr = [&](int tap, int blk) {   // LDS byte address of this lane's piece of rows (chunk, block of 4) shifted by the tap
                 const int sh = (tap / 3 - 1) * g.Wp + (tap % 3 - 1);
                 const unsigned slot = (a_row0 + (unsigned)(kc * 16 + 4 * blk + sh + B3_WIN)) & (B3_WIN - 1);
-                return a_plane0 + slot * ROWB + (a_col ^ b3_swz<CH>(slot));
+                return a_plane0 + slot * ROWB + a_col;
             };
             Frags fb, fa[2];
             read_frags(fb, b_lane + (kc * 16) * ROWB, b_lane + (kc * 16 + 4) * ROWB, B3_PLANE_DO);
@@ -428,34 +417,26 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
     // ---- this workgroup's partial slab: slab[wg][tap][ci][co] (layout of wgrad_kernel; summed by slab_reduce.hip) -----
     float *slab = slabs + (int64_t)blockIdx.x * (TAPS * CH * CH);
     const int i = lane & 31;
-    if constexpr (K::KPARTS == 1) {
+    // the four waves hold partial sums of the SAME 32 x 32 tiles (they split K): add them through LDS (the window is free
+    // now), two taps per round, in wave order
+    float *sum_s = reinterpret_cast<float *>(smem_w);   // [2 taps][4 waves][32 x 32]
 #pragma unroll
-        for (int tap = 0; tap < TAPS; ++tap)
+    for (int t0 = 0; t0 < TAPS; t0 += 2) {
+        __syncthreads();   // the window (first round) / the previous round's readers are done
 #pragma unroll
-            for (int r = 0; r < 16; ++r) slab[(tap * CH + mt * 32 + acc_row(r, lane)) * CH + nt * 32 + i] = acc[tap][r];
-    } else {
-        // CH = 32: the four waves hold partial sums of the SAME 32 x 32 tiles (they split K): add them through LDS (the
-        // window is free now), two taps per round, in wave order -- one slab per workgroup, as for 64 channels
-        static_assert(CH == 32 && K::KPARTS == 4, "the in-workgroup sum is written for 4 waves x 32 x 32");
-        float *sum_s = reinterpret_cast<float *>(smem_w);   // [2 taps][4 waves][32 x 32]
+        for (int u = 0; u < 2; ++u)
+            if (t0 + u < TAPS) {
 #pragma unroll
-        for (int t0 = 0; t0 < TAPS; t0 += 2) {
-            __syncthreads();   // the window (first round) / the previous round's readers are done
+                for (int r = 0; r < 16; ++r) sum_s[((u * 4 + wave) * 32 + acc_row(r, lane)) * 32 + i] = acc[t0 + u][r];
+            }
+        __syncthreads();
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
-                if (t0 + u < TAPS) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sum_s[((u * 4 + wave) * 32 + acc_row(r, lane)) * 32 + i] = acc[t0 + u][r];
-                }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-                if (t0 + u < TAPS) {
-                    const f32x4 *src = reinterpret_cast<const f32x4 *>(sum_s + u * 4 * 1024) + tid;   // 256 threads x 4 floats = one tile
-                    const f32x4 v = ((src[0] + src[256]) + src[512]) + src[768];
-                    *reinterpret_cast<f32x4 *>(slab + (t0 + u) * (CH * CH) + tid * 4) = v;
-                }
-        }
+        for (int u = 0; u < 2; ++u)
+            if (t0 + u < TAPS) {
+                const f32x4 *src = reinterpret_cast<const f32x4 *>(sum_s + u * 4 * 1024) + tid;   // 256 threads x 4 floats = one tile
+                const f32x4 v = ((src[0] + src[256]) + src[512]) + src[768];
+                *reinterpret_cast<f32x4 *>(slab + (t0 + u) * (CH * CH) + tid * 4) = v;
+            }
     }
     if (bias_slabs != nullptr) {
         __syncthreads();
@@ -486,16 +467,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3_kernel(const float *__res
 //     does not care -- and the planes are swizzled by ((row >> 1) & 3) x 32 bytes: eight consecutive rows x 32 bytes then
 //     tile the 64 banks for any window position (the round-2 swizzle served 4 + 4 rows eight apart).
 //   * Offsets are relative to the workgroup's own first row (64-bit base, 32-bit lane offsets): no 2 GiB limit.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned b3x_swz(unsigned row) { return (row & 6u) << 4; }   // ((row >> 1) & 3) * 32 bytes
-
-__device__ __forceinline__ bf16x8 read_tr_frag(unsigned addr_lo, unsigned addr_hi, int imm) {
-    typedef __attribute__((address_space(3))) s16x4 *lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(size_t)(addr_lo + imm));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(size_t)(addr_hi + imm));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <bool INBN>
 __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__restrict__ in, const float *__restrict__ dout,
@@ -548,13 +520,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__re
     }
     auto activate = [&](u32x4 v, int64_t row) {
         if (!INBN) return v;
-        const bool keep = row >= 0 && interior_row32((uint32_t)row, g);
-        float4 f = as_f4(v);
-        f.x = keep ? fmaxf(fmaf(f.x, bn_sc.x, bn_sh.x), 0.f) : 0.f;
-        f.y = keep ? fmaxf(fmaf(f.y, bn_sc.y, bn_sh.y), 0.f) : 0.f;
-        f.z = keep ? fmaxf(fmaf(f.z, bn_sc.z, bn_sh.z), 0.f) : 0.f;
-        f.w = keep ? fmaxf(fmaf(f.w, bn_sc.w, bn_sh.w), 0.f) : 0.f;
-        return as_u4(f);
+        return bn_relu_piece(v, bn_sc, bn_sh, row >= 0 && interior_row32((uint32_t)row, g));
     };
     // buffer resources over the rows this workgroup can touch, [r_first, r_last): offsets relative to r_first stay far below 2^31
     const int64_t r_first = max((int64_t)0, t_begin * TK - halo);
@@ -608,7 +574,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__re
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) b[nt][p] = read_tr_frag(b_lo ^ (nt * 32), b_hi ^ (nt * 32), p * PLANE_DO);
+            for (int p = 0; p < 3; ++p) b[nt][p] = read_tr_frag<bf16x8>(b_lo ^ (nt * 32), b_hi ^ (nt * 32), p * PLANE_DO);
         const unsigned s0 = (unsigned)q0 + lrow + B3_WIN;   // (window slot of this lane's first row) + B3_WIN, before the tap shift
         // The taps are software-pipelined by halves: while the 12 MFMAs of the wave's first 16 input channels (mt = 0) run,
         // the fragments of its second 16 (mt = 1) are in flight, and during those 12 the mt = 0 fragments of the NEXT tap
@@ -620,7 +586,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__re
             const unsigned cs = (a_col ^ b3x_swz(slot_lo)) ^ (mt * 32);   // (slot_hi has the same bits 1..2)
             const unsigned a_lo = a_base + ((slot_lo << 7) | cs), a_hi = a_base + ((slot_hi << 7) | cs);
 #pragma unroll
-            for (int p = 0; p < 3; ++p) a[p] = read_tr_frag(a_lo, a_hi, p * PLANE_IN);
+            for (int p = 0; p < 3; ++p) a[p] = read_tr_frag<bf16x8>(a_lo, a_hi, p * PLANE_IN);
         };
         auto mfmas = [&](int tap, int mt, const bf16x8 (&a)[3]) {
 #define LAD_WB3X_TERM(pa, pb) \
@@ -689,29 +655,6 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_b3x_kernel(const float *__re
 // window, the same event also re-stages the window's 2 x halo older rows from HBM with the new exponent (three binades of
 // headroom make it rare: an activation tensor's tile maxima vary by far less than 8x).  Exponents only ever decrease along a
 // workgroup's range, so what a later, much smaller tile loses is below 2^-37 of the running maximum -- and of the sums it joins.
-typedef short s16x8w __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f16x8 read_tr_frag_h(unsigned addr_lo, unsigned addr_hi, int imm) {
-    typedef __attribute__((address_space(3))) s16x4 *lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(size_t)(addr_lo + imm));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(size_t)(addr_hi + imm));
-    return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-typedef _Float16 wh16x2 __attribute__((ext_vector_type(2)));
-typedef float wf32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2_pair_w(float a, float b, unsigned &p1, unsigned &p2) {
-    const wf32x2 v = {a, b};
-    const wh16x2 h = __builtin_convertvector(v, wh16x2);   // round to nearest even
-    p1 = __builtin_bit_cast(unsigned, h);
-    const wf32x2 r = {a - (float)h.x, b - (float)h.y};     // exact
-    p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, wh16x2));
-}
-__device__ __forceinline__ int scale_exp_w(float amax) {   // amax * 2^k in [2^14, 2^15) (conv_h2.hip: scale_exp)
-    const int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu);
-    const int k = 141 - e;
-    return k > 100 ? 100 : k;
-}
-__device__ __forceinline__ float pow2f_w(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
-__device__ __forceinline__ float wave_max64_w(float v) { return wave_max64_dpp(v); }
 __device__ __forceinline__ float amax4(u32x4 v) {
     const float4 f = as_f4(v);
     return fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w)));
@@ -790,8 +733,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
     auto split = [&](u32x4 v, float scl, u32x2 &h1, u32x2 &h2) {
         const float4 f = as_f4(v);
         unsigned a1, a2, b1, b2;
-        split2_pair_w(f.x * scl, f.y * scl, a1, a2);
-        split2_pair_w(f.z * scl, f.w * scl, b1, b2);
+        split2_pair(f.x * scl, f.y * scl, a1, a2);
+        split2_pair(f.z * scl, f.w * scl, b1, b2);
         h1 = u32x2{a1, b1};
         h2 = u32x2{a2, b2};
     };
@@ -820,13 +763,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
     auto activate = [&](u32x4 v, int row) {
         if (!INBN) return v;
         const bool keep = row >= 0 && interior_row32((uint32_t)row, g);
-        float4 f = as_f4(v);
         const f32x4 bn_sc = *reinterpret_cast<const f32x4 *>(ci_s + pc4 * 4), bn_sh = *reinterpret_cast<const f32x4 *>(ci_s + CH + pc4 * 4);
-        f.x = keep ? fmaxf(fmaf(f.x, bn_sc.x, bn_sh.x), 0.f) : 0.f;
-        f.y = keep ? fmaxf(fmaf(f.y, bn_sc.y, bn_sh.y), 0.f) : 0.f;
-        f.z = keep ? fmaxf(fmaf(f.z, bn_sc.z, bn_sh.z), 0.f) : 0.f;
-        f.w = keep ? fmaxf(fmaf(f.w, bn_sc.w, bn_sh.w), 0.f) : 0.f;
-        return as_u4(f);
+        return bn_relu_piece(v, bn_sc, bn_sh, keep);
     };
     const int n_rows = (int)g.rows;
     const int r_first = max(0, t_begin * TK - halo);
@@ -962,8 +900,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
             m_in = fmaxf(m_in, amax4(pin[u]));
             m_do = fmaxf(m_do, amax4(pdo[u]));
         }
-        m_in = wave_max64_w(m_in);
-        m_do = wave_max64_w(m_do);
+        m_in = wave_max64_dpp(m_in);
+        m_do = wave_max64_dpp(m_do);
         if (lane == 0) {
             smx[wave] = m_in;
             smx[4 + wave] = m_do;
@@ -972,7 +910,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
         m_in = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
         m_do = fmaxf(fmaxf(smx[4], smx[5]), fmaxf(smx[6], smx[7]));
         int d = 0;
-        if (!have || scale_exp_w(m_in) < e_in) {   // (workgroup-uniform) the window's older rows are re-staged with the new exponent
+        if (!have || scale_exp(m_in) < e_in) {   // (workgroup-uniform) the window's older rows are re-staged with the new exponent
             u32x4 wr[NWR];
             float m_w = 0.f;
 #pragma unroll
@@ -983,22 +921,22 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
                 if (r >= 2 * halo) wr[u] = u32x4{0u, 0u, 0u, 0u};   // (not a window row: an activated zero is relu(shift), not 0)
                 m_w = fmaxf(m_w, amax4(wr[u]));
             }
-            m_w = wave_max64_w(m_w);
+            m_w = wave_max64_dpp(m_w);
             if (lane == 0) smx[8 + wave] = m_w;
             __syncthreads();
             m_w = fmaxf(fmaxf(smx[8], smx[9]), fmaxf(smx[10], smx[11]));
-            const int e_new = scale_exp_w(fmaxf(m_in, m_w)) - HEAD_IN;
+            const int e_new = scale_exp(fmaxf(m_in, m_w)) - HEAD_IN;
             d += have ? e_new - e_in : 0;
             e_in = e_new;
-            const float scl = pow2f_w(e_in);
+            const float scl = pow2f(e_in);
 #pragma unroll
             for (int u = 0; u < NWR; ++u) {
                 const int r = prow + RPP * u;
                 if (r < 2 * halo) put_in(q0 - halo + r, pc4, wr[u], scl);
             }
         }
-        if (!have || scale_exp_w(m_do) < e_do) {
-            const int e_new = scale_exp_w(m_do) - HEAD_DO;
+        if (!have || scale_exp(m_do) < e_do) {
+            const int e_new = scale_exp(m_do) - HEAD_DO;
             d += have ? e_new - e_do : 0;
             e_do = e_new;
         }
@@ -1014,7 +952,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
         }
         have = true;
         {
-            const float s_in = pow2f_w(e_in), s_do = pow2f_w(e_do);
+            const float s_in = pow2f(e_in), s_do = pow2f(e_do);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int row = q0 + halo + prow + RPP * u;
@@ -1029,7 +967,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) b[nt][p] = read_tr_frag_h(b_lo ^ (nt * 32), b_hi ^ (nt * 32), p * PLANE_DO);
+            for (int p = 0; p < 2; ++p) b[nt][p] = read_tr_frag<f16x8>(b_lo ^ (nt * 32), b_hi ^ (nt * 32), p * PLANE_DO);
         // a tap's two 16-row groups start at wave-uniform slots (scalar unit); neither wraps, thanks to the guard slots
         auto a_frags = [&](int tap, int mt, f16x8 (&a)[2]) {
             const int sh = q0 + (tap / 3 - 1) * g.Wp + (tap % 3 - 1);
@@ -1037,7 +975,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_h2_kernel(const float *__res
             const unsigned s_hi = __builtin_amdgcn_readfirstlane((unsigned)((sh + 16) & (B3_WIN - 1)) * H2_WIN_PITCH);
             const unsigned a_lo = a_lane + s_lo, a_hi = a_lane + s_hi;
 #pragma unroll
-            for (int p = 0; p < 2; ++p) a[p] = read_tr_frag_h(a_lo, a_hi, p * PLANE_IN + mt * 32);
+            for (int p = 0; p < 2; ++p) a[p] = read_tr_frag<f16x8>(a_lo, a_hi, p * PLANE_IN + mt * 32);
         };
         auto mfmas = [&](int tap, int mt, const f16x8 (&a)[2]) {   // smallest terms first: a1 b2, a2 b1, a1 b1
 #define LAD_WH2_TERM(pa, pb) \
@@ -1122,46 +1060,40 @@ int launch_wgrad_h2(const float *in, const float *in_coef, const float *dout, fl
     return lad::reduce_slabs(lad::SlabReduce{slabs, dbias ? bias_slabs : nullptr, dw, dbias, groups, CH, CH, TAPS}, st);
 }
 
+// 64 channels: wgrad_b3x_kernel (16x16x32, 32-row tiles); 32 channels: wgrad_b3_kernel (32x32x16, 64-row tiles whose rows the waves split)
 template <int CH, bool INBN>
 int launch_wgrad_b3(const float *in, const float *in_coef, const float *dout, float *ws, float *dw, float *dbias, const Geom &g, hipStream_t st) {
-    constexpr int TAPS = 9;
-    using K = WB3<CH>;
-    if (K::TK + 2 * (g.Wp + 1) > B3_WIN) return lad::fail(LAD_ERR_INVALID, "wgrad (bf16 x 3): image too wide for the window (W = %d)", g.Wp - 1);
+    constexpr int TAPS = 9, TK = CH == 64 ? 32 : wb3::TK;
+    if (TK + 2 * (g.Wp + 1) > B3_WIN) return lad::fail(LAD_ERR_INVALID, "wgrad (bf16 x 3): image too wide for the window (W = %d)", g.Wp - 1);
     if (g.rows >= ((int64_t)1 << 31) || g.img >= (1 << 20))
         return lad::fail(LAD_ERR_INVALID, "wgrad (bf16 x 3): tensor too large for 32-bit row arithmetic");
-    const int64_t n_tiles = lad::ceil_div(g.rows, K::TK);
+    if (CH == 32 && g.rows >= ((int64_t)1 << 31) / (CH * 4))   // (wgrad_b3_kernel's offsets are relative to the tensor, not to the workgroup's rows)
+        return lad::fail(LAD_ERR_INVALID, "wgrad (bf16 x 3, 32x32x16 kernel): tensor too large for 32-bit offsets");
+    const int64_t n_tiles = lad::ceil_div(g.rows, TK);
     const int groups = groups_for(n_tiles);
     const int tiles_per_wg = (int)lad::ceil_div(n_tiles, groups);
-    const size_t lds = 3 * K::PLANE_IN + 3 * K::PLANE_DO + K::RPP * CH * sizeof(float);
+    // three planes of the window and of the dout tile, and the bias sums' [rows per pass][CH] floats
+    const size_t lds = CH == 64 ? 3 * B3_WIN * 128 + 3 * 32 * 128 + (THREADS / 16) * 64 * sizeof(float) : wb3::LDS_BYTES;
     float *slabs = ws;
     float *bias_slabs = ws + (int64_t)MAX_GROUPS * TAPS * CH * CH;
-    if constexpr (CH == 64) {   // wgrad_b3x_kernel (16x16x32); the round-2 form of the 64-channel kernel: tools/experiments/retired/
-        static bool attr_x = false;
-        if (!attr_x) {
-            LAD_HIP_CHECK(hipFuncSetAttribute((const void *)wgrad_b3x_kernel<INBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr_x = true;
-        }
-        hipLaunchKernelGGL((wgrad_b3x_kernel<INBN>), dim3(groups), dim3(THREADS), lds, st, in, dout, slabs, dbias ? bias_slabs : nullptr, g,
-                           n_tiles, tiles_per_wg, in_coef);
-        int rcx = lad::check_launch("wgrad_b3x_kernel");
-        if (rcx) return rcx;
-        return lad::reduce_slabs(lad::SlabReduce{slabs, dbias ? bias_slabs : nullptr, dw, dbias, groups, CH, CH, TAPS}, st);
-    } else {
-        static lad::DeviceOnce attr_set;
-        if (!attr_set) {
-            LAD_HIP_CHECK(hipFuncSetAttribute((const void *)wgrad_b3_kernel<CH, INBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr_set = true;
-        }
-        if (g.rows >= ((int64_t)1 << 31) / (CH * 4)) return lad::fail(LAD_ERR_INVALID, "wgrad (bf16 x 3, 32x32x16 kernel): tensor too large for 32-bit offsets");
-        hipLaunchKernelGGL((wgrad_b3_kernel<CH, INBN>), dim3(groups), dim3(THREADS), lds, st, in, dout, slabs, dbias ? bias_slabs : nullptr, g, n_tiles,
-                           tiles_per_wg, in_coef);
-        int rc = lad::check_launch("wgrad_b3_kernel");
-        if (rc) return rc;
-        return lad::reduce_slabs(lad::SlabReduce{slabs, dbias ? bias_slabs : nullptr, dw, dbias, groups, CH, CH, TAPS}, st);
+    const void *kernel;
+    if constexpr (CH == 64) kernel = (const void *)wgrad_b3x_kernel<INBN>;
+    else kernel = (const void *)wgrad_b3_kernel<INBN>;
+    static lad::DeviceOnce attr_set;
+    if (!attr_set) {
+        LAD_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_set = true;
     }
+    if constexpr (CH == 64)
+        hipLaunchKernelGGL((wgrad_b3x_kernel<INBN>), dim3(groups), dim3(THREADS), lds, st, in, dout, slabs, dbias ? bias_slabs : nullptr, g, n_tiles,
+                           tiles_per_wg, in_coef);
+    else
+        hipLaunchKernelGGL((wgrad_b3_kernel<INBN>), dim3(groups), dim3(THREADS), lds, st, in, dout, slabs, dbias ? bias_slabs : nullptr, g, n_tiles,
+                           tiles_per_wg, in_coef);
+    int rc = lad::check_launch(CH == 64 ? "wgrad_b3x_kernel" : "wgrad_b3_kernel");
+    if (rc) return rc;
+    return lad::reduce_slabs(lad::SlabReduce{slabs, dbias ? bias_slabs : nullptr, dw, dbias, groups, CH, CH, TAPS}, st);
 }
-
-
 
 template <int CIN, int COUT, int TAPS>
 int launch_wgrad(const float *in, const float *dout, float *ws, float *dw, float *dbias, const Geom &g, hipStream_t st) {

@@ -1,3 +1,4 @@
+// RETIRED (round 6): lad_b3_tile.h as conv_h2w_variants.hip needs it -- b3_epilogue with ASMBAR / tid_in, which only that kernel used.
 // Pieces of the split-operand tile kernels shared by conv_b3.hip (three bf16 planes) and conv_h2.hip (two f16 planes): the
 // tile constants, the epilogue (bias / addend / sign-bit gate / BatchNorm partial sums / scatter) and the counted waits of
 // the LDS-DMA weight ring.  Device code only; everything is a template or force-inlined.
@@ -38,13 +39,15 @@ struct B3Scatter {
     int64_t part_tile;      // index of this sub-tile's partials
 };
 
-template <int C, bool STAT, bool SCATTER = false, class StoreAcc, class MaskT>
+template <int C, bool STAT, bool SCATTER = false, bool ASMBAR = false, class StoreAcc, class MaskT>
 __device__ __forceinline__ void b3_epilogue(StoreAcc store_acc, const float *__restrict__ bias, const float *addend,
                                             const unsigned long long *__restrict__ abits, float *out, float *__restrict__ partials,
                                             const MaskT *mask_tile, float *out_s, int64_t q0, int64_t rows, const B3Stat &bst,
-                                            const B3Scatter &sct = B3Scatter{nullptr, 0, 0, 0}) {
+                                            const B3Scatter &sct = B3Scatter{nullptr, 0, 0, 0}, int tid_in = -1) {
     constexpr int LDO = C + 4, LPR = C / 4, RPI = 64 / LPR, ITER = 32 / RPI, STEP = RPI * C * 4;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (tid_in: the caller's own copy of threadIdx.x -- a persistent kernel passes one the compiler cannot see through, so that what is
+    // derived from it here is recomputed per tile instead of being kept, and spilled, across the caller's MFMA loop)
+    const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float *my = out_s + wave * 32 * LDO;
     store_acc(my);   // the wave's 32 x C tile, row-major with leading dimension LDO
     const int c4 = lane % LPR, rsub = lane / LPR;
@@ -145,7 +148,9 @@ __device__ __forceinline__ void b3_epilogue(StoreAcc store_acc, const float *__r
     if (partials == nullptr) return;
     *reinterpret_cast<f32x4 *>(my + (rsub * 2 + 0) * C + c4 * 4) = s1;
     *reinterpret_cast<f32x4 *>(my + (rsub * 2 + 1) * C + c4 * 4) = s2;
-    __syncthreads();
+    // (ASMBAR: called by the first four waves of a larger workgroup whose other waves execute a matching bare barrier)
+    if (ASMBAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else __syncthreads();
     if (tid < 2 * C) {
         const int k = tid / C, co = tid - k * C;
         float s = 0.0f;
@@ -157,7 +162,7 @@ __device__ __forceinline__ void b3_epilogue(StoreAcc store_acc, const float *__r
     }
 }
 
-// conv_h2.hip's own entry: b3_epilogue without SCATTER and with the options a launch was given as template parameters
+// conv_h2.hip's own entry: b3_epilogue without SCATTER / ASMBAR and with the options a launch was given as template parameters
 // instead of run-time null tests inside the unrolled row loops (ISA of conv_h2_kernel<64, 2, false, false>: about 200 branches
 // after the last MFMA, most of them these tests).  The arithmetic, its order and the LDS traffic are those of b3_epilogue, line
 // for line -- `+ bias` without a bias still adds +0 (it turns a -0 accumulator into +0, as the shared entry does) -- so `out` and
