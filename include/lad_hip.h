@@ -760,6 +760,64 @@ int lad_lowpass(const void *probs, int32_t dtype, int64_t channels, int64_t fram
                 const double *b_host, const double *a_host, const double *zi_host, double *out, void *workspace,
                 void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Redrawing the segment table (csrc/sample.hip): which frames of which channel form each training example, drawn afresh for
+ * every epoch from regions and pools of regions.  Replaces, on the device, the sampling of the reference's create_data_df.py
+ * (get_subsample :84-95, get_random_segment_from_df :65-81, the rejection loops of get_random_non_laughter_segment :32-63) and
+ * the label rule of compute_features.py:228-243.  The text below IS the specification (tests/_sample_model.py is a second
+ * implementation of it, in Python integers).  Integers only.
+ *
+ * Frames and milliseconds.  fps frames per second (100 or 128), T frames per segment.  Frame f spans the milliseconds
+ * (1000 f / fps, 1000 (f + 1) / fps] in exact rational arithmetic.  A window of frames [a, a + n) lies inside a transcript
+ * interval (lo, hi] (ms) iff 1000 a >= lo fps and 1000 (a + n) <= hi fps, compared as int64 products; the frames of (lo, hi] on
+ * a channel with frames_c feature rows are therefore [ceil(lo fps / 1000), min(floor(hi fps / 1000), frames_c)).  The
+ * millisecond hull of a window is (floor(1000 a / fps), ceil(1000 (a + n) / fps)]; a window inside an interval by the frame
+ * rule has its hull inside it too, and at 100 fps both rules are exact.
+ *
+ * Regions and pools.  A region is (chan, lo, hi) in frames, hi > lo: regions int32 [n_regions][3].  Pool p is the slice
+ * pool_off[p] .. pool_off[p + 1] of the region array (pool_off int32 [n_pools + 1], ascending from 0, at most n_regions).
+ * pool_cum[j] (int64 [n_regions]) is the sum of (hi - lo - T + 1) over the regions of j's pool that precede j; it is read for
+ * measure pools only, whose regions all have hi - lo >= T.
+ *
+ * Rows.  Row i has kind[i] and src[i]:
+ *   LAD_SAMPLE_FIXED         src = a region:  n = min(T, hi - lo), first = lo + mulhi(r1, hi - lo - n + 1)
+ *   LAD_SAMPLE_POOL_ROW      src = a pool:    region j = pool_off[p] + mulhi(r0, regions in p), then as FIXED
+ *                                             (create_data_df.py:75-79: a row of the pool, then a window inside it)
+ *   LAD_SAMPLE_POOL_MEASURE  src = a pool of total measure M = sum of (hi - lo - T + 1) < 2^32:  u = mulhi(r0, M); j = the last
+ *                                             region of the pool with pool_cum[j] <= u; first = lo_j + (u - pool_cum[j]); n = T
+ *                                             (every window of T frames inside the pool's regions is equally likely: the
+ *                                             exact form of the reference's rejection loops, no rejection needed)
+ * Random words.  (r0, r1, r2, r3) = philox4x32_10(counter = (row_id & 0xffffffff, row_id >> 32, epoch, 0x53414D50),
+ * key = (seed & 0xffffffff, seed >> 32)); mulhi(u, n) = (u * n) >> 32.  The tag in word 3 keeps these draws apart from the
+ * augmentation's, which uses small k there.  row_id is the row's place in the table before any permutation or sharding
+ * (row_id NULL: i itself), so a row's window is a pure function of (seed, epoch, row_id): not of batch size, rank or world size.
+ *
+ * Outputs.  chan int32, first int64, count int32 (n_rows each): what lad_gather_segments takes; region (int32, or NULL): the
+ * region index j the row was drawn from.  By construction lo_j <= first and first + count <= hi_j.
+ *
+ * Host copies.  pool_off_host and pool_total_host (int64 [n_pools]: M of a measure pool, anything in [0, 2^32) for another) are
+ * checked before anything is launched, and so are kind_host / src_host when they are not NULL: a kind outside 0..2, a src
+ * outside its array, a POOL_ROW row of an empty pool, a POOL_MEASURE row of a pool with M = 0, M >= 2^32, offsets that do not
+ * ascend from 0 or pass n_regions, T < 1, sizes above 2^30 or a null buffer return LAD_ERR_INVALID with lad_last_error() set.
+ * The kernel still guards every region read by n_regions and every pool read by n_pools; a row it cannot draw gets count 0.
+ * n_rows == 0 returns LAD_OK without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+enum lad_sample_kind { LAD_SAMPLE_FIXED = 0, LAD_SAMPLE_POOL_ROW = 1, LAD_SAMPLE_POOL_MEASURE = 2 };
+int lad_sample_segments(const int32_t *kind, const int32_t *src, int64_t n_rows, const int64_t *row_id, const int32_t *regions,
+                        int64_t n_regions, const int32_t *pool_off, const int64_t *pool_cum, int32_t n_pools,
+                        const int32_t *kind_host, const int32_t *src_host, const int32_t *pool_off_host,
+                        const int64_t *pool_total_host, int32_t T, uint64_t seed, uint32_t epoch, int32_t *chan, int64_t *first,
+                        int32_t *count, int32_t *region, void *stream);
+/* out[i][s] = milliseconds of set s of channel set_chan[i] inside the hull of window i = frames [first[i], first[i] + count[i])
+ * at fps frames per second: F(hull_hi) - F(hull_lo) with F the coverage function of lad_score_runs' index (a negative first or
+ * count is read as 0).  bounds int32 [n_intervals][2], offsets int32 [n_channels * n_sets + 1]: the CSR layout of
+ * lad_score_runs with n_sets sets per channel instead of 5; within a set intervals are non-empty, sorted and disjoint,
+ * 0 <= lo < hi.  The host copies are checked before the launch as lad_score_runs checks its index (LAD_ERR_INVALID, nothing
+ * launched); a set_chan outside [0, n_channels) gives a row of zeros.  out: DEVICE int32 [n][n_sets]. */
+int lad_window_coverage(const int32_t *set_chan, const int64_t *first, const int32_t *count, int64_t n, int32_t fps,
+                        const int32_t *bounds, const int32_t *offsets, const int32_t *bounds_host, const int32_t *offsets_host,
+                        int64_t n_intervals, int32_t n_channels, int32_t n_sets, int32_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

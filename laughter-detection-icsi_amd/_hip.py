@@ -187,6 +187,12 @@ SIGNATURES = {
     "lad_lowpass_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "lad_lowpass": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64)] + [ctypes.POINTER(c_double)] * 3
                     + [c_void_p, c_void_p, c_void_p]),
+    # redrawing the segment table, transcript coverage of windows (csrc/sample.hip)
+    "lad_sample_segments": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i32,
+                                    ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
+                                    c_i32, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lad_window_coverage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, ctypes.POINTER(c_i32),
+                                    ctypes.POINTER(c_i32), c_i64, c_i32, c_i32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -62,3 +62,19 @@ AUGMENT['mix'] = {
 }
 
 AUGMENT['spec+mix'] = {**AUGMENT['spec'], **AUGMENT['mix']}
+
+# Segment-table presets (sampling.SegmentPools.plan; the convention is in include/lad_hip.h next to lad_sample_segments).
+# 'reference' is create_data_df.py's scheme: per laugh row num_laugh_samples windows of the row and num_non_laugh_samples
+# negatives, floor(0.7 n) of them silence, floor(0.1 n) noise, the rest speech (:124-126); random=True draws every negative from
+# anywhere outside laughter and invalid regions (:144-147).  The reference reads the two counts from its environment
+# (NUM_OF_LAUGH_SAMPLES / NUM_OF_NON_LAUGH_SAMPLES, :212-213) and ships no values: the ones here are this project's default.
+SAMPLING = {}
+
+SAMPLING['reference'] = {
+    'num_laugh_samples': 10,
+    'num_non_laugh_samples': 10,
+    'silence_share': 0.7,
+    'noise_share': 0.1,
+    'subsample_duration': 1.0,  # seconds: the segment length (config.py:56 of the reference)
+    'random': False,
+}

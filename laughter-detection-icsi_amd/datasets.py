@@ -123,11 +123,18 @@ class LadDataset(torch.utils.data.Dataset):
     augment: an augment.AugmentConfig -- the batches are augmented in the gather launch, differently in every epoch
     (`set_epoch`); None: the plain gather.  noise: what mixing draws from -- 'self' (the channels this table names that hold at
     least a segment's frames: other speech, no extra data, and never a channel that only another split sharing the store uses), a
-    list of store keys / indices, or a NoiseChannels."""
+    list of store keys / indices, or a NoiseChannels.
+    redraw: the windows are drawn afresh by `set_epoch` (csrc/sample.hip; the convention: include/lad_hip.h next to
+    lad_sample_segments) -- 'window': every row inside its own region (a table with region_first / region_frames:
+    segments.table_from_rows(keep_regions=True)); a sampling.Sampler of len(table) rows whose pools name the table's channels: every
+    row by its kind.  One launch per epoch into the arrays the gather reads, no synchronisation, no host copy.  Until the first
+    `set_epoch` the table's own windows stand.  redraw_seed: the seed of a 'window' redraw (a Sampler
+    brings its own).  None (the default): the table as it is, and nothing here runs."""
 
-    def __init__(self, store, table, pad_value=LOG_EPSILON, augment=None, noise=None):
+    def __init__(self, store, table, pad_value=LOG_EPSILON, augment=None, noise=None, redraw=None, redraw_seed=0):
         super().__init__()
         self.store, self.table, self.pad_value = store, table, pad_value
+        self.redraw, self._draw_table, self._draw_seed = redraw, None, int(redraw_seed)
         self.augment, self.noise, self.epoch = augment, None, 0
         if augment is not None:
             T = table.frames_per_segment
@@ -143,6 +150,10 @@ class LadDataset(torch.utils.data.Dataset):
                 raise ValueError("augmented segments need 0 <= first frame < 2^32")
         remap = np.asarray([store.index_of(k) for k in table.channels], np.int32)
         dev = store.device
+        if redraw is not None:
+            # (with augmentation as well: every first frame a draw can give lies below its region's upper end, and _make_draw_table
+            # keeps those within int32 -- the check on 0 <= first < 2^32 is made there, once, not per epoch)
+            self._draw_table, self._draw_seed = self._make_draw_table(redraw, remap)
         self._chan = torch.from_numpy(remap[table.channel]).to(dev)
         self._first = torch.from_numpy(table.first_frame).to(dev)
         self._count = torch.from_numpy(table.n_frames).to(dev)
@@ -151,9 +162,38 @@ class LadDataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.table)
 
+    def _make_draw_table(self, redraw, remap):
+        """(sampling.DrawTable with channels as the store counts them, seed)."""
+        import sampling
+        table, store = self.table, self.store
+        frames = np.asarray([m.shape[0] for m in store.mats], np.int64)
+        if isinstance(redraw, str):
+            if redraw != 'window':
+                raise ValueError(f"redraw must be None, 'window' or a sampling.Sampler, got {redraw!r}")
+            if table.region_first is None or table.region_frames is None:
+                raise ValueError("redraw='window' needs a table with regions (segments.table_from_rows(..., keep_regions=True))")
+            chan = remap[table.channel]
+            lo = np.minimum(table.region_first, table.first_frame)
+            own_end = table.first_frame + table.n_frames
+            hi = np.maximum(np.minimum(table.region_first + table.region_frames, frames[chan]), own_end)
+            if len(table) and (int(lo.min()) < 0 or int(hi.max()) >= 2 ** 31 or np.any(hi <= lo)):
+                raise ValueError("redraw='window': a region is empty or lies outside 0 .. 2^31 - 1 frames")
+            n = len(table)
+            return sampling.DrawTable(np.zeros(n, np.int32), np.arange(n, dtype=np.int32), np.stack([chan, lo, hi], axis=1),
+                                      np.zeros(1, np.int32), np.zeros(n, np.int64), np.zeros(0, np.int64), table.frames_per_segment,
+                                      table.row_id, store.device), self._draw_seed
+        if len(redraw) != len(table) or list(redraw.pools.channels) != list(table.channels) or redraw.pools.T != table.frames_per_segment:
+            raise ValueError("the Sampler and the table differ in rows, channels or frames per segment (table = sampler.table())")
+        if len(redraw.pools.regions) and np.any(redraw.pools.regions[:, 2] > frames[remap[redraw.pools.regions[:, 0]]]):
+            raise ValueError("a region of the Sampler's pools ends past its channel's features in the store")
+        return redraw.draw_table(remap, store.device), redraw.seed
+
     def set_epoch(self, epoch):
-        """The epoch number of the batches to come (augmentation only: part of the random counter)."""
+        """The epoch number of the batches to come: part of the augmentation's random counter, and with `redraw` the table's windows
+        are drawn for it now."""
         self.epoch = int(epoch)
+        if self._draw_table is not None:
+            self._draw_table.draw(self._draw_seed, self.epoch, out=(self._chan, self._first, self._count))
 
     def __getitem__(self, cuts):
         idx = torch.as_tensor(cuts, dtype=torch.int64, device=self.store.device).view(-1)

@@ -110,13 +110,14 @@ class SegmentLoader:
 INDEX_SHUFFLE_SEED = 0
 
 
-def load_segment_table(cutset_dir, split, shuffle=False, seed=None, world=1, index_seed=INDEX_SHUFFLE_SEED):
+def load_segment_table(cutset_dir, split, shuffle=False, seed=None, world=1, index_seed=INDEX_SHUFFLE_SEED, keep_regions=False):
     """The epoch's segment order for `split` (host integers only, no GPU): `{split}_df.csv` -> index-time permutation
-    (compute_features.py:191-193) -> optional loader-time shuffle (load_data.py:27-28).  Identical on every rank."""
+    (compute_features.py:191-193) -> optional loader-time shuffle (load_data.py:27-28).  Identical on every rank.
+    keep_regions: the table also carries each row's (start, duration) region and its place in the CSV (redraw='window')."""
     if split not in ['train', 'dev', 'test']:
         raise ValueError(
             f"Unexpected value for split. Needs to be one of 'train, dev, test'. Found {split}")
-    table = segments.table_from_csv(os.path.join(cutset_dir, f'{split}_df.csv'))
+    table = segments.table_from_csv(os.path.join(cutset_dir, f'{split}_df.csv'), keep_regions=keep_regions)
     if index_seed is not None:
         table = table.shuffled(index_seed)
     if shuffle:
@@ -192,7 +193,7 @@ def _stored_features(manifest, path, num_filters, extractor=None):
 
 def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, audio_root=None, seed=None, rank=0,
                                world=1, store=None, index_seed=INDEX_SHUFFLE_SEED, feats_manifest=None, resample=False,
-                               augment=None, noise=None):
+                               augment=None, noise=None, redraw=None, transcripts=None, channels=None, redraw_seed=None):
     '''
     Create a dataloader for the provided split
         - split needs to be one of 'train', 'dev' and 'test'
@@ -214,37 +215,98 @@ def create_training_dataloader(cutset_dir, split, shuffle=False, batch_size=32, 
         - noise: what augment.mix_p mixes in.  'self': the channels of this split that hold at least a segment's frames (other
           speech, no extra data); a directory or a list of audio / .npy paths: featurised into the same store under the keys
           `noise:<file name without extension>`
+        - redraw: the training windows are drawn afresh on the GPU before every epoch (`loader.dataset.set_epoch(e)`: one launch of
+          csrc/sample.hip, a pure function of (redraw_seed, epoch, the row's place in the table)).  'window': the rows of
+          `{split}_df.csv`, each inside its own (start, duration) region, as Gillick et al. did.  'transcripts': the table is
+          sampling.SegmentPools.plan(config.SAMPLING['reference'], the meetings the CSV's meeting_id column names) over the
+          `transcripts` / `channels` tables (as sweep_eval.TranscriptIndex takes them); the CSV only says which meetings the
+          split holds and how its channels are keyed.  The index_seed / shuffle permutation is applied to the rows once; every
+          rank redraws the whole table from the same (seed, epoch), nothing is communicated.  Only for split 'train'.
+          None (the default): today's batches, bit for bit.  (`resample` is the audio's sampling rate, hence the name.)
+        - redraw_seed: default `seed`, or 0
     '''
     if noise is not None and augment is None:
         raise ValueError("noise channels without an augmentation config: pass augment=")
-    table = load_segment_table(cutset_dir, split, shuffle=shuffle, seed=seed, world=world, index_seed=index_seed)
+    if redraw is not None:
+        if redraw not in ('window', 'transcripts'):
+            raise ValueError(f"redraw must be None, 'window' or 'transcripts', got {redraw!r}")
+        if split != 'train':
+            raise ValueError(f"redraw is for the training split only (the {split} batches are never redrawn)")
+        if (redraw == 'transcripts') != (transcripts is not None and channels is not None):
+            raise ValueError("redraw='transcripts' needs the transcripts and channels tables, and only it takes them")
+        if redraw_seed is None:
+            redraw_seed = seed if seed is not None else 0
+    elif transcripts is not None or channels is not None or redraw_seed is not None:
+        raise ValueError("transcripts / channels / redraw_seed without redraw=")
+    table = load_segment_table(cutset_dir, split, shuffle=shuffle, seed=seed, world=world, index_seed=index_seed,
+                               keep_regions=redraw == 'window')
     if store is None:
         extractor = get_feat_extractor(num_samples=cfg.FEAT['num_samples'], num_filters=cfg.FEAT['num_filters'])
         store = FeatureStore(extractor)
     root = audio_root if audio_root is not None else cutset_dir
     manifest = read_feats_manifest(feats_manifest) if feats_manifest is not None else None
-    for key in table.channels:
-        if key not in store.keys:
-            path = key if os.path.isabs(key) else os.path.join(root, key)
-            if not os.path.exists(path):
-                for alt in (".wav", ".npy"):
-                    if os.path.exists(os.path.splitext(path)[0] + alt):
-                        path = os.path.splitext(path)[0] + alt
-                        break
-            stored = _stored_features(manifest, path, cfg.FEAT['num_filters'], getattr(store, 'extractor', None)) if manifest is not None else None
-            if stored is not None:
-                store.add_features(key, stored)
-            elif resample:
-                store.add_audio(key, load_audio_device(path, device=store.device, resample=True))
-            else:
-                store.add_audio(key, load_audio(path))
-    if augment is None:
+
+    def load_channels(keys):
+        for key in keys:
+            if key not in store.keys:
+                path = key if os.path.isabs(key) else os.path.join(root, key)
+                if not os.path.exists(path):
+                    for alt in (".wav", ".npy"):
+                        if os.path.exists(os.path.splitext(path)[0] + alt):
+                            path = os.path.splitext(path)[0] + alt
+                            break
+                stored = _stored_features(manifest, path, cfg.FEAT['num_filters'], getattr(store, 'extractor', None)) if manifest is not None else None
+                if stored is not None:
+                    store.add_features(key, stored)
+                elif resample:
+                    store.add_audio(key, load_audio_device(path, device=store.device, resample=True))
+                else:
+                    store.add_audio(key, load_audio(path))
+
+    sampler = None
+    if redraw == 'transcripts':
+        sampler, table = _transcript_sampler(os.path.join(cutset_dir, f'{split}_df.csv'), table.frames_per_segment, transcripts, channels,
+                                             store, load_channels, redraw_seed, shuffle, seed, world, index_seed)
+    load_channels(table.channels)
+    if redraw is not None:
+        dataset = LadDataset(store, table, augment=augment, noise=_noise_channels(store, noise, resample) if augment is not None else None,
+                             redraw=sampler if sampler is not None else 'window', redraw_seed=redraw_seed)
+    elif augment is None:
         dataset = LadDataset(store, table)
     else:
         dataset = LadDataset(store, table, augment=augment, noise=_noise_channels(store, noise, resample))
     # train-mode BatchNorm needs two segments per batch on every rank: a shorter ragged tail is dropped on all ranks alike
     return SegmentLoader(dataset, SegmentSampler(len(table), max_cuts=batch_size, rank=rank, world=world,
                                                  min_batch=2 if split == 'train' else 1))
+
+
+def _transcript_sampler(csv_path, T, transcripts, channels, store, load_channels, redraw_seed, shuffle, seed, world, index_seed):
+    """(sampling.Sampler, its epoch-0 SegmentTable) for redraw='transcripts': the plan of config.SAMPLING['reference'] for the
+    meetings the CSV's meeting_id column names, over pools that end where the channels' features in the store end, permuted once as
+    load_segment_table permutes the CSV's rows."""
+    import csv
+
+    import sampling
+    import sweep_eval
+    with open(csv_path, newline="") as f:
+        meetings = list(dict.fromkeys(r["meeting_id"] for r in csv.DictReader(f)))
+    rows = [r for r in sweep_eval._records(transcripts, sweep_eval.ROW_COLUMNS) if r["meeting_id"] in meetings]
+    chans = [c for c in sweep_eval._records(channels, sweep_eval.CHANNEL_COLUMNS) if c["meeting_id"] in meetings]
+    unknown = [m for m in meetings if m not in {c["meeting_id"] for c in chans}]
+    if unknown:
+        raise ValueError(f"the split names meetings the channel table does not hold: {unknown}")
+    keys = [sampling.channel_key(c["meeting_id"], c["chan"]) for c in chans if c["part_id"] not in (None, "")]
+    load_channels(keys)
+    frames = {k: int(store.mats[store.index_of(k)].shape[0]) for k in keys}
+    pools = sampling.SegmentPools.from_transcripts(rows, chans, fps=cfg.FEAT['num_samples'], T=T, frames=frames)
+    sampler = sampling.Sampler(pools, pools.plan('reference', meetings), redraw_seed, device=store.device)
+    if index_seed is not None:
+        sampler = sampler.take(np.random.default_rng(index_seed).permutation(len(sampler)))
+    if shuffle:
+        if seed is None and world > 1:
+            raise ValueError("shuffle=True in a data-parallel job needs an explicit seed (every rank must draw the same order)")
+        sampler = sampler.take(np.random.default_rng(seed).permutation(len(sampler)))
+    return sampler, sampler.table(0)
 
 
 def _noise_channels(store, noise, resample=False):

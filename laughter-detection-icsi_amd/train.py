@@ -213,7 +213,34 @@ def make_parser():
     parser.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed); the same on every rank')
     parser.add_argument('--noise', type=str, default=None,
                         help="what --augment mix / spec+mix mixes in: 'self' (the other training channels) or a directory of .wav / .npy files")
+    parser.add_argument('--redraw', type=str, default='none', choices=['none', 'window', 'transcripts'],
+                        help="redraw the training windows on the GPU before every epoch: 'window' inside each row's own (start, "
+                             "duration) region of train_df.csv, 'transcripts' from the transcript tables by config.SAMPLING['reference'] "
+                             "(train_df.csv then only names the split's meetings); the dev batches are never redrawn")
+    parser.add_argument('--redraw_seed', type=int, default=None, help='seed of the redraw (default: --seed); the same on every rank')
+    parser.add_argument('--transcripts', type=str, default=None, help='--redraw transcripts: the transcript CSV of evaluate_sweep.py')
+    parser.add_argument('--channels', type=str, default=None, help='--redraw transcripts: the channel CSV of evaluate_sweep.py')
     return parser
+
+
+def redraw_from_args(args):
+    """Keyword arguments of the training loader for the --redraw flags; a contradiction between them is a ValueError."""
+    tables = args.transcripts is not None or args.channels is not None
+    if args.redraw != 'transcripts' and tables:
+        raise ValueError("--transcripts / --channels without --redraw transcripts")
+    if args.redraw == 'none':
+        if args.redraw_seed is not None:
+            raise ValueError("--redraw_seed without --redraw window / transcripts")
+        return {}
+    kw = dict(redraw=args.redraw, redraw_seed=args.seed if args.redraw_seed is None else args.redraw_seed)
+    if args.redraw == 'transcripts':
+        if args.transcripts is None or args.channels is None:
+            raise ValueError("--redraw transcripts needs --transcripts CSV and --channels CSV")
+        import sweep_eval
+        from evaluate_sweep import read_csv
+        kw['transcripts'] = read_csv(args.transcripts, sweep_eval.ROW_COLUMNS, ("start", "end", "length"))
+        kw['channels'] = read_csv(args.channels, sweep_eval.CHANNEL_COLUMNS, ("length",))
+    return kw
 
 
 def augment_from_args(args):
@@ -232,6 +259,7 @@ def main(argv=None):
     warn_ignored_flags(args, parser)
     try:
         augment_cfg, noise = augment_from_args(args)
+        redraw_kw = redraw_from_args(args)
     except ValueError as e:
         raise SystemExit(f"train.py: {e}")
 
@@ -276,7 +304,9 @@ def main(argv=None):
                                                       audio_root=args.data_root, feats_manifest=manifests.get('dev'))
     train_loader = load_data.create_training_dataloader(data_dir, 'train', batch_size=batch_size, audio_root=args.data_root,
                                                         rank=rank, world=world, store=dev_loader.dataset.store,
-                                                        feats_manifest=manifests.get('train'), augment=augment_cfg, noise=noise)
+                                                        feats_manifest=manifests.get('train'), augment=augment_cfg, noise=noise, **redraw_kw)
+    if rank == 0 and redraw_kw:
+        print(f"Redraw: {args.redraw} (seed {redraw_kw['redraw_seed']}): {len(train_loader.dataset)} training windows drawn afresh every epoch")
     if rank == 0 and augment_cfg is not None:
         n_noise = len(train_loader.dataset.noise) if train_loader.dataset.noise is not None else 0
         print(f"Augmentation: {args.augment} (seed {augment_cfg.seed}, {n_noise} noise channels) on the training batches")
@@ -289,7 +319,7 @@ def main(argv=None):
     start = time.time()
     for epoch in range(args.num_epochs):
         t0 = time.time()
-        train_loader.dataset.set_epoch(model.epoch)   # (augmentation only: every epoch draws its own; model.epoch survives a restart)
+        train_loader.dataset.set_epoch(model.epoch)   # (augmentation, redraw: every epoch draws its own; model.epoch survives a restart)
         loss = run_epoch(model, train_loader, dev_loader, args.checkpoint_dir, log_frequency, batch_size, rows, reducer,
                          rank=rank, max_steps=args.max_steps, grad_accum=grad_accum)
         torch.cuda.synchronize()
