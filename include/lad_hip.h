@@ -691,6 +691,61 @@ int lad_score_runs(const void *runs_workspace, const int32_t *table, const int32
                    int64_t *scores, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Threshold sweep with hysteresis and gap filling (csrc/binarize.hip): the event tables of K settings in one pass.
+ * The reference has one threshold and a minimum length (laugh_segmenter.py:74-111); these are the two further controls of
+ * event-detection post-processing, onset / offset / min_duration_off of pyannote.audio's Binarize restated on this project's
+ * frame and time conventions (parity with pyannote itself is not pinned).  The text below IS the specification
+ * (tests/_binarize_model.py is a second implementation of it, a per-frame loop).
+ *
+ * Frames.  v[i] is the fixed probability in float64 exactly as lad_runs_count: p > 1 -> 1, p <= 0 -> 1e-7, anything else
+ * unchanged, NaN included; a float32 sample is widened exactly.
+ * Settings.  Setting k is (onsets[k], offsets[k], min_gaps[k]), doubles, all finite, offsets[k] <= onsets[k], min_gaps[k] >= 0.
+ * Masks.  H[i] = v[i] > onset, L[i] = v[i] > offset, compared in float64 whatever the track's type.  NaN is in neither, and H
+ * lies inside L.
+ * Hysteresis.  active[-1] = 0, active[i] = H[i] or (active[i - 1] and L[i]).  Equivalently every maximal run of L that holds at
+ * least one H frame yields exactly one run, from its first H frame to the end of the L run.  Consecutive hysteresis runs have
+ * at least one off frame between them: next.first - prev.last >= 2.
+ * Gap filling, per channel c.  Two consecutive hysteresis runs are joined iff NOT (next.first / fps[c] - prev.last / fps[c] >
+ * min_gap): float64, IEEE division, no reciprocal, contraction off -- the rule lad_score_runs uses for end - start > min_length.
+ * Joining is pairwise on the original neighbours, so chains collapse; a merged run is (first of its first, last of its last).
+ * min_gap = 0 never joins.
+ * Minimum length.  After gap filling, where it is for the plain sweep: with the caller, or in lad_score_runs.
+ * Reduction.  With offsets[k] == onsets[k] and min_gaps[k] == 0 the result is the run table of lad_runs_count / lad_runs_fill
+ * for thresholds[k] = onsets[k], bit for bit.
+ *
+ * Two steps, seven launches whatever K and channels are, no atomics (identical bytes on every call):
+ *   lad_binarize_count -> workspace: int32 counts[channels * K] at its start, the HYSTERESIS runs of channel c, setting k at
+ *                         c * K + k: an upper bound of the merged counts.  The caller copies them to the host to size the buffers.
+ *   lad_binarize_fill  -> raw_table: the hysteresis runs, table: the runs after gap filling, each int32[.][2], the (c, k)
+ *                         tables back to back in c * K + k order, rows ascending; the counts at the start of the workspace are
+ *                         REPLACED by the merged counts.  After that the workspace and `table` can be handed to lad_score_runs
+ *                         (n_thresholds = K, counts_host = the merged counts read back) as if lad_runs_count / lad_runs_fill had
+ *                         produced them.
+ * probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype).  onsets, offsets, min_gaps: HOST
+ * double[n_settings].  The tile is lad_runs_tile_frames() frames.
+ * ---------------------------------------------------------------------------------------------- */
+/* largest n_settings of one call (64) */
+int32_t lad_binarize_max_settings(void);
+/* bytes of workspace for lad_binarize_count / lad_binarize_fill; needs no GPU.  -1 and lad_last_error() for channels outside
+ * 1..65535, frames outside 1..2^30 or n_settings outside 1..lad_binarize_max_settings(). */
+int64_t lad_binarize_workspace_bytes(int64_t channels, int64_t frames, int32_t n_settings);
+/* counting step (three launches on `stream`).  LAD_ERR_INVALID with lad_last_error() set and nothing launched for sizes out of
+ * range, an unknown dtype, a null pointer, a non-finite onset or offset, or offsets[k] > onsets[k]. */
+int lad_binarize_count(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *onsets,
+                       const double *offsets, int32_t n_settings, void *workspace, void *stream);
+/* fill step (four launches on `stream`): same probs / onsets / offsets / workspace as the lad_binarize_count before it.
+ * fps: DEVICE double[channels]; fps_host: HOST copy of the same values, checked before anything is launched.  counts_host: HOST
+ * int32[channels * n_settings], the hysteresis counts the caller read back.  raw_table, table: DEVICE int32[capacity_runs][2]
+ * each, two different buffers.  LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for what
+ * lad_binarize_count refuses, a min_gap that is negative or not finite, an fps that is not positive and finite, counts that are
+ * not run counts of such a track, or counts that sum to more than capacity_runs.  The kernels never write or read a row at or
+ * beyond capacity_runs, whatever the workspace holds.  Counts that sum to 0 return LAD_OK without a launch. */
+int lad_binarize_fill(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *onsets,
+                      const double *offsets, const double *min_gaps, int32_t n_settings, const double *fps,
+                      const double *fps_host, void *workspace, const int32_t *counts_host, int32_t *raw_table,
+                      int32_t *table, int64_t capacity_runs, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sampling-rate conversion of one channel by up / down = sr_out / sr_in (reduced), polyphase FIR on the device.
  * Replaces the host resampling of the reference's readers: librosa.load(audio_path, sr=44100) in front of the wav cuts
  * (segment_laughter.py:134) and librosa.load(sr=8000) of the code it descends from (laugh_segmenter.py:157-185).

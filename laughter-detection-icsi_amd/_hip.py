@@ -173,6 +173,14 @@ SIGNATURES = {
     "lad_score_runs": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_void_p,
                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
                                ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
+    # threshold sweep with hysteresis and gap filling (csrc/binarize.hip)
+    "lad_binarize_max_settings": (c_i32, []),
+    "lad_binarize_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "lad_binarize_count": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_i32,
+                                   c_void_p, c_void_p]),
+    "lad_binarize_fill": (c_int, [c_void_p, c_i32, c_i64, c_i64] + [ctypes.POINTER(c_double)] * 3
+                          + [c_i32, c_void_p, ctypes.POINTER(c_double), c_void_p, ctypes.POINTER(c_i32), c_void_p, c_void_p, c_i64,
+                             c_void_p]),
     # sampling-rate conversion (csrc/resample.hip)
     "lad_resample_out_len": (c_i64, [c_i64, c_i32, c_i32]),
     "lad_resample_tile_outputs": (c_i32, []),

@@ -78,3 +78,12 @@ SAMPLING['reference'] = {
     'subsample_duration': 1.0,  # seconds: the segment length (config.py:56 of the reference)
     'random': False,
 }
+
+# Hysteresis / gap-filling presets (keyword arguments of laugh_segmenter.binarize_instances and of the offset_drops= / min_gaps=
+# axes of sweep_eval; the convention is in include/lad_hip.h next to lad_binarize_count).  The reference has neither control; 'off'
+# is its rule (one threshold, no joining), 'sweep' the two extra axes tools/bench_binarize.py times.  Nothing reads this unless asked.
+BINARIZE = {}
+
+BINARIZE['off'] = {'offset_drops': [0.0], 'min_gaps': [0.0]}
+
+BINARIZE['sweep'] = {'offset_drops': [0.0, 0.1, 0.2], 'min_gaps': [0.0, 0.1, 0.3]}

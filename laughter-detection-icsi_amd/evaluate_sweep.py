@@ -19,6 +19,9 @@ Writes `eval_df_per_meeting.csv` (the 14 columns of analyse.py:255-257) and `sum
 (csrc/runs.hip + csrc/score.hip through sweep_eval.score_sweep_device); both scorers write the same bytes.
 `--lowpass CUTOFF` (default: off) smooths every track first, as the reference's lowpass (laugh_segmenter.py:49-55) does before
 its thresholds: on the host with scipy, under the device scorer on the GPU (csrc/lowpass.hip) with each track's true length.
+`--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling to the sweep (laugh_segmenter.binarize_instances
+under the host scorer, csrc/binarize.hip under the device scorer): the CSVs get the columns offset_drop and min_gap behind min_len
+and the summary is grouped by all four.  Without the two flags the files are what they were.
 """
 import argparse
 import csv
@@ -72,7 +75,15 @@ def cutoff_arg(text):
     return value
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None):
+def float_list(text):
+    """--offset_drops / --min_gaps: a comma-separated list of non-negative numbers."""
+    values = [float(t) for t in text.split(',')]
+    if not all(np.isfinite(v) and v >= 0 for v in values):
+        raise argparse.ArgumentTypeError(f"finite values >= 0, got {text}")
+    return values
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
@@ -80,7 +91,7 @@ def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=
         padded[c, :len(t)] = t
     lengths = [len(t) for t in tracks] if lowpass is not None else None
     return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
-                                         lowpass=lowpass, lengths=lengths)
+                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps)
 
 
 def write_csv(path, columns, rows):
@@ -106,6 +117,12 @@ def build_parser():
                         help='smooth every track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards and '
                              'backwards (laugh_segmenter.lowpass under the host scorer, csrc/lowpass.hip under the device scorer; the '
                              "reference's own cutoff is 0.01); default: off")
+    parser.add_argument('--offset_drops', type=float_list, default=None,
+                        help='(not in the reference) comma-separated list: hysteresis, an event that starts above a threshold lasts '
+                             'until the track falls to or below threshold - drop; default: absent (no hysteresis axis)')
+    parser.add_argument('--min_gaps', type=float_list, default=None,
+                        help='(not in the reference) comma-separated list of seconds: events separated by a pause of at most this '
+                             'become one, before the min_length filter; default: absent (no gap-filling axis)')
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
 
@@ -124,18 +141,22 @@ def main(argv=None):
         for (meeting, chan), t in zip(channels, tracks):
             if len(t) <= 9:
                 raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
+    binarize = args.offset_drops is not None or args.min_gaps is not None
+    extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps) if binarize else {}
     if args.scorer == "device":
-        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass)
+        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra)
     else:
         if args.lowpass is not None:
             import laugh_segmenter
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
-        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index)
-    per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index)
+        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra)
+    per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
     os.makedirs(args.out_dir, exist_ok=True)
-    write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"), sweep_eval.EVAL_COLUMNS, per_meeting)
-    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), sweep_eval.SUM_COLUMNS, sweep_eval.calc_sum_stats(per_meeting))
-    print(f"{len(channels)} channels, {len(thresholds) * len(min_lengths)} settings ({args.scorer} scorer): "
+    write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"),
+              sweep_eval.EVAL_COLUMNS_BINARIZE if binarize else sweep_eval.EVAL_COLUMNS, per_meeting)
+    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), sweep_eval.SUM_COLUMNS_BINARIZE if binarize else sweep_eval.SUM_COLUMNS,
+              sweep_eval.calc_sum_stats(per_meeting, binarize=binarize))
+    print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 
 

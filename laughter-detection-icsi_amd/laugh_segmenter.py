@@ -11,7 +11,14 @@ The Gillick-era MFCC code below laugh_segmenter.py:115 is dead in the reference 
 `get_laughter_instances_device` / `get_laughter_frame_spans_device` are the opt-in device form of the same sweep for a track that
 is already in GPU memory (csrc/runs.hip: the run tables of all thresholds, and of several channels, in four launches): only the
 compact tables cross to the host, and the dictionary is the host function's bit for bit.  They have no CPU fallback.
+
+`binarize_frame_spans` / `binarize_instances` add the two further controls of event-detection post-processing, which the reference
+does not have: hysteresis (an event starts above an onset threshold and lasts until the track falls to or below a lower offset
+threshold) and gap filling (events separated by a short pause become one, before the minimum-length filter).  The convention is
+written out in include/lad_hip.h (lad_binarize_count).  `binarize_frame_spans_device` / `binarize_instances_device` are their
+device forms (csrc/binarize.hip), with the same results and no CPU fallback.
 """
+import math
 import ctypes
 
 import numpy as np
@@ -187,3 +194,171 @@ def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fp
             keep = length > min_l
             instance_dict[(thr, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
     return {(thr, min_l): instance_dict[(thr, min_l)] for thr in thresholds for min_l in min_lengths}
+
+
+# ---- hysteresis and gap filling (include/lad_hip.h: lad_binarize_count has the convention) ----------------------------------------
+def _check_setting(onset, offset, min_gap):
+    onset, offset, min_gap = float(onset), float(offset), float(min_gap)
+    if not (math.isfinite(onset) and math.isfinite(offset) and math.isfinite(min_gap)):
+        raise ValueError(f"onset, offset and min_gap must be finite, got ({onset}, {offset}, {min_gap})")
+    if offset > onset:
+        raise ValueError(f"offset {offset} lies above onset {onset}")
+    if min_gap < 0:
+        raise ValueError(f"min_gap must be >= 0, got {min_gap}")
+    return onset, offset, min_gap
+
+
+def _check_fps(fps):
+    fps = float(fps)
+    if not (math.isfinite(fps) and fps > 0):
+        raise ValueError(f"fps must be positive and finite, got {fps}")
+    return fps
+
+
+def _hysteresis_spans(p, onset, offset):
+    """p: fixed probabilities.  Every maximal run of p > offset that holds a frame with p > onset -> (its first such frame, the
+    end of the run): int64 (n, 2)."""
+    held = run_spans(p > offset)
+    if len(held) == 0:
+        return held
+    onsets = np.flatnonzero(p > onset)
+    at = np.searchsorted(onsets, held[:, 0], side="left")             # the first onset frame at or behind the run's start
+    first = onsets[np.minimum(at, len(onsets) - 1)] if len(onsets) else np.zeros(len(held), np.int64)
+    has = (at < len(onsets)) & (first <= held[:, 1])
+    return np.stack([first[has], held[has, 1]], axis=1).astype(np.int64)
+
+
+def _fill_gaps(spans, min_gap, fps):
+    """Consecutive runs are joined iff not (next.first / fps - prev.last / fps > min_gap), pairwise on the original neighbours."""
+    if len(spans) < 2:
+        return spans
+    head = np.concatenate([[True], spans[1:, 0] / fps - spans[:-1, 1] / fps > min_gap])
+    tail = np.concatenate([head[1:], [True]])
+    return np.stack([spans[head, 0], spans[tail, 1]], axis=1)
+
+
+def binarize_frame_spans(probs, onset, offset, min_gap=0.0, fps=100.):
+    """Integer (first_frame, last_frame) events of one setting: hysteresis between `onset` and `offset` (offset <= onset), then
+    gap filling by `min_gap` seconds at `fps` frames per second.  int64 (n, 2).  offset == onset and min_gap == 0 is
+    get_laughter_frame_spans(probs, onset)."""
+    onset, offset, min_gap = _check_setting(onset, offset, min_gap)
+    return _fill_gaps(_hysteresis_spans(fix_probs(probs), onset, offset), min_gap, np.float64(_check_fps(fps)))
+
+
+def _binarize_keys(thresholds, offset_drops, min_gaps):
+    for drop in offset_drops:
+        if not (math.isfinite(float(drop)) and float(drop) >= 0):
+            raise ValueError(f"an offset drop must be finite and >= 0, got {drop}")
+    triples = [(thr, drop, gap) for thr in thresholds for drop in offset_drops for gap in min_gaps]
+    settings = [_check_setting(thr, thr - drop, gap) for thr, drop, gap in triples]        # offset = thr - drop, once, Python float
+    return triples, settings
+
+
+def _instances_from_spans(triples, spans_list, min_lengths, fps):
+    instance_dict = {}
+    for (thr, drop, gap), spans in zip(triples, spans_list):
+        starts, ends = spans[:, 0] / fps, spans[:, 1] / fps
+        length = ends - starts
+        for min_l in min_lengths:
+            keep = length > min_l
+            instance_dict[(thr, drop, gap, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
+    return instance_dict
+
+
+def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+    """{(threshold, offset_drop, min_gap, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then drop, then gap, then
+    min_length.  The onset is the threshold and the offset is threshold - offset_drop (drop >= 0); events are (first / fps,
+    last / fps) and kept iff end - start > min_length, after gap filling.  drop = 0 and gap = 0 give the lists of
+    get_laughter_instances."""
+    thresholds, min_lengths, offset_drops, min_gaps = list(thresholds), list(min_lengths), list(offset_drops), list(min_gaps)
+    triples, settings = _binarize_keys(thresholds, offset_drops, min_gaps)
+    fps = np.float64(_check_fps(fps))
+    p = fix_probs(probs)
+    held = {}
+    spans_list = []
+    for onset, offset, gap in settings:
+        if (onset, offset) not in held:
+            held[(onset, offset)] = _hysteresis_spans(p, onset, offset)
+        spans_list.append(_fill_gaps(held[(onset, offset)], gap, fps))
+    return _instances_from_spans(triples, spans_list, min_lengths, fps)
+
+
+def _device_binarize(probs, settings, fps_host, extra_bytes=0):
+    """lad_binarize_count + lad_binarize_fill for at most lad_binarize_max_settings() settings.  probs: (C, T) float32 / float64 GPU
+    tensor, T >= 1; settings: [(onset, offset, min_gap)]; fps_host: float64 numpy (C,).  Everything stays on the device: returns
+    (workspace, table, counts, fps_dev) with `workspace` a uint8 tensor whose first lad_binarize_workspace_bytes bytes are the
+    binarize workspace (the merged counts at its start) followed by extra_bytes for the caller, `table` the merged (total, 2) int32
+    tables back to back, and counts the merged counts, int32 numpy (C * K,)."""
+    import torch
+
+    import _hip
+    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
+        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    _hip.require_cuda(probs, "probs")
+    lib = _hip.lib()
+    C, T = probs.shape
+    K = len(settings)
+    f64p, i32p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    cols = [(ctypes.c_double * max(K, 1))(*[float(s[j]) for s in settings]) for j in range(3)]
+    dtype = 0 if probs.dtype == torch.float32 else 1     # lad_runs_dtype
+    ws_bytes = lib.lad_binarize_workspace_bytes(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_binarize_workspace_bytes")
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
+        fps_dev = torch.from_numpy(fps_host).to(probs.device)
+        _hip.check(lib.lad_binarize_count(_hip.ptr(probs), dtype, C, T, cols[0], cols[1], K, _hip.ptr(ws), stream),
+                   "lad_binarize_count")
+        raw_counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
+        total = int(raw_counts.sum(dtype=np.int64))
+        both = torch.empty((2, max(total, 1), 2), dtype=torch.int32, device=probs.device)
+        _hip.check(lib.lad_binarize_fill(_hip.ptr(probs), dtype, C, T, cols[0], cols[1], cols[2], K, _hip.ptr(fps_dev),
+                                         fps_host.ctypes.data_as(f64p), _hip.ptr(ws), raw_counts.ctypes.data_as(i32p),
+                                         _hip.ptr(both[0]), _hip.ptr(both[1]), total, stream), "lad_binarize_fill")
+        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())         # the merged counts
+        return ws, both[1][:int(counts.sum(dtype=np.int64))], counts, fps_dev
+
+
+def _fps_per_channel(fps, C):
+    f = [fps] * C if np.ndim(fps) == 0 else list(fps)
+    if len(f) != C:
+        raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
+    return np.asarray([_check_fps(x) for x in f], dtype=np.float64)
+
+
+def binarize_frame_spans_device(probs, settings, fps=100.):
+    """Device form of binarize_frame_spans for a list of settings (onset, offset, min_gap).  probs: (T,) GPU tensor (float32 /
+    float64, contiguous) -> [int64 (n, 2) array per setting], each equal to binarize_frame_spans(probs.cpu(), *setting, fps);
+    (C, T) -> one such list per channel, fps a float or one per channel.  More settings than lad_binarize_max_settings() are
+    split into several calls.  No CPU fallback."""
+    import _hip
+    settings = [_check_setting(*s) for s in settings]
+    single = getattr(probs, "ndim", None) == 1
+    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
+    if getattr(p2, "ndim", None) != 2:
+        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device sweep has no CPU fallback)")
+    C, T = p2.shape
+    fps_host = _fps_per_channel(fps, C)
+    out = [[] for _ in range(C)]
+    if T == 0 or C == 0 or not settings:
+        _hip.require_cuda(p2, "probs")
+        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
+    else:
+        step = int(_hip.lib().lad_binarize_max_settings())
+        for k0 in range(0, len(settings), step):
+            _, table, counts, _ = _device_binarize(p2, settings[k0:k0 + step], fps_host)
+            part = _split_tables(counts.astype(np.int64).reshape(C, -1), table.cpu().numpy())
+            for c in range(C):
+                out[c] += part[c]
+    return out[0] if single else out
+
+
+def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+    """binarize_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
+    import _hip
+    if getattr(probs, "ndim", None) != 1:
+        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
+    thresholds, min_lengths, offset_drops, min_gaps = list(thresholds), list(min_lengths), list(offset_drops), list(min_gaps)
+    triples, settings = _binarize_keys(thresholds, offset_drops, min_gaps)
+    fps = np.float64(_check_fps(fps))
+    return _instances_from_spans(triples, binarize_frame_spans_device(probs, settings, fps), min_lengths, fps)

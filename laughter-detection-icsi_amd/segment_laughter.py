@@ -24,6 +24,10 @@ cross to the host, and the track itself only when `--save_probs` asks for it.  S
 `--lowpass CUTOFF` (default: off) smooths the track before the sweep with the reference's `lowpass` (laugh_segmenter.py:49-55,
 which segment_laughter.py:107-108 leaves commented out): scipy on the host under `--segmenter host`, csrc/lowpass.hip under
 `--segmenter device`, where the track still never leaves the GPU.  `--save_probs` keeps writing the raw track.
+
+`--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling (laugh_segmenter.binarize_instances, or
+csrc/binarize.hip under `--segmenter device`): the instances of setting (thr, drop, gap, min_len) go to
+`t_<thr>/l_<min_len>/d_<drop>_g_<gap>/`.  Without the two flags paths and bytes are what they were.
 """
 import argparse
 import os
@@ -108,12 +112,13 @@ def save_audio_instances(instances, audio_path, output_dir, rate=None):
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
-                  save_audio_rate=None, lowpass=None):
+                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
     (None: the file's own).  lowpass: a cutoff (of Nyquist): the track is smoothed before the sweep (segment_laughter.py:107-108), on
-    the host or on the device like the sweep itself; save_probs still gets the raw track."""
+    the host or on the device like the sweep itself; save_probs still gets the raw track.
+    offset_drops / min_gaps (either given): hysteresis and gap filling; the dictionary's keys are (thr, drop, gap, min_len)."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if save_to_audio_files and output_dir is None:
@@ -131,18 +136,29 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     if lowpass is not None and (segmenter == "host" or rank == 0):
         probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
             laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
-    if segmenter == "host":
-        instance_dict = laugh_segmenter.get_laughter_instances(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
-    elif rank == 0:
-        instance_dict = laugh_segmenter.get_laughter_instances_device(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps)
+    binarize = offset_drops is not None or min_gaps is not None
+    if binarize:
+        extra = dict(offset_drops=list(offset_drops) if offset_drops is not None else [0.0],
+                     min_gaps=list(min_gaps) if min_gaps is not None else [0.0])
+        sweep = laugh_segmenter.binarize_instances if segmenter == "host" else laugh_segmenter.binarize_instances_device
+    else:
+        extra = {}
+        sweep = laugh_segmenter.get_laughter_instances if segmenter == "host" else laugh_segmenter.get_laughter_instances_device
+    if segmenter == "host" or rank == 0:
+        instance_dict = sweep(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps, **extra)
     else:
         instance_dict = {}
     sweep_time = time.time() - start_time - predict_time
     if rank == 0:
         for setting, instances in instance_dict.items():
-            if verbose:
+            if verbose and binarize:
+                print(f"Found {len(instances)} laughs for threshold {setting[0]}, offset drop {setting[1]}, min_gap {setting[2]} and "
+                      f"min_length {setting[3]}.")
+            elif verbose:
                 print(f"Found {len(instances)} laughs for threshold {setting[0]} and min_length {setting[1]}.")
-            out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[1]}')
+            out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[-1]}')
+            if binarize:
+                out_dir = os.path.join(out_dir, f'd_{setting[1]}_g_{setting[2]}')
             if save_to_textgrid or (save_to_audio_files and len(instances) > 0):
                 os.makedirs(out_dir, exist_ok=True)
             if save_to_audio_files and len(instances) > 0:
@@ -168,6 +184,14 @@ def cutoff_arg(text):
     return value
 
 
+def float_list(text):
+    """--offset_drops / --min_gaps: a comma-separated list of non-negative numbers."""
+    values = [float(t) for t in text.split(',')]
+    if not all(np.isfinite(v) and v >= 0 for v in values):
+        raise argparse.ArgumentTypeError(f"finite values >= 0, got {text}")
+    return values
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--model_path', type=str, default='checkpoints/in_use/resnet_with_augmentation')
@@ -191,6 +215,12 @@ def build_parser():
                         help="smooth the probability track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards "
                              "and backwards (the reference's lowpass, cutoff 0.01, which it leaves commented out); on the host or the "
                              "GPU as --segmenter says; default: off")
+    parser.add_argument('--offset_drops', type=float_list, default=None,
+                        help="(not in the reference) comma-separated list: hysteresis, an instance that starts above a threshold lasts "
+                             "until the track falls to or below threshold - drop; default: absent")
+    parser.add_argument('--min_gaps', type=float_list, default=None,
+                        help="(not in the reference) comma-separated list of seconds: instances separated by a pause of at most this "
+                             "become one, before the min_length filter; default: absent")
     parser.add_argument('--resample', type=str, default='False',
                         help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
                              "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
@@ -220,7 +250,7 @@ def main(argv=None):
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
                   segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
-                  lowpass=args.lowpass)
+                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps)
 
 
 if __name__ == '__main__':

@@ -11,6 +11,8 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
     score_sweep_host       the host sweep + score_instances for several tracks -> int64 (C, K, L, 7)
     score_sweep_device     the same array for tracks in GPU memory (csrc/runs.hip + csrc/score.hip): besides the C x K run counts
                            only the scores cross to the host.  No CPU fallback.
+                           Both take offset_drops= / min_gaps= (hysteresis and gap filling: laugh_segmenter.binarize_instances,
+                           csrc/binarize.hip) and then return (C, K, D, G, L, 7).
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
 
@@ -26,6 +28,9 @@ EVAL_COLUMNS = ["meeting", "threshold", "min_len", "precision", "recall", "corr_
                 "num_of_pred_laughs", "valid_pred_laughs", "num_of_transc_laughs", "tot_fp_speech_time", "tot_fp_noise_time",
                 "tot_fp_silence_time"]                                # analyse.py:255-257
 SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.py:290
+# with the hysteresis / gap-filling axes (not in the reference): offset_drop and min_gap follow min_len
+EVAL_COLUMNS_BINARIZE = EVAL_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVAL_COLUMNS[3:]
+SUM_COLUMNS_BINARIZE = SUM_COLUMNS[:2] + ["offset_drop", "min_gap"] + SUM_COLUMNS[2:]
 ROW_COLUMNS = ("meeting_id", "part_id", "chan", "start", "end", "length", "type", "laugh_type")
 CHANNEL_COLUMNS = ("meeting_id", "part_id", "chan", "length")
 FACTOR = 1000.0                # utils.py:14: 1000 / frame_duration, frame_duration = 1 ms (config.py:46-52)
@@ -263,12 +268,33 @@ def _fps_list(fps, C):
     return f
 
 
-def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index):
+def _binarize_axes(offset_drops, min_gaps):
+    """None, or the two extra axes as lists (one given: the other is [0.0], which changes nothing)."""
+    if offset_drops is None and min_gaps is None:
+        return None
+    return (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
+
+
+def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None):
     """laugh_segmenter.get_laughter_instances + score_instances per track -> int64 (C, K, L, 7).  tracks: C arrays (lengths may
-    differ); channels: C (meeting_id, chan); fps: a float or C floats."""
+    differ); channels: C (meeting_id, chan); fps: a float or C floats.
+    offset_drops / min_gaps (either given): laugh_segmenter.binarize_instances instead -- hysteresis with offset = threshold - drop
+    and gap filling -> int64 (C, K, D, G, L, 7)."""
     import laugh_segmenter as ls
     thresholds, min_lengths = list(thresholds), list(min_lengths)
     f = _fps_list(fps, len(channels))
+    axes = _binarize_axes(offset_drops, min_gaps)
+    if axes is not None:
+        drops, gaps = axes
+        out = np.zeros((len(channels), len(thresholds), len(drops), len(gaps), len(min_lengths), len(FIELDS)), np.int64)
+        for c, (track, mc) in enumerate(zip(tracks, channels)):
+            got = score_instances(ls.binarize_instances(track, thresholds, min_lengths, f[c], drops, gaps), index, *mc)
+            for k, thr in enumerate(thresholds):
+                for d, drop in enumerate(drops):
+                    for g, gap in enumerate(gaps):
+                        for l, min_l in enumerate(min_lengths):
+                            out[c, k, d, g, l] = got[(thr, drop, gap, min_l)]
+        return out
     out = np.zeros((len(channels), len(thresholds), len(min_lengths), len(FIELDS)), np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
         got = score_instances(ls.get_laughter_instances(track, thresholds, min_lengths, f[c]), index, *mc)
@@ -278,13 +304,17 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index):
     return out
 
 
-def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None):
+def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
+                       min_gaps=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
     TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
     the run tables never leave the device.
     lowpass: a cutoff (of Nyquist): every track is smoothed on the device first (laugh_segmenter.lowpass_device: lad_lowpass before
-    lad_runs_count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN)."""
+    lad_runs_count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN).
+    offset_drops / min_gaps (either given): hysteresis with offset = threshold - drop and gap filling -> int64 (C, K, D, G, L, 7),
+    equal to score_sweep_host with the same two lists: lad_binarize_count + lad_binarize_fill + the same lad_score_runs, at most
+    lad_binarize_max_settings() of the K * D * G settings per round; the low-pass composes in front as above."""
     import torch
 
     import _hip
@@ -301,8 +331,9 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     if C != len(channels):
         raise ValueError(f"{C} tracks for {len(channels)} channels")
     f = _fps_list(fps, C)
-    out_shape = (C, K, L, len(FIELDS))
-    if C == 0 or T == 0 or K == 0 or L == 0:
+    axes = _binarize_axes(offset_drops, min_gaps)
+    out_shape = (C, K, L, len(FIELDS)) if axes is None else (C, K, len(axes[0]), len(axes[1]), L, len(FIELDS))
+    if T == 0 or 0 in out_shape:
         return np.zeros(out_shape, np.int64)
     if lowpass is not None:
         import laugh_segmenter as ls
@@ -318,6 +349,8 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     fps_host = np.asarray(f, dtype=np.float64)
     dtype = 0 if probs.dtype == torch.float32 else 1                               # lad_runs_dtype
     i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    if axes is not None:
+        return _score_binarized(probs, dix, thresholds, axes, mls, L, fps_host, out_shape)
     ws_bytes = lib.lad_runs_workspace_bytes(C, T, K)
     _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_runs_workspace_bytes")
     sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, K, L)
@@ -342,11 +375,53 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         return scores.cpu().numpy()
 
 
-def eval_rows(scores, channels, thresholds, min_lengths, index):
+def _score_binarized(probs, dix, thresholds, axes, mls, L, fps_host, out_shape):
+    """The (C, K, D, G, L, 7) scores of score_sweep_device: rounds of at most lad_binarize_max_settings() settings, each
+    lad_binarize_count + lad_binarize_fill + lad_score_runs with the round's settings in the place of the thresholds."""
+    import torch
+
+    import _hip
+    import laugh_segmenter as ls
+    lib = _hip.lib()
+    C, T = probs.shape
+    _, settings = ls._binarize_keys(thresholds, axes[0], axes[1])
+    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    step = int(lib.lad_binarize_max_settings())
+    parts = []
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        for k0 in range(0, len(settings), step):
+            chunk = settings[k0:k0 + step]
+            n = len(chunk)
+            sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
+            _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
+            ws, table, counts, fps_dev = ls._device_binarize(probs, chunk, fps_host, extra_bytes=sws_bytes)
+            sws = ws[ws.numel() - sws_bytes:]
+            scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
+            if len(table) == 0:
+                table = torch.zeros((1, 2), dtype=torch.int32, device=probs.device)
+            _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
+                                          _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
+                                          dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
+                                          fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(sws), _hip.ptr(scores), stream),
+                       "lad_score_runs")
+            parts.append(scores.cpu().numpy())
+    return np.concatenate(parts, axis=1).reshape(out_shape)
+
+
+def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None):
     """eval_preds (analyse.py:152-225) for every meeting and setting: a list of 14-value rows in EVAL_COLUMNS order, meetings
     ascending, thresholds-major.  scores: (C, K, L, 7) of score_sweep_host / score_sweep_device for `channels`.  Channels without a
-    participant are left out (analyse.py:27-28); the float sums run over participants in ascending part_id order (:173-197)."""
+    participant are left out (analyse.py:27-28); the float sums run over participants in ascending part_id order (:173-197).
+    offset_drops / min_gaps (either given): scores is (C, K, D, G, L, 7) and a row has the 16 values of EVAL_COLUMNS_BINARIZE
+    (offset_drop and min_gap behind min_len), thresholds-major, then drop, then gap, then min_len."""
     scores = np.asarray(scores)
+    axes = _binarize_axes(offset_drops, min_gaps)
+    if axes is None:
+        settings = [((k, l), (thr, min_l)) for k, thr in enumerate(thresholds) for l, min_l in enumerate(min_lengths)]
+    else:
+        settings = [((k, d, g, l), (thr, min_l, drop, gap)) for k, thr in enumerate(thresholds) for d, drop in enumerate(axes[0])
+                    for g, gap in enumerate(axes[1]) for l, min_l in enumerate(min_lengths)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
         part = index.participant(m, chan)
@@ -357,46 +432,47 @@ def eval_rows(scores, channels, thresholds, min_lengths, index):
         parts = sorted(per_meeting[m])
         tot_transc = index.tot_len(m, "laugh")
         n_transc = index.num_laugh_rows(m)
-        for k, thr in enumerate(thresholds):
-            for l, min_l in enumerate(min_lengths):
-                corr_t = incorr_t = speech_t = noise_t = silence_t = 0
-                n_pred = n_valid = 0
-                for _, c in parts:
-                    s = [int(v) for v in scores[c, k, l]]
-                    n_pred += s[0]
-                    n_valid += s[1]
-                    if s[0] == 0:
-                        continue                                                   # (no row of this participant: groupby skips it)
-                    pred_length = to_sec(s[2])                                     # laugh_match :133-145
-                    correct = to_sec(s[3])
-                    corr_t += correct
-                    incorr_t += pred_length - correct
-                    speech_t += to_sec(s[4])
-                    noise_t += to_sec(s[5])
-                    silence_t += to_sec(s[6])
-                pred_t = corr_t + incorr_t
-                prec = 1 if pred_t == 0 else corr_t / pred_t
-                recall = float("nan") if tot_transc == 0 else corr_t / tot_transc
-                rows.append([m, thr, min_l, prec, recall, corr_t, pred_t, tot_transc, n_pred, n_valid, n_transc, speech_t, noise_t,
-                             silence_t])
+        for at, key in settings:
+            corr_t = incorr_t = speech_t = noise_t = silence_t = 0
+            n_pred = n_valid = 0
+            for _, c in parts:
+                s = [int(v) for v in scores[(c,) + at]]
+                n_pred += s[0]
+                n_valid += s[1]
+                if s[0] == 0:
+                    continue                                                       # (no row of this participant: groupby skips it)
+                pred_length = to_sec(s[2])                                         # laugh_match :133-145
+                correct = to_sec(s[3])
+                corr_t += correct
+                incorr_t += pred_length - correct
+                speech_t += to_sec(s[4])
+                noise_t += to_sec(s[5])
+                silence_t += to_sec(s[6])
+            pred_t = corr_t + incorr_t
+            prec = 1 if pred_t == 0 else corr_t / pred_t
+            recall = float("nan") if tot_transc == 0 else corr_t / tot_transc
+            rows.append([m, *key, prec, recall, corr_t, pred_t, tot_transc, n_pred, n_valid, n_transc, speech_t, noise_t, silence_t])
     return rows
 
 
-def calc_sum_stats(rows):
+def calc_sum_stats(rows, binarize=False):
     """analyse.py:269-298: per (min_len, threshold) the sums of corr_pred_time, tot_pred_time and tot_transc_laugh_time over the
     meetings (in row order), precision = corr / pred (1 where pred is 0), recall = corr / transcribed (float division: NaN or inf
-    where that is 0).  Rows of SUM_COLUMNS, ordered by (min_len, threshold) as the groupby."""
+    where that is 0).  Rows of SUM_COLUMNS, ordered by (min_len, threshold) as the groupby.
+    binarize: the rows are eval_rows' 16-value ones; grouped by (min_len, threshold, offset_drop, min_gap), rows of
+    SUM_COLUMNS_BINARIZE."""
+    n_keys = 4 if binarize else 2
     sums = {}
     for r in rows:
-        acc = sums.setdefault((r[2], r[1]), [0, 0, 0])
-        acc[0] += r[5]
-        acc[1] += r[6]
-        acc[2] += r[7]
+        acc = sums.setdefault((r[2], r[1]) + tuple(r[3:1 + n_keys]), [0, 0, 0])
+        acc[0] += r[1 + n_keys + 2]
+        acc[1] += r[1 + n_keys + 3]
+        acc[2] += r[1 + n_keys + 4]
     out = []
-    for (min_l, thr) in sorted(sums):
-        corr, pred, transc = (np.float64(v) for v in sums[(min_l, thr)])
+    for key in sorted(sums):
+        corr, pred, transc = (np.float64(v) for v in sums[key])
         with np.errstate(divide="ignore", invalid="ignore"):
             prec = 1.0 if pred == 0 else float(corr / pred)
             recall = float(corr / transc)
-        out.append([thr, min_l, prec, recall])
+        out.append([key[1], key[0], *key[2:], prec, recall])
     return out
