@@ -1,13 +1,13 @@
 // Threshold sweep with hysteresis and gap filling: for K settings (onset, offset, min_gap) at once, the table of events
 // (first_frame, last_frame) of a probability track.  The convention is written out in include/lad_hip.h; in short, with
-// v the fixed probability in float64 (as runs.hip), H = v > onset, L = v > offset (offset <= onset, so H is inside L):
+// v the fixed probability in float64 (load_fixed), H = v > onset, L = v > offset (offset <= onset, so H is inside L):
 //   hysteresis   active[i] = H[i] or (active[i - 1] and L[i]), active[-1] = 0: every maximal run of L that holds an H frame gives
 //                one run, from its first H frame to the end of the L run
 //   gap filling  consecutive hysteresis runs are joined iff not (next.first / fps - prev.last / fps > min_gap), float64
 // offset == onset and min_gap == 0 is the plain sweep of runs.hip, bit for bit.
 //
 // A frame's state depends on an unbounded past, so a tile cannot decide alone.  It resolves itself for BOTH carry-ins instead:
-//   binarize_tile_kernel  one wave owns a tile of 512 frames as 8 ballot words (runs.hip's layout).  For a setting, a seed S inside
+//   binarize_tile_kernel  one wave owns a tile of 512 frames as 8 ballot words (lad_sweep_tile.h).  For a setting, a seed S inside
 //                         L floods upwards through L's ones as the carry chain of the multi-word add X = L + S + carry-in: inside a
 //                         run of ones the sum leaves the bits below the first seed alone, clears the first seed and carries out at
 //                         the top, so active = ((X ^ L) | S) & L.  Stored per (channel, setting, tile): the number of run starts
@@ -17,7 +17,7 @@
 //                         composition; its exclusive scan evaluated at active[-1] = 0 is each tile's carry-in and the rank of its
 //                         first start, its total the number of hysteresis runs
 //   binarize_rows_kernel  exclusive scan of the C * K run counts: each raw table's first row (and the total behind the last)
-//   binarize_fill_kernel  the tile pass again with the resolved carry-in: starts and ends placed by rank (as runs_fill_kernel)
+//   binarize_fill_kernel  the tile pass again with the resolved carry-in: starts and ends placed by rank (place_runs)
 //                         into the raw table
 //   binarize_heads_kernel / binarize_base_kernel / binarize_merge_kernel
 //                         over the raw table: a row is a head unless it joins the row before it in the same (channel, setting);
@@ -27,19 +27,11 @@
 // Seven launches whatever K and C are (three to count, four to fill).  No atomic anywhere: rows ascend by construction and two
 // calls write the same bytes.  Every table store is guarded by the caller's capacity, every raw-table read too.  No scratch.
 #pragma clang fp contract(off)
-#include <cmath>
-
-#include "lad_common.h"
+// The tile geometry, the limits, the fixed load, starts / ends and their placement by rank, and the scan are lad_sweep_tile.h's.
+#include "lad_sweep_tile.h"
 
 namespace {
-constexpr int WAVE = 64;
-constexpr int WORDS = 8;                    // 64-frame words per tile
-constexpr int TILE = WAVE * WORDS;          // frames per wave: lad_runs_tile_frames()
-constexpr int WAVES = 4;                    // tiles per workgroup
-constexpr int THREADS = WAVE * WAVES;
-constexpr int MAX_K = 64;                   // settings per call: lane k of a wave carries setting k's count / first row
-constexpr int64_t MAX_T = (int64_t)1 << 30; // frame indices and per-setting run counts are int32
-constexpr int MAX_C = 65535;                // grid.y
+using namespace lad::sweep;
 constexpr int SLICES = 16;                  // workgroups that share one raw table in the run-level passes
 
 struct Settings {
@@ -49,23 +41,12 @@ struct Gaps {
     double v[MAX_K];
 };
 
-// fix_over_underflow in float64, as runs.hip
-template <typename T>
-__device__ inline double load_fixed(const T *__restrict__ p, int64_t i, int64_t n) {
-    if (i < 0 || i >= n) return __builtin_nan("");   // beyond the track: in neither mask
-    double v = (double)p[i];
-    if (v > 1.0) v = 1.0;
-    else if (v <= 0.0) v = 0.0000001;
-    return v;
-}
-
 template <typename T>
 struct TileRegs {
     double v[WORDS];
     double after;   // the frame behind the tile (every lane holds it: one address, one cache line)
     __device__ inline void load(const T *__restrict__ chan, int64_t tile0, int64_t n, int lane) {
-#pragma unroll
-        for (int j = 0; j < WORDS; ++j) v[j] = load_fixed(chan, tile0 + j * WAVE + lane, n);
+        load_tile(chan, tile0, n, lane, v);
         after = load_fixed(chan, tile0 + TILE, n);
     }
     __device__ inline void masks(double onset, double offset, unsigned long long (&H)[WORDS], unsigned long long (&L)[WORDS]) const {
@@ -91,15 +72,6 @@ __device__ inline void resolve(const unsigned long long (&H)[WORDS], const unsig
         A[j] = ((y ^ L[j]) | H[j]) & L[j];
         c = c1 | c2;
     }
-}
-
-__device__ inline unsigned long long starts_of(const unsigned long long (&m)[WORDS], int j, unsigned long long before) {
-    const unsigned long long prev = j == 0 ? (before & 1ull) : (m[j - 1] >> 63);
-    return m[j] & ~((m[j] << 1) | prev);
-}
-__device__ inline unsigned long long ends_of(const unsigned long long (&m)[WORDS], int j, unsigned long long behind) {
-    const unsigned long long next = j == WORDS - 1 ? (behind & 1ull) : (m[j + 1] & 1ull);
-    return m[j] & ~((m[j] >> 1) | (next << 63));
 }
 
 // what a tile is to the frames behind it: bits 0..9 starts for carry-in 0, 10..19 starts for carry-in 1 (at most 256 each),
@@ -192,40 +164,12 @@ __global__ __launch_bounds__(THREADS) void binarize_scan_kernel(uint32_t *__rest
     if (threadIdx.x == 0) counts[blockIdx.x] = carry.n0;
 }
 
-// exclusive scan of load(i), i in [0, len), by one workgroup: store(i, sum before i), store(len, total)  (as runs_scan_kernel)
-template <typename Load, typename Store>
-__device__ inline void block_scan(int64_t len, Load load, Store store) {
-    __shared__ long long wave_sum[WAVES];
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (int64_t base = 0; base < len; base += THREADS) {
-        const int64_t i = base + threadIdx.x;
-        const long long x = i < len ? (long long)load(i) : 0ll;
-        long long incl = x;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const long long y = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += y;
-        }
-        if (lane == WAVE - 1) wave_sum[wave] = incl;
-        __syncthreads();
-        long long before = carry, all = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            if (w < wave) before += wave_sum[w];
-            all += wave_sum[w];
-        }
-        if (i < len) store(i, before + incl - x);
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) store(len, carry);
-}
-
 // first_row[g] = rows of the raw tables before table g, first_row[CK] = rows of all of them
 __global__ __launch_bounds__(THREADS) void binarize_rows_kernel(const int32_t *__restrict__ counts, int64_t CK,
                                                                  int64_t *__restrict__ first_row) {
-    block_scan(CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
+    const long long all =
+        block_scan<long long>(0, CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
+    if (threadIdx.x == 0) first_row[CK] = all;
 }
 
 // raw table: row (first_row[c * K + k] + rank) = (first_frame, last_frame) of the hysteresis run of that rank
@@ -248,31 +192,15 @@ __global__ __launch_bounds__(THREADS) void binarize_fill_kernel(const T *__restr
         my_row = first_row[(int64_t)c * K + lane] + (long long)(w >> 1);
         my_cin = w & 1u;
     }
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int k = 0; k < K; ++k) {
         unsigned long long H[WORDS], L[WORDS], A[WORDS];
         r.masks(set.onset[k], set.offset[k], H, L);
-        long long row = __shfl(my_row, k, WAVE);
+        const long long row = __shfl(my_row, k, WAVE);
         const unsigned cin = (unsigned)__shfl((int)my_cin, k, WAVE);
         resolve(H, L, cin, A);
         // the frame behind the tile matters only when the tile's last frame is active: it then goes on iff it is in L
-        const unsigned long long behind = __ballot(r.after > set.offset[k]) & 1ull;
-#pragma unroll
-        for (int j = 0; j < WORDS; ++j) {
-            const unsigned long long s = starts_of(A, j, (unsigned long long)cin), e = ends_of(A, j, behind);
-            const int32_t frame = (int32_t)(tile0 + j * WAVE + lane);
-            const int before = __popcll(s & below);                 // starts in this word below this lane
-            const int is_start = (int)((s >> lane) & 1ull);
-            if (is_start) {
-                const long long at = row + before;
-                if (at >= 0 && at < capacity) raw[2 * at] = frame;
-            }
-            if ((e >> lane) & 1ull) {
-                const long long at = row + before + is_start - 1;    // (starts at frames <= this one) - 1
-                if (at >= 0 && at < capacity) raw[2 * at + 1] = frame;
-            }
-            row += __popcll(s);
-        }
+        const unsigned long long behind = __ballot(r.after > set.offset[k]);
+        place_runs(A, cin, behind, tile0, lane, row, capacity, raw);
     }
 }
 
@@ -330,7 +258,9 @@ __global__ __launch_bounds__(THREADS) void binarize_heads_kernel(const int32_t *
 // slice_base[j] = heads before slice j over all tables = the merged row of slice j's first head; then the merged counts
 __global__ __launch_bounds__(THREADS) void binarize_base_kernel(const int32_t *__restrict__ slice_heads, int64_t CK,
                                                                  int64_t *__restrict__ slice_base, int32_t *__restrict__ counts) {
-    block_scan(CK * SLICES, [&](int64_t i) { return slice_heads[i]; }, [&](int64_t i, long long v) { slice_base[i] = v; });
+    const long long all = block_scan<long long>(0, CK * SLICES, [&](int64_t i) { return slice_heads[i]; },
+                                                [&](int64_t i, long long v) { slice_base[i] = v; });
+    if (threadIdx.x == 0) slice_base[CK * SLICES] = all;
     __syncthreads();   // (one workgroup: its own stores are visible to it behind the barrier)
     for (int64_t g = threadIdx.x; g < CK; g += THREADS) counts[g] = (int32_t)(slice_base[(g + 1) * SLICES] - slice_base[g * SLICES]);
 }
@@ -376,18 +306,18 @@ __global__ __launch_bounds__(THREADS) void binarize_merge_kernel(const int32_t *
 struct Workspace {
     int64_t counts, first_row, slice_heads, slice_base, tile_info, bytes, n_tiles;
 };
-inline bool layout(int64_t C, int64_t T, int64_t K, Workspace &w) {
-    if (C < 1 || C > MAX_C || T < 1 || T > MAX_T || K < 1 || K > MAX_K) return false;
+inline Workspace layout(int64_t C, int64_t T, int64_t K) {   // of sizes that check_sizes has passed
+    using lad::up256;
     const int64_t ck = C * K;
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    Workspace w;
     w.n_tiles = lad::ceil_div(T, TILE);
     w.counts = 0;
-    w.first_row = up(ck * 4);
-    w.slice_heads = w.first_row + up((ck + 1) * 8);
-    w.slice_base = w.slice_heads + up(ck * SLICES * 4);
-    w.tile_info = w.slice_base + up((ck * SLICES + 1) * 8);
-    w.bytes = w.tile_info + up(ck * w.n_tiles * 4);
-    return true;
+    w.first_row = up256(ck * 4);
+    w.slice_heads = w.first_row + up256((ck + 1) * 8);
+    w.slice_base = w.slice_heads + up256(ck * SLICES * 4);
+    w.tile_info = w.slice_base + up256((ck * SLICES + 1) * 8);
+    w.bytes = w.tile_info + up256(ck * w.n_tiles * 4);
+    return w;
 }
 inline int settings_from(const char *who, const double *onsets, const double *offsets, int K, Settings &s) {
     for (int k = 0; k < MAX_K; ++k) {
@@ -404,24 +334,17 @@ inline int settings_from(const char *who, const double *onsets, const double *of
 extern "C" int32_t lad_binarize_max_settings(void) { return MAX_K; }
 
 extern "C" int64_t lad_binarize_workspace_bytes(int64_t channels, int64_t frames, int32_t n_settings) {
-    Workspace w;
-    if (!layout(channels, frames, n_settings, w)) {
-        lad::fail(LAD_ERR_INVALID, "lad_binarize_workspace_bytes: channels 1..%d, frames 1..2^30, settings 1..%d (got %lld, %lld, %d)",
-                  MAX_C, MAX_K, (long long)channels, (long long)frames, n_settings);
-        return -1;
-    }
-    return w.bytes;
+    if (check_sizes("lad_binarize_workspace_bytes", "settings", channels, frames, n_settings)) return -1;
+    return layout(channels, frames, n_settings).bytes;
 }
 
 extern "C" int lad_binarize_count(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *onsets,
                                   const double *offsets, int32_t n_settings, void *workspace, void *stream) {
     using namespace lad;
-    Workspace w;
     LAD_REQUIRE(probs && onsets && offsets && workspace, "lad_binarize_count: null buffer");
-    LAD_REQUIRE(dtype == LAD_RUNS_F32 || dtype == LAD_RUNS_F64, "lad_binarize_count: dtype %d (LAD_RUNS_F32 or LAD_RUNS_F64)", dtype);
-    LAD_REQUIRE(layout(channels, frames, n_settings, w),
-                "lad_binarize_count: channels 1..%d, frames 1..2^30, settings 1..%d (got %lld, %lld, %d)", MAX_C, MAX_K,
-                (long long)channels, (long long)frames, n_settings);
+    if (int rc = check_dtype("lad_binarize_count", dtype)) return rc;
+    if (int rc = check_sizes("lad_binarize_count", "settings", channels, frames, n_settings)) return rc;
+    const Workspace w = layout(channels, frames, n_settings);
     Settings set;
     if (int rc = settings_from("lad_binarize_count", onsets, offsets, n_settings, set)) return rc;
     char *ws = (char *)workspace;
@@ -431,12 +354,10 @@ extern "C" int lad_binarize_count(const void *probs, int32_t dtype, int64_t chan
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)ceil_div(w.n_tiles, WAVES), (unsigned)channels);
     const int K = n_settings;
-    if (dtype == LAD_RUNS_F32)
-        hipLaunchKernelGGL(binarize_tile_kernel<float>, grid, dim3(THREADS), 0, st, (const float *)probs, frames, K, set, w.n_tiles,
-                           tile_info);
-    else
-        hipLaunchKernelGGL(binarize_tile_kernel<double>, grid, dim3(THREADS), 0, st, (const double *)probs, frames, K, set, w.n_tiles,
-                           tile_info);
+    with_track_type(dtype, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(binarize_tile_kernel<T>, grid, dim3(THREADS), 0, st, (const T *)probs, frames, K, set, w.n_tiles, tile_info);
+    });
     if (int rc = check_launch("binarize_tile_kernel")) return rc;
     hipLaunchKernelGGL(binarize_scan_kernel, dim3((unsigned)(channels * K)), dim3(THREADS), 0, st, tile_info, w.n_tiles, counts);
     if (int rc = check_launch("binarize_scan_kernel")) return rc;
@@ -449,12 +370,10 @@ extern "C" int lad_binarize_fill(const void *probs, int32_t dtype, int64_t chann
                                  const double *fps_host, void *workspace, const int32_t *counts_host, int32_t *raw_table,
                                  int32_t *table, int64_t capacity_runs, void *stream) {
     using namespace lad;
-    Workspace w;
     LAD_REQUIRE(probs && onsets && offsets && min_gaps && fps && fps_host && workspace && counts_host, "lad_binarize_fill: null buffer");
-    LAD_REQUIRE(dtype == LAD_RUNS_F32 || dtype == LAD_RUNS_F64, "lad_binarize_fill: dtype %d (LAD_RUNS_F32 or LAD_RUNS_F64)", dtype);
-    LAD_REQUIRE(layout(channels, frames, n_settings, w),
-                "lad_binarize_fill: channels 1..%d, frames 1..2^30, settings 1..%d (got %lld, %lld, %d)", MAX_C, MAX_K,
-                (long long)channels, (long long)frames, n_settings);
+    if (int rc = check_dtype("lad_binarize_fill", dtype)) return rc;
+    if (int rc = check_sizes("lad_binarize_fill", "settings", channels, frames, n_settings)) return rc;
+    const Workspace w = layout(channels, frames, n_settings);
     LAD_REQUIRE(capacity_runs >= 0, "lad_binarize_fill: negative capacity");
     Settings set;
     if (int rc = settings_from("lad_binarize_fill", onsets, offsets, n_settings, set)) return rc;
@@ -464,16 +383,9 @@ extern "C" int lad_binarize_fill(const void *probs, int32_t dtype, int64_t chann
         LAD_REQUIRE(std::isfinite(gaps.v[k]) && gaps.v[k] >= 0.0, "lad_binarize_fill: min_gap[%d] = %g is not a finite number >= 0", k,
                     gaps.v[k]);
     }
-    for (int64_t c = 0; c < channels; ++c)
-        LAD_REQUIRE(fps_host[c] > 0.0 && std::isfinite(fps_host[c]), "lad_binarize_fill: fps[%lld] = %g is not a positive finite number",
-                    (long long)c, fps_host[c]);
-    int64_t total = 0;
-    for (int64_t i = 0; i < channels * n_settings; ++i) {
-        LAD_REQUIRE(counts_host[i] >= 0 && counts_host[i] <= (frames + 1) / 2,
-                    "lad_binarize_fill: counts_host[%lld] = %d is not a run count of a %lld-frame track", (long long)i, counts_host[i],
-                    (long long)frames);
-        total += counts_host[i];
-    }
+    if (int rc = check_fps("lad_binarize_fill", fps_host, channels)) return rc;
+    const int64_t total = total_runs("lad_binarize_fill", counts_host, channels * n_settings, frames);
+    if (total < 0) return LAD_ERR_INVALID;
     LAD_REQUIRE(total <= capacity_runs, "lad_binarize_fill: the tables hold %lld runs, the buffers %lld (nothing was written)",
                 (long long)total, (long long)capacity_runs);
     if (total == 0) return LAD_OK;                    // (the counts in the workspace are all zero already)
@@ -488,12 +400,11 @@ extern "C" int lad_binarize_fill(const void *probs, int32_t dtype, int64_t chann
     const dim3 grid((unsigned)ceil_div(w.n_tiles, WAVES), (unsigned)channels);
     const int K = n_settings;
     const int64_t CK = channels * K;
-    if (dtype == LAD_RUNS_F32)
-        hipLaunchKernelGGL(binarize_fill_kernel<float>, grid, dim3(THREADS), 0, st, (const float *)probs, frames, K, set, w.n_tiles,
-                           tile_info, first_row, capacity_runs, raw_table);
-    else
-        hipLaunchKernelGGL(binarize_fill_kernel<double>, grid, dim3(THREADS), 0, st, (const double *)probs, frames, K, set, w.n_tiles,
-                           tile_info, first_row, capacity_runs, raw_table);
+    with_track_type(dtype, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(binarize_fill_kernel<T>, grid, dim3(THREADS), 0, st, (const T *)probs, frames, K, set, w.n_tiles, tile_info,
+                           first_row, capacity_runs, raw_table);
+    });
     if (int rc = check_launch("binarize_fill_kernel")) return rc;
     const dim3 run_grid((unsigned)CK, SLICES);
     hipLaunchKernelGGL(binarize_heads_kernel, run_grid, dim3(THREADS), 0, st, (const int32_t *)raw_table, first_row, K, fps, gaps,

@@ -53,6 +53,7 @@ struct DeviceOnce {
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t up256(int64_t bytes) { return (bytes + 255) / 256 * 256; }   // the pitch of the parts of a workspace
 
 // Partial slabs of one weight-gradient launch (slab_reduce.hip): slab[wg][tap][ci][co], bias_slab[wg][co] (or nullptr)
 struct SlabReduce {

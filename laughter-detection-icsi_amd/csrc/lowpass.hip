@@ -206,7 +206,7 @@ struct Workspace {
 };
 inline bool layout(int64_t C, int64_t T, Workspace &w) {
     if (C < 1 || C > MAX_C || T < MIN_T || T > MAX_T) return false;
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const auto up = lad::up256;
     w.n_tiles = lad::ceil_div(T + 2 * PAD, TILE);
     w.fwd = 0;
     w.states = up(C * (T + 2 * PAD) * 8);

@@ -13,7 +13,7 @@
 // Index: per (channel, class) sorted, disjoint, non-empty intervals (lo, hi] (CSR: bounds[n][2], offsets[channels * 5 + 1];
 // classes INVALID, LAUGH, SPEECH, NOISE, SILENCE), the last four with INVALID already subtracted by whoever built the index.
 // Coverage F(x) = milliseconds of a class in (0, x] = cum[i] + min(x, hi_i) - lo_i for the last interval i with lo_i < x, where
-// cum is the exclusive running length (score_scan_kernel: one scan per (channel, class), as runs_scan_kernel), so that
+// cum is the exclusive running length (score_scan_kernel: one scan per (channel, class): block_scan), so that
 // |(a, b] n class| = F(b) - F(a): no set arithmetic here.
 //
 // Shape: two launches after one memset of the output.
@@ -25,20 +25,14 @@
 //                      (min_length, field) -- integer sums: whatever order the waves arrive in, the bytes are the same.
 // Every index read is clamped to the index, every row read to the caller's row count.  No LDS in the row kernel, no scratch.
 #pragma clang fp contract(off)
-#include <cmath>
-
-#include "lad_common.h"
+// The limits of the sweep whose workspace this reads, and the scan, are lad_sweep_tile.h's.
+#include "lad_sweep_tile.h"
 
 namespace {
-constexpr int WAVE = 64;
-constexpr int WAVES = 4;
-constexpr int THREADS = WAVE * WAVES;
+using namespace lad::sweep;
 constexpr int CLASSES = 5;                         // INVALID, LAUGH, SPEECH, NOISE, SILENCE
 constexpr int FIELDS = 7;                          // n_pred, n_valid, pred_ms, corr_ms, fp_speech_ms, fp_noise_ms, fp_silence_ms
 constexpr int MAX_L = 8;                           // min_lengths per call: lane l * 7 + f of a wave carries one sum
-constexpr int MAX_K = 64;                          // as runs.hip
-constexpr int MAX_C = 65535;
-constexpr int64_t MAX_T = (int64_t)1 << 30;
 constexpr int64_t MAX_INTERVALS = (int64_t)1 << 30;
 constexpr int64_t MAX_ROWS = (int64_t)1 << 38;     // grid.x of the row kernel
 constexpr double MS = 1000.0;                      // utils.to_frames: 1000 / frame_duration, frame_duration = 1 ms
@@ -47,35 +41,6 @@ struct MinLengths {
     double v[MAX_L];
 };
 
-// exclusive scan of load(i), i in [lo, hi), by one workgroup: store(i, sum of load(j) for lo <= j < i)  (as runs_scan_kernel)
-template <typename Load, typename Store>
-__device__ inline void block_scan(int64_t lo, int64_t hi, Load load, Store store) {
-    __shared__ long long wave_total[WAVES];
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (int64_t base = lo; base < hi; base += THREADS) {
-        const int64_t i = base + threadIdx.x;
-        const long long x = i < hi ? (long long)load(i) : 0ll;
-        long long incl = x;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const long long y = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += y;
-        }
-        if (lane == WAVE - 1) wave_total[wave] = incl;
-        __syncthreads();
-        long long before = carry, all = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            if (w < wave) before += wave_total[w];
-            all += wave_total[w];
-        }
-        if (i < hi) store(i, before + incl - x);
-        carry += all;
-        __syncthreads();
-    }
-}
-
 // workgroup s < segments: cum[i] = total length of the intervals before i in the same (channel, class) s;
 // workgroup `segments`: first_row[i] = rows of the run tables before table i (the counts lad_runs_count left in its workspace)
 __global__ __launch_bounds__(THREADS) void score_scan_kernel(const int32_t *__restrict__ bounds, const int32_t *__restrict__ offsets,
@@ -83,13 +48,14 @@ __global__ __launch_bounds__(THREADS) void score_scan_kernel(const int32_t *__re
                                                              const int32_t *__restrict__ counts, int64_t CK,
                                                              int64_t *__restrict__ first_row) {
     if ((int64_t)blockIdx.x == segments) {
-        block_scan(0, CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
+        block_scan<long long>(0, CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
         return;
     }
     int64_t o0 = offsets[blockIdx.x], o1 = offsets[blockIdx.x + 1];
     o0 = o0 < 0 ? 0 : (o0 > n_intervals ? n_intervals : o0);
     o1 = o1 < o0 ? o0 : (o1 > n_intervals ? n_intervals : o1);
-    block_scan(o0, o1, [&](int64_t i) { return bounds[2 * i + 1] - bounds[2 * i]; }, [&](int64_t i, long long v) { cum[i] = (int32_t)v; });
+    block_scan<long long>(o0, o1, [&](int64_t i) { return bounds[2 * i + 1] - bounds[2 * i]; },
+                          [&](int64_t i, long long v) { cum[i] = (int32_t)v; });
 }
 
 __device__ inline long long wave_sum64(long long s) {
@@ -199,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__re
     }
 }
 
-inline int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
+using lad::up256;
 
 inline bool sizes_ok(int64_t C, int64_t n_intervals, int64_t K, int64_t L) {
     return C >= 1 && C <= MAX_C && n_intervals >= 0 && n_intervals <= MAX_INTERVALS && K >= 1 && K <= MAX_K && L >= 1 && L <= MAX_L;
@@ -239,9 +205,9 @@ extern "C" int lad_score_runs(const void *runs_workspace, const int32_t *table, 
         LAD_REQUIRE(ml.v[l] == ml.v[l], "lad_score_runs: min_lengths[%d] is NaN", l);
     }
     // millisecond values are int32: to_frames(frames / fps) < 2^31 for every channel
+    if (int rc = check_fps("lad_score_runs", fps_host, channels)) return rc;
     for (int64_t c = 0; c < channels; ++c) {
         const double f = fps_host[c];
-        LAD_REQUIRE(f > 0.0 && std::isfinite(f), "lad_score_runs: fps[%lld] = %g is not a positive finite number", (long long)c, f);
         const double ms = std::nearbyint((double)frames / f * MS);
         LAD_REQUIRE(ms < 2147483648.0,
                     "lad_score_runs: millisecond overflow: %lld frames at fps[%lld] = %g end at %.0f ms, int32 holds 2^31 - 1",
@@ -264,13 +230,8 @@ extern "C" int lad_score_runs(const void *runs_workspace, const int32_t *table, 
                         (long long)i, lo, hi, (long long)(s / CLASSES), (long long)(s % CLASSES));
         }
     }
-    int64_t rows = 0;
-    for (int64_t i = 0; i < CK; ++i) {
-        LAD_REQUIRE(counts_host[i] >= 0 && counts_host[i] <= (frames + 1) / 2,
-                    "lad_score_runs: counts_host[%lld] = %d is not a run count of a %lld-frame track", (long long)i, counts_host[i],
-                    (long long)frames);
-        rows += counts_host[i];
-    }
+    const int64_t rows = total_runs("lad_score_runs", counts_host, CK, frames);
+    if (rows < 0) return LAD_ERR_INVALID;
     LAD_REQUIRE(rows <= MAX_ROWS, "lad_score_runs: %lld run-table rows, at most 2^38 per call", (long long)rows);
     LAD_REQUIRE(rows == 0 || table, "lad_score_runs: null table");
 

@@ -123,33 +123,69 @@ def get_laughter_frame_spans(probs, threshold):
     return run_spans(fix_probs(probs) > threshold)
 
 
-def _device_run_tables(probs, thresholds):
-    """probs: (C, T) float32 / float64 GPU tensor, T >= 1.  Returns (counts (C, K) int64, table (total, 2) int32 numpy): the
-    (c, k) tables back to back in c * K + k order (include/lad_hip.h: lad_runs_count, lad_runs_fill)."""
+def _device_track(probs, what="sweep"):
+    """What every device form asks of its probability tensor: (T,) or (C, T), in GPU memory, contiguous, float32 or float64.
+    Returns (the (C, T) tensor, its lad_runs_dtype, whether it was a (T,) one)."""
     import torch
 
     import _hip
-    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    single = getattr(probs, "ndim", None) == 1
+    if single and hasattr(probs, "unsqueeze"):
+        probs = probs.unsqueeze(0)
+    if getattr(probs, "ndim", None) != 2:
+        raise _hip.LadHipError(f"probs must be a (T,) or (C, T) GPU tensor (the device {what} has no CPU fallback)")
     _hip.require_cuda(probs, "probs")
+    if probs.dtype not in (torch.float32, torch.float64):
+        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    return probs, 0 if probs.dtype == torch.float32 else 1, single
+
+
+def _device_tables(probs, dtype, settings, fps_host=None, binarize=False, extra_bytes=0):
+    """Count + fill of one family (include/lad_hip.h) on a (C, T) tensor that _device_track has passed, T >= 1: lad_runs_* for K
+    thresholds, or with binarize lad_binarize_* for K (onset, offset, min_gap), at most lad_binarize_max_settings() of them, with
+    fps_host a float64 numpy (C,).  Everything stays on the device: returns (workspace, table, counts, fps_dev) with `workspace` a
+    uint8 tensor whose first lad_*_workspace_bytes bytes are the family's workspace (the tables' counts at its start, where
+    lad_score_runs reads them) followed by extra_bytes for the caller, `table` the (total, 2) int32 tables back to back in
+    c * K + k order, counts their row counts, int32 numpy (C * K,), and fps_dev fps_host on the device (None without one)."""
+    import torch
+
+    import _hip
     lib = _hip.lib()
+    name = "lad_binarize" if binarize else "lad_runs"
     C, T = probs.shape
-    K = len(thresholds)
-    thr = (ctypes.c_double * max(K, 1))(*[float(t) for t in thresholds])
-    dtype = 0 if probs.dtype == torch.float32 else 1     # lad_runs_dtype
-    ws_bytes = lib.lad_runs_workspace_bytes(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_runs_workspace_bytes")
+    K = len(settings)
+    cols = [(ctypes.c_double * K)(*[float(v) for v in col]) for col in (zip(*settings) if binarize else [settings])]
+    ws_bytes = getattr(lib, name + "_workspace_bytes")(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, name + "_workspace_bytes")
     with torch.cuda.device(probs.device):
         stream = _hip.stream_handle(probs.device)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
-        _hip.check(lib.lad_runs_count(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), stream), "lad_runs_count")
-        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
+        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
+        fps_dev = None if fps_host is None else torch.from_numpy(fps_host).to(probs.device)
+        track = (_hip.ptr(probs), dtype, C, T)
+
+        def counts_now():
+            return np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
+        _hip.check(getattr(lib, name + "_count")(*track, *cols[:2], K, _hip.ptr(ws), stream), name + "_count")
+        counts = counts_now()
         total = int(counts.sum(dtype=np.int64))
-        table = torch.empty((total, 2), dtype=torch.int32, device=probs.device)
-        _hip.check(lib.lad_runs_fill(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws),
-                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _hip.ptr(table), total, stream),
-                   "lad_runs_fill")
-        return counts.astype(np.int64).reshape(C, K), table.cpu().numpy()
+        cptr = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        tables = torch.empty((2 if binarize else 1, max(total, 1), 2), dtype=torch.int32, device=probs.device)
+        if binarize:            # the hysteresis runs go to tables[0], the merged ones to tables[1] and their counts over the raw ones
+            _hip.check(lib.lad_binarize_fill(*track, *cols, K, _hip.ptr(fps_dev), fps_host.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                             _hip.ptr(ws), cptr, _hip.ptr(tables[0]), _hip.ptr(tables[1]), total, stream),
+                       "lad_binarize_fill")
+            counts = counts_now()
+        else:
+            _hip.check(lib.lad_runs_fill(*track, *cols, K, _hip.ptr(ws), cptr, _hip.ptr(tables[0]), total, stream), "lad_runs_fill")
+        return ws, tables[-1][:int(counts.sum(dtype=np.int64))], counts, fps_dev
+
+
+def _device_run_tables(probs, thresholds):
+    """probs: (C, T) float32 / float64 GPU tensor, T >= 1.  Returns (counts (C, K) int64, table (total, 2) int32 numpy): the
+    (c, k) tables back to back in c * K + k order."""
+    probs, dtype, _ = _device_track(probs)
+    _, table, counts, _ = _device_tables(probs, dtype, list(thresholds))
+    return counts.astype(np.int64).reshape(len(probs), -1), table.cpu().numpy()
 
 
 def _split_tables(counts, table):
@@ -159,41 +195,55 @@ def _split_tables(counts, table):
     return [[table[edges[c * K + k]:edges[c * K + k + 1]].astype(np.int64) for k in range(K)] for c in range(C)]
 
 
+def _device_frame_spans(probs, settings, fps=None, binarize=False):
+    """[int64 (n, 2) array per setting] for a (T,) tensor, one such list per channel for a (C, T) one: the tables of
+    _device_tables on the host.  The plain sweep is one call whatever the number of thresholds (the library refuses more than
+    lad_runs_max_thresholds()); settings go in rounds of at most lad_binarize_max_settings()."""
+    import _hip
+    probs, dtype, single = _device_track(probs)
+    C, T = probs.shape
+    fps_host = _fps_per_channel(fps, C) if binarize else None
+    if T == 0 or C == 0 or not settings:
+        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
+    else:
+        out = [[] for _ in range(C)]
+        step = int(_hip.lib().lad_binarize_max_settings()) if binarize else len(settings)
+        for k0 in range(0, len(settings), step):
+            _, table, counts, _ = _device_tables(probs, dtype, settings[k0:k0 + step], fps_host, binarize)
+            part = _split_tables(counts.astype(np.int64).reshape(C, -1), table.cpu().numpy())
+            for c in range(C):
+                out[c] += part[c]
+    return out[0] if single else out
+
+
 def get_laughter_frame_spans_device(probs, thresholds):
     """Device form of get_laughter_frame_spans for a list of thresholds.  probs: (T,) GPU tensor (float32 / float64, contiguous) ->
     [int64 (n, 2) array of (first_frame, last_frame) per threshold], each equal to get_laughter_frame_spans(probs.cpu(), thr);
     (C, T) -> one such list per channel, from the same four launches."""
-    import _hip
-    thresholds = list(thresholds)
-    single = getattr(probs, "ndim", None) == 1
-    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
-    if getattr(p2, "ndim", None) != 2:
-        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device sweep has no CPU fallback)")
-    C, T = p2.shape
-    if T == 0 or C == 0 or not thresholds:
-        _hip.require_cuda(p2, "probs")
-        out = [[np.zeros((0, 2), np.int64) for _ in thresholds] for _ in range(C)]
-    else:
-        out = _split_tables(*_device_run_tables(p2, thresholds))
-    return out[0] if single else out
+    return _device_frame_spans(probs, list(thresholds))
 
 
-def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
-    """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats).
-    The run tables come from the device; first / fps, last / fps and end - start > min_length are evaluated on them in float64
-    (the arithmetic of the reference's Python floats)."""
-    import _hip
-    if getattr(probs, "ndim", None) != 1:
-        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
-    thresholds = list(thresholds)
+def _instances_from_spans(keys, spans_list, min_lengths, fps):
+    """{(*key, min_length): [(start_s, end_s), ...]}, keys-major: first / fps, last / fps and end - start > min_length in float64
+    (the arithmetic of the reference's Python floats) on the integer spans of each key."""
     instance_dict = {}
-    for thr, spans in zip(thresholds, get_laughter_frame_spans_device(probs, thresholds)):
+    for key, spans in zip(keys, spans_list):
         starts, ends = spans[:, 0] / fps, spans[:, 1] / fps
         length = ends - starts
         for min_l in min_lengths:
             keep = length > min_l
-            instance_dict[(thr, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
-    return {(thr, min_l): instance_dict[(thr, min_l)] for thr in thresholds for min_l in min_lengths}
+            instance_dict[(*key, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
+    return instance_dict
+
+
+def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+    """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats).
+    The run tables come from the device; the seconds and the min_length filter are evaluated on them on the host."""
+    import _hip
+    if getattr(probs, "ndim", None) != 1:
+        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
+    thresholds = list(thresholds)
+    return _instances_from_spans([(thr,) for thr in thresholds], get_laughter_frame_spans_device(probs, thresholds), min_lengths, fps)
 
 
 # ---- hysteresis and gap filling (include/lad_hip.h: lad_binarize_count has the convention) ----------------------------------------
@@ -254,17 +304,6 @@ def _binarize_keys(thresholds, offset_drops, min_gaps):
     return triples, settings
 
 
-def _instances_from_spans(triples, spans_list, min_lengths, fps):
-    instance_dict = {}
-    for (thr, drop, gap), spans in zip(triples, spans_list):
-        starts, ends = spans[:, 0] / fps, spans[:, 1] / fps
-        length = ends - starts
-        for min_l in min_lengths:
-            keep = length > min_l
-            instance_dict[(thr, drop, gap, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
-    return instance_dict
-
-
 def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
     """{(threshold, offset_drop, min_gap, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then drop, then gap, then
     min_length.  The onset is the threshold and the offset is threshold - offset_drop (drop >= 0); events are (first / fps,
@@ -283,47 +322,13 @@ def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., off
     return _instances_from_spans(triples, spans_list, min_lengths, fps)
 
 
-def _device_binarize(probs, settings, fps_host, extra_bytes=0):
-    """lad_binarize_count + lad_binarize_fill for at most lad_binarize_max_settings() settings.  probs: (C, T) float32 / float64 GPU
-    tensor, T >= 1; settings: [(onset, offset, min_gap)]; fps_host: float64 numpy (C,).  Everything stays on the device: returns
-    (workspace, table, counts, fps_dev) with `workspace` a uint8 tensor whose first lad_binarize_workspace_bytes bytes are the
-    binarize workspace (the merged counts at its start) followed by extra_bytes for the caller, `table` the merged (total, 2) int32
-    tables back to back, and counts the merged counts, int32 numpy (C * K,)."""
-    import torch
-
-    import _hip
-    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
-    _hip.require_cuda(probs, "probs")
-    lib = _hip.lib()
-    C, T = probs.shape
-    K = len(settings)
-    f64p, i32p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-    cols = [(ctypes.c_double * max(K, 1))(*[float(s[j]) for s in settings]) for j in range(3)]
-    dtype = 0 if probs.dtype == torch.float32 else 1     # lad_runs_dtype
-    ws_bytes = lib.lad_binarize_workspace_bytes(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_binarize_workspace_bytes")
-    with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
-        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
-        fps_dev = torch.from_numpy(fps_host).to(probs.device)
-        _hip.check(lib.lad_binarize_count(_hip.ptr(probs), dtype, C, T, cols[0], cols[1], K, _hip.ptr(ws), stream),
-                   "lad_binarize_count")
-        raw_counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
-        total = int(raw_counts.sum(dtype=np.int64))
-        both = torch.empty((2, max(total, 1), 2), dtype=torch.int32, device=probs.device)
-        _hip.check(lib.lad_binarize_fill(_hip.ptr(probs), dtype, C, T, cols[0], cols[1], cols[2], K, _hip.ptr(fps_dev),
-                                         fps_host.ctypes.data_as(f64p), _hip.ptr(ws), raw_counts.ctypes.data_as(i32p),
-                                         _hip.ptr(both[0]), _hip.ptr(both[1]), total, stream), "lad_binarize_fill")
-        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())         # the merged counts
-        return ws, both[1][:int(counts.sum(dtype=np.int64))], counts, fps_dev
-
-
-def _fps_per_channel(fps, C):
+def _fps_per_channel(fps, C, each=_check_fps):
+    """One fps or C of them -> float64 numpy (C,).  each=float leaves a value that is not positive and finite to whoever divides by
+    it (the library refuses it: LadHipError)."""
     f = [fps] * C if np.ndim(fps) == 0 else list(fps)
     if len(f) != C:
         raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
-    return np.asarray([_check_fps(x) for x in f], dtype=np.float64)
+    return np.asarray([each(x) for x in f], dtype=np.float64)
 
 
 def binarize_frame_spans_device(probs, settings, fps=100.):
@@ -331,26 +336,7 @@ def binarize_frame_spans_device(probs, settings, fps=100.):
     float64, contiguous) -> [int64 (n, 2) array per setting], each equal to binarize_frame_spans(probs.cpu(), *setting, fps);
     (C, T) -> one such list per channel, fps a float or one per channel.  More settings than lad_binarize_max_settings() are
     split into several calls.  No CPU fallback."""
-    import _hip
-    settings = [_check_setting(*s) for s in settings]
-    single = getattr(probs, "ndim", None) == 1
-    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
-    if getattr(p2, "ndim", None) != 2:
-        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device sweep has no CPU fallback)")
-    C, T = p2.shape
-    fps_host = _fps_per_channel(fps, C)
-    out = [[] for _ in range(C)]
-    if T == 0 or C == 0 or not settings:
-        _hip.require_cuda(p2, "probs")
-        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
-    else:
-        step = int(_hip.lib().lad_binarize_max_settings())
-        for k0 in range(0, len(settings), step):
-            _, table, counts, _ = _device_binarize(p2, settings[k0:k0 + step], fps_host)
-            part = _split_tables(counts.astype(np.int64).reshape(C, -1), table.cpu().numpy())
-            for c in range(C):
-                out[c] += part[c]
-    return out[0] if single else out
+    return _device_frame_spans(probs, [_check_setting(*s) for s in settings], fps, binarize=True)
 
 
 def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):

@@ -261,18 +261,23 @@ def score_instances(instances, index, meeting_id, chan):
     return out
 
 
-def _fps_list(fps, C):
-    f = [float(fps)] * C if np.ndim(fps) == 0 else [float(x) for x in fps]
-    if len(f) != C:
-        raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
-    return f
-
-
 def _binarize_axes(offset_drops, min_gaps):
     """None, or the two extra axes as lists (one given: the other is [0.0], which changes nothing)."""
     if offset_drops is None and min_gaps is None:
         return None
     return (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
+
+
+def _cells(thresholds, min_lengths, axes):
+    """[(index into a score array behind the channel, threshold, min_length, () or (offset_drop, min_gap))], thresholds-major, then
+    drop, then gap, then min_length."""
+    extras = [((), ())] if axes is None else [((d, g), (drop, gap)) for d, drop in enumerate(axes[0]) for g, gap in enumerate(axes[1])]
+    return [((k, *at, l), thr, min_l, extra) for k, thr in enumerate(thresholds) for at, extra in extras
+            for l, min_l in enumerate(min_lengths)]
+
+
+def _score_shape(C, thresholds, min_lengths, axes):
+    return (C, len(thresholds), *([] if axes is None else [len(a) for a in axes]), len(min_lengths), len(FIELDS))
 
 
 def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None):
@@ -282,25 +287,18 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offs
     and gap filling -> int64 (C, K, D, G, L, 7)."""
     import laugh_segmenter as ls
     thresholds, min_lengths = list(thresholds), list(min_lengths)
-    f = _fps_list(fps, len(channels))
+    f = ls._fps_per_channel(fps, len(channels), each=float).tolist()
     axes = _binarize_axes(offset_drops, min_gaps)
-    if axes is not None:
-        drops, gaps = axes
-        out = np.zeros((len(channels), len(thresholds), len(drops), len(gaps), len(min_lengths), len(FIELDS)), np.int64)
-        for c, (track, mc) in enumerate(zip(tracks, channels)):
-            got = score_instances(ls.binarize_instances(track, thresholds, min_lengths, f[c], drops, gaps), index, *mc)
-            for k, thr in enumerate(thresholds):
-                for d, drop in enumerate(drops):
-                    for g, gap in enumerate(gaps):
-                        for l, min_l in enumerate(min_lengths):
-                            out[c, k, d, g, l] = got[(thr, drop, gap, min_l)]
-        return out
-    out = np.zeros((len(channels), len(thresholds), len(min_lengths), len(FIELDS)), np.int64)
+    cells = _cells(thresholds, min_lengths, axes)
+    out = np.zeros(_score_shape(len(channels), thresholds, min_lengths, axes), np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
-        got = score_instances(ls.get_laughter_instances(track, thresholds, min_lengths, f[c]), index, *mc)
-        for k, thr in enumerate(thresholds):
-            for l, min_l in enumerate(min_lengths):
-                out[c, k, l] = got[(thr, min_l)]
+        if axes is None:
+            instances = ls.get_laughter_instances(track, thresholds, min_lengths, f[c])
+        else:
+            instances = ls.binarize_instances(track, thresholds, min_lengths, f[c], *axes)
+        got = score_instances(instances, index, *mc)
+        for at, thr, min_l, extra in cells:
+            out[(c, *at)] = got[(thr, *extra, min_l)]
     return out
 
 
@@ -318,94 +316,47 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     import torch
 
     import _hip
-    if getattr(probs, "ndim", None) == 1 and hasattr(probs, "unsqueeze"):
-        probs = probs.unsqueeze(0)
-    if getattr(probs, "ndim", None) != 2:
-        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device scorer has no CPU fallback)")
-    if isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
-    _hip.require_cuda(probs, "probs")
+    import laugh_segmenter as ls
+    probs, dtype, _ = ls._device_track(probs, "scorer")
     channels, thresholds, min_lengths = list(channels), list(thresholds), list(min_lengths)
     C, T = probs.shape
-    K, L = len(thresholds), len(min_lengths)
+    L = len(min_lengths)
     if C != len(channels):
         raise ValueError(f"{C} tracks for {len(channels)} channels")
-    f = _fps_list(fps, C)
+    fps_host = ls._fps_per_channel(fps, C, each=float)
     axes = _binarize_axes(offset_drops, min_gaps)
-    out_shape = (C, K, L, len(FIELDS)) if axes is None else (C, K, len(axes[0]), len(axes[1]), L, len(FIELDS))
+    out_shape = _score_shape(C, thresholds, min_lengths, axes)
     if T == 0 or 0 in out_shape:
         return np.zeros(out_shape, np.int64)
     if lowpass is not None:
-        import laugh_segmenter as ls
-        probs = ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths)
+        probs, dtype, _ = ls._device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
     elif lengths is not None:
         raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
     dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
     if dix.channels != channels or dix.device != probs.device:
         raise ValueError("the DeviceIndex was built for other channels or another device")
-    thr = (ctypes.c_double * K)(*[float(t) for t in thresholds])
     mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
-    fps_host = np.asarray(f, dtype=np.float64)
-    dtype = 0 if probs.dtype == torch.float32 else 1                               # lad_runs_dtype
     i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    if axes is not None:
-        return _score_binarized(probs, dix, thresholds, axes, mls, L, fps_host, out_shape)
-    ws_bytes = lib.lad_runs_workspace_bytes(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_runs_workspace_bytes")
-    sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, K, L)
-    _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
-    with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
-        ws = torch.empty(ws_bytes + sws_bytes, dtype=torch.uint8, device=probs.device)
-        sws = ws[ws_bytes:]
-        fps_dev = torch.from_numpy(fps_host).to(probs.device)
-        scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
-        _hip.check(lib.lad_runs_count(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), stream), "lad_runs_count")
-        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())            # (synchronises)
-        total = int(counts.sum(dtype=np.int64))
-        table = torch.empty((max(total, 1), 2), dtype=torch.int32, device=probs.device)
-        cptr = counts.ctypes.data_as(i32p)
-        _hip.check(lib.lad_runs_fill(_hip.ptr(probs), dtype, C, T, thr, K, _hip.ptr(ws), cptr, _hip.ptr(table), total, stream),
-                   "lad_runs_fill")
-        _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), cptr, C, T, K, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
-                                      dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
-                                      _hip.ptr(fps_dev), fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(sws), _hip.ptr(scores),
-                                      stream), "lad_score_runs")
-        return scores.cpu().numpy()
-
-
-def _score_binarized(probs, dix, thresholds, axes, mls, L, fps_host, out_shape):
-    """The (C, K, D, G, L, 7) scores of score_sweep_device: rounds of at most lad_binarize_max_settings() settings, each
-    lad_binarize_count + lad_binarize_fill + lad_score_runs with the round's settings in the place of the thresholds."""
-    import torch
-
-    import _hip
-    import laugh_segmenter as ls
-    lib = _hip.lib()
-    C, T = probs.shape
-    _, settings = ls._binarize_keys(thresholds, axes[0], axes[1])
-    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    step = int(lib.lad_binarize_max_settings())
+    if axes is None:            # one round whatever K is: the library refuses more thresholds than lad_runs_max_thresholds()
+        settings, step = thresholds, len(thresholds)
+    else:
+        settings, step = ls._binarize_keys(thresholds, *axes)[1], int(lib.lad_binarize_max_settings())
     parts = []
-    with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
-        for k0 in range(0, len(settings), step):
-            chunk = settings[k0:k0 + step]
-            n = len(chunk)
-            sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
-            _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
-            ws, table, counts, fps_dev = ls._device_binarize(probs, chunk, fps_host, extra_bytes=sws_bytes)
-            sws = ws[ws.numel() - sws_bytes:]
+    for k0 in range(0, len(settings), step):
+        chunk = settings[k0:k0 + step]
+        n = len(chunk)
+        sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
+        _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
+        ws, table, counts, fps_dev = ls._device_tables(probs, dtype, chunk, fps_host, axes is not None, extra_bytes=sws_bytes)
+        with torch.cuda.device(probs.device):
             scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
-            if len(table) == 0:
-                table = torch.zeros((1, 2), dtype=torch.int32, device=probs.device)
             _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
                                           _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
                                           dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
-                                          fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(sws), _hip.ptr(scores), stream),
-                       "lad_score_runs")
-            parts.append(scores.cpu().numpy())
+                                          fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(ws[ws.numel() - sws_bytes:]), _hip.ptr(scores),
+                                          _hip.stream_handle(probs.device)), "lad_score_runs")
+        parts.append(scores.cpu().numpy())
     return np.concatenate(parts, axis=1).reshape(out_shape)
 
 
@@ -417,11 +368,7 @@ def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=Non
     (offset_drop and min_gap behind min_len), thresholds-major, then drop, then gap, then min_len."""
     scores = np.asarray(scores)
     axes = _binarize_axes(offset_drops, min_gaps)
-    if axes is None:
-        settings = [((k, l), (thr, min_l)) for k, thr in enumerate(thresholds) for l, min_l in enumerate(min_lengths)]
-    else:
-        settings = [((k, d, g, l), (thr, min_l, drop, gap)) for k, thr in enumerate(thresholds) for d, drop in enumerate(axes[0])
-                    for g, gap in enumerate(axes[1]) for l, min_l in enumerate(min_lengths)]
+    settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
         part = index.participant(m, chan)

@@ -285,6 +285,29 @@ def test_scores_against_the_host_scorer(lowpass):
     assert (dev[:, :, 0, 2, 0, 0] <= plain[:, :, 0, 0]).all() and (dev[:, :, 0, 2, 0, 0] < plain[:, :, 0, 0]).any()   # gaps join
 
 
+def test_scored_sweep_of_two_rounds():
+    """80 settings: a round of lad_binarize_max_settings() = 64 and one of 16, three tiles and a ragged end, two channels."""
+    import sweep_eval as se
+    T, C = 3 * 512 + 7, 2
+    fps = [100.0, 97.25]
+    index = _corpus(31, ["fe001", "me002"], T / 97.25, 12, 1.0)                         # channel length 0.97 * T / 97.25
+    channels = [(M, f"chan{i}") for i in range(C)]
+    thresholds, drops, gaps, min_lengths = [0.2, 0.35, 0.5, 0.65, 0.8], [0.0, 0.05, 0.1, 0.2], [0.0, 0.05, 0.2, 1.0], [0.0, 0.1]
+    tracks = np.stack([recipe.make_prob_track(60 + c, T) for c in range(C)]).astype(np.float32)
+    host = se.score_sweep_host(list(tracks), channels, thresholds, min_lengths, fps, index, offset_drops=drops, min_gaps=gaps)
+    # nothing here passes on empty tables, and the two rounds score different settings
+    assert host.shape == (2, 5, 4, 4, 2, 7) and (host[..., 0, 0] > 0).all() and (host.sum(axis=(0, 1, 2, 3, 4)) > 0).all()
+    flat = host.reshape(C, 80, 2, 7)
+    assert not np.array_equal(flat[:, :16], flat[:, 64:])
+    d = torch.from_numpy(tracks).cuda()
+    dev = se.score_sweep_device(d, channels, thresholds, min_lengths, fps, index, offset_drops=drops, min_gaps=gaps)
+    assert dev.dtype == np.int64 and dev.shape == (2, 5, 4, 4, 2, 7)
+    assert np.array_equal(dev, host)
+    assert np.array_equal(dev[:, :, 0, 0], se.score_sweep_device(d, channels, thresholds, min_lengths, fps, index))
+    again = se.score_sweep_device(d, channels, thresholds, min_lengths, fps, index, offset_drops=drops, min_gaps=gaps)
+    assert again.tobytes() == dev.tobytes()
+
+
 def test_instances_device_against_host():
     import laugh_segmenter as ls
     thresholds, min_lengths, drops, gaps = [0.2, 0.5, 0.9], [0.0, 0.1, 0.2], [0.0, 0.1, 0.4], [0.0, 0.05, 0.5]
