@@ -691,6 +691,56 @@ int lad_score_runs(const void *runs_workspace, const int32_t *table, const int32
                    int64_t *scores, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Event-level scores of the sweep (csrc/events.hip): which transcribed laughs were found, which predicted laughs were real, into
+ * how many pieces a laugh was split and how far its boundaries lie off.  lad_score_runs measures predicted milliseconds and
+ * analyse.py:255-257 counts events on both sides (num_of_pred_laughs, valid_pred_laughs, num_of_transc_laughs) without ever
+ * matching them; nothing in the reference does this.  The text below IS the specification (tests/_events_model.py is a second
+ * implementation of it, per-millisecond sets and per-pair loops).
+ *
+ * Inputs.  Those of lad_score_runs: the run tables of lad_runs_* or lad_binarize_* with their counts at the start of that
+ * workspace, the CSR index, fps and min_lengths; and two integers, min_overlap_ms >= 0 and min_overlap_pct in 0..100.
+ * Predictions.  A run (first, last) of channel c is the millisecond interval (a, b] exactly as for lad_score_runs:
+ * a = rint(first / fps[c] * 1000), b = rint(last / fps[c] * 1000) in float64 with IEEE division and contraction off; the run is
+ * kept for min_length l iff last / fps[c] - first / fps[c] > l.  Within one table a and b do not decrease and a_next >= b_prev,
+ * so the intervals are disjoint.  a == b is possible; such a run overlaps nothing.
+ * Reference events.  The events of channel c are the intervals (lo, hi] of its LAUGH segment of the index: transcribed laughter
+ * with INVALID subtracted, adjacent and overlapping rows merged.  An event is such a maximal interval, not a transcript row.
+ * Pairs.  The overlap of an event and a prediction is ov(e, p) = max(0, min(b, hi) - max(a, lo)); e and p are linked iff ov >= 1.
+ * Per event, over the kept predictions of one (c, k, l): cov_e = the sum of ov; frag_e = the number of links; first_e and last_e
+ * = the first and last linked prediction in table order; touched iff frag_e >= 1; hit iff cov_e >= max(1, min_overlap_ms) and
+ * 100 * cov_e >= min_overlap_pct * (hi - lo).
+ * Per kept prediction: lov_p = |(a, b] n LAUGH| (F(b) - F(a) with lad_score_runs' coverage function), pred_p = |(a, b] \ INVALID|;
+ * hit iff lov_p >= max(1, min_overlap_ms) and 100 * lov_p >= min_overlap_pct * pred_p.  All products are int64.
+ * Output.  events[c][k][l] = seven int64 values (enum lad_event_field):
+ *   N_REF          events of the channel (the same for every k, l)
+ *   REF_TOUCHED    events with at least one link
+ *   REF_HIT        events that are hit
+ *   PRED_HIT       kept predictions that are hit
+ *   LINKS          sum of frag_e over all events
+ *   ONSET_ABS_MS   sum over hit events of abs(a(first_e) - lo)
+ *   OFFSET_ABS_MS  sum over hit events of abs(b(last_e) - hi)
+ * so that REF_HIT <= REF_TOUCHED <= N_REF, LINKS >= REF_TOUCHED, PRED_HIT <= lad_score_runs' n_valid, REF_HIT == REF_TOUCHED for
+ * (min_overlap_ms, min_overlap_pct) = (1, 0), and a channel without a participant (five empty sets) has seven zeros.
+ * Integer sums accumulated with vector global atomics on int64: identical bytes on every call.
+ * ---------------------------------------------------------------------------------------------- */
+enum lad_event_field { LAD_EVENT_N_REF = 0, LAD_EVENT_REF_TOUCHED = 1, LAD_EVENT_REF_HIT = 2, LAD_EVENT_PRED_HIT = 3,
+                       LAD_EVENT_LINKS = 4, LAD_EVENT_ONSET_ABS_MS = 5, LAD_EVENT_OFFSET_ABS_MS = 6, LAD_EVENT_FIELDS = 7 };
+/* bytes of workspace for lad_score_events with run tables of total_runs rows in all (the sum of the counts); needs no GPU.  -1 and
+ * lad_last_error() for what lad_score_workspace_bytes refuses or total_runs outside 0..2^38. */
+int64_t lad_score_events_workspace_bytes(int64_t channels, int64_t n_intervals, int32_t n_thresholds, int32_t n_min_lengths,
+                                         int64_t total_runs);
+/* the seven values for every (channel, threshold, min_length) at once: a memset and at most three launches on `stream`, whatever
+ * n_thresholds and channels are.  Arguments, limits and checks as lad_score_runs (tables of lad_runs_fill, or the merged table and
+ * merged counts of lad_binarize_fill); workspace: its own, of lad_score_events_workspace_bytes for the sum of counts_host;
+ * events: DEVICE int64[channels][n_thresholds][n_min_lengths][7].  LAD_ERR_INVALID with lad_last_error() set, nothing launched and
+ * nothing written, for what lad_score_runs refuses, min_overlap_ms < 0 or min_overlap_pct outside 0..100. */
+int lad_score_events(const void *runs_workspace, const int32_t *table, const int32_t *counts_host, int64_t channels,
+                     int64_t frames, int32_t n_thresholds, const int32_t *bounds, const int32_t *offsets,
+                     const int32_t *bounds_host, const int32_t *offsets_host, int64_t n_intervals, const double *fps,
+                     const double *fps_host, const double *min_lengths, int32_t n_min_lengths,
+                     int32_t min_overlap_ms, int32_t min_overlap_pct, void *workspace, int64_t *events, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Threshold sweep with hysteresis and gap filling (csrc/binarize.hip): the event tables of K settings in one pass.
  * The reference has one threshold and a minimum length (laugh_segmenter.py:74-111); these are the two further controls of
  * event-detection post-processing, onset / offset / min_duration_off of pyannote.audio's Binarize restated on this project's

@@ -173,6 +173,11 @@ SIGNATURES = {
     "lad_score_runs": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_void_p,
                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
                                ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
+    # event-level scores of the sweep (csrc/events.hip)
+    "lad_score_events_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i64]),
+    "lad_score_events": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_void_p,
+                                 ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
+                                 ctypes.POINTER(c_double), c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     # threshold sweep with hysteresis and gap filling (csrc/binarize.hip)
     "lad_binarize_max_settings": (c_i32, []),
     "lad_binarize_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),

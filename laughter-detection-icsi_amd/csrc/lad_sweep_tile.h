@@ -1,7 +1,9 @@
-// What the threshold sweep's sources share (runs.hip, binarize.hip, score.hip): the tile geometry and the limits of a call, the fixed
-// load of a probability, run starts / ends of a tile's ballot words and their placement by rank, the workgroup scan, and the host
-// checks whose messages differ only in the entry point's name and in what it calls its K axis ("thresholds" / "settings").
-// lad_score_runs reads the workspace the other two wrote, so there is one definition of each.
+// What the threshold sweep's sources share (runs.hip, binarize.hip, score.hip, events.hip): the tile geometry and the limits of a
+// call, the fixed load of a probability, run starts / ends of a tile's ballot words and their placement by rank, the workgroup scan,
+// what the two scorers do alike with a run-table row and the interval index (the scans in front, the table a row belongs to, the
+// coverage look-up, the wave sum), and the host checks whose messages differ only in the entry point's name and in what it calls
+// its K axis ("thresholds" / "settings").  lad_score_runs and lad_score_events read the workspace the other two wrote, so there is
+// one definition of each.
 #pragma once
 #include <cmath>
 
@@ -17,6 +19,15 @@ constexpr int THREADS = WAVE * WAVES;
 constexpr int MAX_K = 64;                   // thresholds / settings per call: lane k of a wave carries number k's count / first row
 constexpr int64_t MAX_T = (int64_t)1 << 30; // frame indices and per-threshold run counts are int32
 constexpr int MAX_C = 65535;                // grid.y
+constexpr int CLASSES = 5;                  // of the interval index: INVALID, LAUGH, SPEECH, NOISE, SILENCE (enum lad_score_class)
+constexpr int MAX_L = 8;                    // min_lengths per scoring call: lane l * 7 + f of a wave carries one sum
+constexpr int64_t MAX_INTERVALS = (int64_t)1 << 30;
+constexpr int64_t MAX_ROWS = (int64_t)1 << 38;     // grid.x of a kernel with one lane per run-table row
+constexpr double MS = 1000.0;               // utils.to_frames: 1000 / frame_duration, frame_duration = 1 ms
+
+struct MinLengths {
+    double v[MAX_L];
+};
 
 // fix_over_underflow in float64 (the reference maps Python floats)
 template <typename T>
@@ -99,6 +110,95 @@ __device__ inline Acc block_scan(int64_t lo, int64_t hi, Load load, Store store)
     return carry;
 }
 
+// ---- the scorers (score.hip, events.hip) ----------------------------------------------------------------------------------------
+// the scans in front of a scorer, one workgroup each: workgroup s < segments: cum[i] = total length of the intervals before i in the
+// same (channel, class) s; workgroup `segments`: first_row[i] = rows of the run tables before table i (the counts lad_runs_count /
+// lad_binarize_fill left at the start of their workspace)
+__device__ inline void scan_index_and_counts(const int32_t *__restrict__ bounds, const int32_t *__restrict__ offsets, int64_t n_intervals,
+                                             int32_t *__restrict__ cum, int64_t segments, const int32_t *__restrict__ counts, int64_t CK,
+                                             int64_t *__restrict__ first_row) {
+    if ((int64_t)blockIdx.x == segments) {
+        block_scan<long long>(0, CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
+        return;
+    }
+    int64_t o0 = offsets[blockIdx.x], o1 = offsets[blockIdx.x + 1];
+    o0 = o0 < 0 ? 0 : (o0 > n_intervals ? n_intervals : o0);
+    o1 = o1 < o0 ? o0 : (o1 > n_intervals ? n_intervals : o1);
+    block_scan<long long>(o0, o1, [&](int64_t i) { return bounds[2 * i + 1] - bounds[2 * i]; },
+                          [&](int64_t i, long long v) { cum[i] = (int32_t)v; });
+}
+
+__device__ inline long long wave_sum64(long long s) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) s += __shfl_xor(s, d, WAVE);
+    return s;
+}
+
+// the table a row belongs to: the last (c, k) whose first row is <= row (an empty table shares its first row with the next one, so
+// the last such table is the one that holds the row)
+__device__ inline long long table_of_row(const int64_t *__restrict__ first_row, int64_t CK, int64_t row) {
+    int64_t at = 0, n = CK;
+    while (n > 1) {
+        const int64_t half = n >> 1;
+        if (first_row[at + half] <= row) at += half;
+        n -= half;
+    }
+    return at;
+}
+
+// a run's seconds, its keep bits (bit l: end - start > min_length l) and its millisecond interval (x[0], x[1]]
+__device__ inline unsigned run_ms(int32_t first, int32_t last, double fps, const MinLengths &ml, int L, int32_t (&x)[2]) {
+    const double start = (double)first / fps, end = (double)last / fps;
+    const double len = end - start;
+    unsigned keep = 0;
+#pragma unroll
+    for (int l = 0; l < MAX_L; ++l)
+        if (l < L && len > ml.v[l]) keep |= 1u << l;
+    x[0] = (int32_t)rint(start * MS);
+    x[1] = (int32_t)rint(end * MS);
+    return keep;
+}
+
+// F[2 j + s] = coverage of class j of channel c in (0, x[s]], j < NC: 2 NC searches advanced together (as many independent loads per
+// step), base[s] ending at the last interval with lo < x, if there is one.  size[j]: intervals of the class.  Every read is clamped
+// to the index.
+template <int NC>
+__device__ inline void coverage_pairs(int64_t c, const int32_t (&x)[2], const int32_t *__restrict__ bounds, const int32_t *__restrict__ cum,
+                                      const int32_t *__restrict__ offsets, int64_t n_intervals, int32_t (&F)[2 * NC], int32_t (&size)[NC]) {
+    int32_t base[2 * NC], left[2 * NC];
+    int32_t longest = 0;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        int64_t o0 = offsets[c * CLASSES + j], o1 = offsets[c * CLASSES + j + 1];
+        o0 = o0 < 0 ? 0 : (o0 > n_intervals ? n_intervals : o0);
+        o1 = o1 < o0 ? o0 : (o1 > n_intervals ? n_intervals : o1);
+        size[j] = (int32_t)(o1 - o0);
+        base[2 * j] = base[2 * j + 1] = (int32_t)o0;
+        left[2 * j] = left[2 * j + 1] = size[j];
+        longest = size[j] > longest ? size[j] : longest;
+    }
+    for (int32_t n = longest; n > 1; n -= n >> 1) {
+#pragma unroll
+        for (int s = 0; s < 2 * NC; ++s) {
+            const int32_t half = left[s] >> 1;
+            if (half > 0) {
+                const int32_t mid = base[s] + half;
+                if (bounds[2 * (int64_t)mid] < x[s & 1]) base[s] = mid;
+                left[s] -= half;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 2 * NC; ++s) {
+        F[s] = 0;
+        if (size[s >> 1] > 0) {
+            const int32_t lo = bounds[2 * (int64_t)base[s]], hi = bounds[2 * (int64_t)base[s] + 1];
+            const int32_t xs = x[s & 1];
+            if (lo < xs) F[s] = cum[base[s]] + (xs < hi ? xs : hi) - lo;
+        }
+    }
+}
+
 // ---- host side: `who` is the entry point, `what` its name for the K axis -------------------------------------------------------
 inline int check_sizes(const char *who, const char *what, int64_t channels, int64_t frames, int32_t K) {
     LAD_REQUIRE(channels >= 1 && channels <= MAX_C && frames >= 1 && frames <= MAX_T && K >= 1 && K <= MAX_K,
@@ -125,6 +225,51 @@ inline int check_fps(const char *who, const double *fps_host, int64_t channels) 
     for (int64_t c = 0; c < channels; ++c)
         LAD_REQUIRE(fps_host[c] > 0.0 && std::isfinite(fps_host[c]), "%s: fps[%lld] = %g is not a positive finite number", who,
                     (long long)c, fps_host[c]);
+    return LAD_OK;
+}
+
+// what a scorer asks of its sizes (message by the caller: the two name different things)
+inline bool score_sizes_ok(int64_t C, int64_t n_intervals, int64_t K, int64_t L) {
+    return C >= 1 && C <= MAX_C && n_intervals >= 0 && n_intervals <= MAX_INTERVALS && K >= 1 && K <= MAX_K && L >= 1 && L <= MAX_L;
+}
+
+// the min_lengths of a scoring call as a kernel argument
+inline int load_min_lengths(const char *who, const double *min_lengths, int L, MinLengths &ml) {
+    for (int l = 0; l < MAX_L; ++l) {
+        ml.v[l] = l < L ? min_lengths[l] : 0.0;
+        LAD_REQUIRE(ml.v[l] == ml.v[l], "%s: min_lengths[%d] is NaN", who, l);
+    }
+    return LAD_OK;
+}
+
+// what a scorer asks of the time base and the interval index before it launches anything: millisecond values are int32
+// (to_frames(frames / fps) < 2^31 for every channel); offsets ascend from 0 to n_intervals; within a (channel, class) intervals are
+// non-empty, sorted and disjoint
+inline int check_index(const char *who, int64_t channels, int64_t frames, const double *fps_host, const int32_t *offsets_host,
+                       const int32_t *bounds_host, int64_t n_intervals) {
+    if (int rc = check_fps(who, fps_host, channels)) return rc;
+    for (int64_t c = 0; c < channels; ++c) {
+        const double f = fps_host[c];
+        const double ms = std::nearbyint((double)frames / f * MS);
+        LAD_REQUIRE(ms < 2147483648.0, "%s: millisecond overflow: %lld frames at fps[%lld] = %g end at %.0f ms, int32 holds 2^31 - 1", who,
+                    (long long)frames, (long long)c, f, ms);
+    }
+    LAD_REQUIRE(offsets_host[0] == 0 && offsets_host[channels * CLASSES] == n_intervals,
+                "%s: index offsets run from %d to %d, expected 0 to %lld", who, offsets_host[0], offsets_host[channels * CLASSES],
+                (long long)n_intervals);
+    for (int64_t s = 0; s < channels * CLASSES; ++s) {
+        const int64_t o0 = offsets_host[s], o1 = offsets_host[s + 1];
+        LAD_REQUIRE(o0 <= o1 && o1 <= n_intervals, "%s: index offsets do not ascend at channel %lld, class %lld (%lld, %lld)", who,
+                    (long long)(s / CLASSES), (long long)(s % CLASSES), (long long)o0, (long long)o1);
+        for (int64_t i = o0; i < o1; ++i) {
+            const int32_t lo = bounds_host[2 * i], hi = bounds_host[2 * i + 1];
+            LAD_REQUIRE(lo >= 0 && hi > lo, "%s: index interval %lld (%d, %d] of channel %lld, class %lld is empty or negative", who,
+                        (long long)i, lo, hi, (long long)(s / CLASSES), (long long)(s % CLASSES));
+            LAD_REQUIRE(i == o0 || lo >= bounds_host[2 * i - 1],
+                        "%s: index interval %lld (%d, %d] of channel %lld, class %lld is unsorted or overlaps the one before it", who,
+                        (long long)i, lo, hi, (long long)(s / CLASSES), (long long)(s % CLASSES));
+        }
+    }
     return LAD_OK;
 }
 

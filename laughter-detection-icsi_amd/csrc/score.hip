@@ -30,38 +30,14 @@
 
 namespace {
 using namespace lad::sweep;
-constexpr int CLASSES = 5;                         // INVALID, LAUGH, SPEECH, NOISE, SILENCE
 constexpr int FIELDS = 7;                          // n_pred, n_valid, pred_ms, corr_ms, fp_speech_ms, fp_noise_ms, fp_silence_ms
-constexpr int MAX_L = 8;                           // min_lengths per call: lane l * 7 + f of a wave carries one sum
-constexpr int64_t MAX_INTERVALS = (int64_t)1 << 30;
-constexpr int64_t MAX_ROWS = (int64_t)1 << 38;     // grid.x of the row kernel
-constexpr double MS = 1000.0;                      // utils.to_frames: 1000 / frame_duration, frame_duration = 1 ms
 
-struct MinLengths {
-    double v[MAX_L];
-};
-
-// workgroup s < segments: cum[i] = total length of the intervals before i in the same (channel, class) s;
-// workgroup `segments`: first_row[i] = rows of the run tables before table i (the counts lad_runs_count left in its workspace)
+// the scans of lad_sweep_tile.h: cum per (channel, class), and each run table's first row
 __global__ __launch_bounds__(THREADS) void score_scan_kernel(const int32_t *__restrict__ bounds, const int32_t *__restrict__ offsets,
                                                              int64_t n_intervals, int32_t *__restrict__ cum, int64_t segments,
                                                              const int32_t *__restrict__ counts, int64_t CK,
                                                              int64_t *__restrict__ first_row) {
-    if ((int64_t)blockIdx.x == segments) {
-        block_scan<long long>(0, CK, [&](int64_t i) { return counts[i]; }, [&](int64_t i, long long v) { first_row[i] = v; });
-        return;
-    }
-    int64_t o0 = offsets[blockIdx.x], o1 = offsets[blockIdx.x + 1];
-    o0 = o0 < 0 ? 0 : (o0 > n_intervals ? n_intervals : o0);
-    o1 = o1 < o0 ? o0 : (o1 > n_intervals ? n_intervals : o1);
-    block_scan<long long>(o0, o1, [&](int64_t i) { return bounds[2 * i + 1] - bounds[2 * i]; },
-                          [&](int64_t i, long long v) { cum[i] = (int32_t)v; });
-}
-
-__device__ inline long long wave_sum64(long long s) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) s += __shfl_xor(s, d, WAVE);
-    return s;
+    scan_index_and_counts(bounds, offsets, n_intervals, cum, segments, counts, CK, first_row);
 }
 
 __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__restrict__ table, int64_t rows,
@@ -79,61 +55,12 @@ __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__re
     for (int f = 0; f < FIELDS; ++f) v[f] = 0;
     unsigned keep = 0;            // bit l: the run passes min_length l
     if (valid) {
-        // the table this row belongs to: the last (c, k) whose first row is <= row (an empty table shares its first row with the
-        // next one, so the last such table is the one that holds the row)
-        {
-            int64_t at = 0, n = CK;
-            while (n > 1) {
-                const int64_t half = n >> 1;
-                if (first_row[at + half] <= row) at += half;
-                n -= half;
-            }
-            g = at;
-        }
+        g = table_of_row(first_row, CK, row);
         const int c = (int)(g / K);
-        const double f = fps[c];
-        const double start = (double)table[2 * row] / f, end = (double)table[2 * row + 1] / f;
-        const double len = end - start;
-#pragma unroll
-        for (int l = 0; l < MAX_L; ++l)
-            if (l < L && len > ml.v[l]) keep |= 1u << l;
         int32_t x[2];
-        x[0] = (int32_t)rint(start * MS);
-        x[1] = (int32_t)rint(end * MS);
-        // ten searches (five classes x {a, b}) advanced together: base[s] ends at the last interval with lo < x, if there is one
-        int32_t base[2 * CLASSES], left[2 * CLASSES], size[CLASSES];
-        int32_t longest = 0;
-#pragma unroll
-        for (int j = 0; j < CLASSES; ++j) {
-            int64_t o0 = offsets[(int64_t)c * CLASSES + j], o1 = offsets[(int64_t)c * CLASSES + j + 1];
-            o0 = o0 < 0 ? 0 : (o0 > n_intervals ? n_intervals : o0);
-            o1 = o1 < o0 ? o0 : (o1 > n_intervals ? n_intervals : o1);
-            size[j] = (int32_t)(o1 - o0);
-            base[2 * j] = base[2 * j + 1] = (int32_t)o0;
-            left[2 * j] = left[2 * j + 1] = size[j];
-            longest = size[j] > longest ? size[j] : longest;
-        }
-        for (int32_t n = longest; n > 1; n -= n >> 1) {
-#pragma unroll
-            for (int s = 0; s < 2 * CLASSES; ++s) {
-                const int32_t half = left[s] >> 1;
-                if (half > 0) {
-                    const int32_t mid = base[s] + half;
-                    if (bounds[2 * (int64_t)mid] < x[s & 1]) base[s] = mid;
-                    left[s] -= half;
-                }
-            }
-        }
-        int32_t F[2 * CLASSES];
-#pragma unroll
-        for (int s = 0; s < 2 * CLASSES; ++s) {
-            F[s] = 0;
-            if (size[s >> 1] > 0) {
-                const int32_t lo = bounds[2 * (int64_t)base[s]], hi = bounds[2 * (int64_t)base[s] + 1];
-                const int32_t xs = x[s & 1];
-                if (lo < xs) F[s] = cum[base[s]] + (xs < hi ? xs : hi) - lo;
-            }
-        }
+        keep = run_ms(table[2 * row], table[2 * row + 1], fps[c], ml, L, x);
+        int32_t F[2 * CLASSES], size[CLASSES];
+        coverage_pairs<CLASSES>(c, x, bounds, cum, offsets, n_intervals, F, size);
         const int32_t pred = (x[1] - x[0]) - (F[1] - F[0]);      // |(a, b] \ INVALID|
         v[0] = 1;
         v[1] = size[0] > 0 ? (pred > 0 ? 1 : 0) : 1;              // analyse.py:185-187
@@ -167,15 +94,12 @@ __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__re
 
 using lad::up256;
 
-inline bool sizes_ok(int64_t C, int64_t n_intervals, int64_t K, int64_t L) {
-    return C >= 1 && C <= MAX_C && n_intervals >= 0 && n_intervals <= MAX_INTERVALS && K >= 1 && K <= MAX_K && L >= 1 && L <= MAX_L;
-}
 }  // namespace
 
 extern "C" int32_t lad_score_max_min_lengths(void) { return MAX_L; }
 
 extern "C" int64_t lad_score_workspace_bytes(int64_t channels, int64_t n_intervals, int32_t n_thresholds, int32_t n_min_lengths) {
-    if (!sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths)) {
+    if (!score_sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths)) {
         lad::fail(LAD_ERR_INVALID,
                   "lad_score_workspace_bytes: channels 1..%d, intervals 0..2^30, thresholds 1..%d, min_lengths 1..%d (got %lld, %lld, %d, %d)",
                   MAX_C, MAX_K, MAX_L, (long long)channels, (long long)n_intervals, n_thresholds, n_min_lengths);
@@ -190,7 +114,7 @@ extern "C" int lad_score_runs(const void *runs_workspace, const int32_t *table, 
                               const double *fps_host, const double *min_lengths, int32_t n_min_lengths, void *workspace,
                               int64_t *scores, void *stream) {
     using namespace lad;
-    LAD_REQUIRE(sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths) && frames >= 1 && frames <= MAX_T,
+    LAD_REQUIRE(score_sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths) && frames >= 1 && frames <= MAX_T,
                 "lad_score_runs: channels 1..%d, frames 1..2^30, intervals 0..2^30, thresholds 1..%d, min_lengths 1..%d "
                 "(got %lld, %lld, %lld, %d, %d)",
                 MAX_C, MAX_K, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_thresholds, n_min_lengths);
@@ -200,36 +124,8 @@ extern "C" int lad_score_runs(const void *runs_workspace, const int32_t *table, 
     const int K = n_thresholds, L = n_min_lengths;
     const int64_t CK = channels * K;
     MinLengths ml;
-    for (int l = 0; l < MAX_L; ++l) {
-        ml.v[l] = l < L ? min_lengths[l] : 0.0;
-        LAD_REQUIRE(ml.v[l] == ml.v[l], "lad_score_runs: min_lengths[%d] is NaN", l);
-    }
-    // millisecond values are int32: to_frames(frames / fps) < 2^31 for every channel
-    if (int rc = check_fps("lad_score_runs", fps_host, channels)) return rc;
-    for (int64_t c = 0; c < channels; ++c) {
-        const double f = fps_host[c];
-        const double ms = std::nearbyint((double)frames / f * MS);
-        LAD_REQUIRE(ms < 2147483648.0,
-                    "lad_score_runs: millisecond overflow: %lld frames at fps[%lld] = %g end at %.0f ms, int32 holds 2^31 - 1",
-                    (long long)frames, (long long)c, f, ms);
-    }
-    // the index: offsets ascend from 0 to n_intervals; within a (channel, class) intervals are non-empty, sorted and disjoint
-    LAD_REQUIRE(offsets_host[0] == 0 && offsets_host[channels * CLASSES] == n_intervals,
-                "lad_score_runs: index offsets run from %d to %d, expected 0 to %lld", offsets_host[0],
-                offsets_host[channels * CLASSES], (long long)n_intervals);
-    for (int64_t s = 0; s < channels * CLASSES; ++s) {
-        const int64_t o0 = offsets_host[s], o1 = offsets_host[s + 1];
-        LAD_REQUIRE(o0 <= o1 && o1 <= n_intervals, "lad_score_runs: index offsets do not ascend at channel %lld, class %lld (%lld, %lld)",
-                    (long long)(s / CLASSES), (long long)(s % CLASSES), (long long)o0, (long long)o1);
-        for (int64_t i = o0; i < o1; ++i) {
-            const int32_t lo = bounds_host[2 * i], hi = bounds_host[2 * i + 1];
-            LAD_REQUIRE(lo >= 0 && hi > lo, "lad_score_runs: index interval %lld (%d, %d] of channel %lld, class %lld is empty or negative",
-                        (long long)i, lo, hi, (long long)(s / CLASSES), (long long)(s % CLASSES));
-            LAD_REQUIRE(i == o0 || lo >= bounds_host[2 * i - 1],
-                        "lad_score_runs: index interval %lld (%d, %d] of channel %lld, class %lld is unsorted or overlaps the one before it",
-                        (long long)i, lo, hi, (long long)(s / CLASSES), (long long)(s % CLASSES));
-        }
-    }
+    if (int rc = load_min_lengths("lad_score_runs", min_lengths, L, ml)) return rc;
+    if (int rc = check_index("lad_score_runs", channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
     const int64_t rows = total_runs("lad_score_runs", counts_host, CK, frames);
     if (rows < 0) return LAD_ERR_INVALID;
     LAD_REQUIRE(rows <= MAX_ROWS, "lad_score_runs: %lld run-table rows, at most 2^38 per call", (long long)rows);

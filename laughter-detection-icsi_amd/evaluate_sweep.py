@@ -22,6 +22,11 @@ its thresholds: on the host with scipy, under the device scorer on the GPU (csrc
 `--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling to the sweep (laugh_segmenter.binarize_instances
 under the host scorer, csrc/binarize.hip under the device scorer): the CSVs get the columns offset_drop and min_gap behind min_len
 and the summary is grouped by all four.  Without the two flags the files are what they were.
+`--events` (default: off; not in the reference, which counts events and never matches them) also writes
+`event_df_per_meeting.csv` and `event_sum_stats.csv`: event-level precision, recall and F1, fragments per touched event and mean
+onset / offset errors (sweep_eval.event_rows; the convention stands above lad_score_events in include/lad_hip.h), with
+`--event_min_overlap_ms` and `--event_min_overlap_pct` deciding when an event or a prediction counts as hit; under the device
+scorer from csrc/events.hip.  Without the flag the directory holds the two files above and nothing else.
 """
 import argparse
 import csv
@@ -83,7 +88,21 @@ def float_list(text):
     return values
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None):
+def non_negative_int(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"an integer >= 0, got {text}")
+    return value
+
+
+def percent(text):
+    value = int(text)
+    if not 0 <= value <= 100:
+        raise argparse.ArgumentTypeError(f"an integer in 0..100, got {text}")
+    return value
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None, events=None):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
@@ -91,7 +110,7 @@ def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=
         padded[c, :len(t)] = t
     lengths = [len(t) for t in tracks] if lowpass is not None else None
     return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
-                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps)
+                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps, events=events)
 
 
 def write_csv(path, columns, rows):
@@ -123,6 +142,14 @@ def build_parser():
     parser.add_argument('--min_gaps', type=float_list, default=None,
                         help='(not in the reference) comma-separated list of seconds: events separated by a pause of at most this '
                              'become one, before the min_length filter; default: absent (no gap-filling axis)')
+    parser.add_argument('--events', action='store_true',
+                        help='(not in the reference) also write event_df_per_meeting.csv and event_sum_stats.csv: event-level '
+                             'precision / recall / F1, fragmentation and onset / offset errors against the merged laugh intervals')
+    parser.add_argument('--event_min_overlap_ms', type=non_negative_int, default=1,
+                        help='an event (a prediction) is hit if at least this many of its milliseconds are predicted (transcribed '
+                             'laughter), and at least 1; default: 1')
+    parser.add_argument('--event_min_overlap_pct', type=percent, default=0,
+                        help='... and at least this many per cent of it (of its part outside INVALID), 0..100; default: 0')
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
 
@@ -143,19 +170,29 @@ def main(argv=None):
                 raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
     binarize = args.offset_drops is not None or args.min_gaps is not None
     extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps) if binarize else {}
+    criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if args.events else {}
     if args.scorer == "device":
-        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra)
+        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
     else:
         if args.lowpass is not None:
             import laugh_segmenter
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
-        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra)
+        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
+    if args.events:
+        scores, events = scores
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
     os.makedirs(args.out_dir, exist_ok=True)
     write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"),
               sweep_eval.EVAL_COLUMNS_BINARIZE if binarize else sweep_eval.EVAL_COLUMNS, per_meeting)
     write_csv(os.path.join(args.out_dir, "sum_stats.csv"), sweep_eval.SUM_COLUMNS_BINARIZE if binarize else sweep_eval.SUM_COLUMNS,
               sweep_eval.calc_sum_stats(per_meeting, binarize=binarize))
+    if args.events:
+        per_meeting_events = sweep_eval.event_rows(scores, events, channels, thresholds, min_lengths, index, **extra)
+        write_csv(os.path.join(args.out_dir, "event_df_per_meeting.csv"),
+                  sweep_eval.EVENT_COLUMNS_BINARIZE if binarize else sweep_eval.EVENT_COLUMNS, per_meeting_events)
+        write_csv(os.path.join(args.out_dir, "event_sum_stats.csv"),
+                  sweep_eval.EVENT_SUM_COLUMNS_BINARIZE if binarize else sweep_eval.EVENT_SUM_COLUMNS,
+                  sweep_eval.event_sum_stats(per_meeting_events, binarize=binarize))
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

@@ -15,10 +15,17 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
                            csrc/binarize.hip) and then return (C, K, D, G, L, 7).
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
+    event_scores_instances host event scorer of one channel's dictionary -> {key: 7 ints} (include/lad_hip.h: lad_score_events has
+                           the convention; not in the reference, which counts events on both sides and never matches them)
+                           score_sweep_host / score_sweep_device take events=(min_overlap_ms, min_overlap_pct) and then return
+                           (scores, events), the second from event_scores_instances / csrc/events.hip
+    event_rows             per (meeting, threshold, min_len) event precision, recall, F1, fragmentation and boundary errors
+    event_sum_stats        the same figures over all meetings
 
 Everything is integer arithmetic plus a few IEEE float64 operations, so host and device agree exactly.
 """
 import ctypes
+import operator
 
 import numpy as np
 
@@ -31,6 +38,13 @@ SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.
 # with the hysteresis / gap-filling axes (not in the reference): offset_drop and min_gap follow min_len
 EVAL_COLUMNS_BINARIZE = EVAL_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVAL_COLUMNS[3:]
 SUM_COLUMNS_BINARIZE = SUM_COLUMNS[:2] + ["offset_drop", "min_gap"] + SUM_COLUMNS[2:]
+EVENT_FIELDS = ("n_ref", "ref_touched", "ref_hit", "pred_hit", "links", "onset_abs_ms", "offset_abs_ms")      # enum lad_event_field
+EVENT_COLUMNS = ["meeting", "threshold", "min_len", "event_precision", "event_recall", "event_f1", "num_ref_events",
+                 "ref_events_touched", "ref_events_hit", "valid_pred_laughs", "pred_laughs_hit", "links",
+                 "fragments_per_touched_event", "mean_onset_err", "mean_offset_err"]
+EVENT_COLUMNS_BINARIZE = EVENT_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVENT_COLUMNS[3:]
+EVENT_SUM_COLUMNS = EVENT_COLUMNS[1:]
+EVENT_SUM_COLUMNS_BINARIZE = EVENT_COLUMNS_BINARIZE[1:]
 ROW_COLUMNS = ("meeting_id", "part_id", "chan", "start", "end", "length", "type", "laugh_type")
 CHANNEL_COLUMNS = ("meeting_id", "part_id", "chan", "length")
 FACTOR = 1000.0                # utils.py:14: 1000 / frame_duration, frame_duration = 1 ms (config.py:46-52)
@@ -261,6 +275,54 @@ def score_instances(instances, index, meeting_id, chan):
     return out
 
 
+def _event_criteria(events):
+    """(min_overlap_ms, min_overlap_pct) as two ints (TypeError for anything that is not an integer)."""
+    min_ms, min_pct = (operator.index(v) for v in events)
+    return min_ms, min_pct
+
+
+def _event_spans(a, b, sets, min_ms, min_pct):
+    """The seven integers of lad_score_events for predictions (a, b] (int64 arrays in table order) against the scoring sets."""
+    invalid, laugh = sets[0], sets[1]
+    need = max(1, min_ms)
+    lov = coverage(laugh, b) - coverage(laugh, a)
+    pred = (b - a) - (coverage(invalid, b) - coverage(invalid, a))
+    pred_hit = int(np.count_nonzero((lov >= need) & (100 * lov >= min_pct * pred)))
+    real = b > a                                                                   # a == b overlaps nothing
+    a, b = a[real], b[real]
+    if len(laugh) == 0 or len(a) == 0:
+        return (len(laugh), 0, 0, pred_hit, 0, 0, 0)
+    # the predictions left are disjoint with a and b ascending, so those linked to (lo, hi] are the rows from the first with b > lo
+    # up to the last with a < hi, and cov is the coverage of the prediction set itself
+    lo, hi = laugh[:, 0], laugh[:, 1]
+    i0, i1 = np.searchsorted(b, lo, side="right"), np.searchsorted(a, hi, side="left")
+    frag = i1 - i0
+    spans = np.stack([a, b], axis=1)
+    cov = coverage(spans, hi) - coverage(spans, lo)
+    hit = (cov >= need) & (100 * cov >= min_pct * (hi - lo))
+    onset = np.abs(a[np.minimum(i0, len(a) - 1)] - lo)
+    offset = np.abs(b[np.maximum(i1 - 1, 0)] - hi)
+    return (len(laugh), int(np.count_nonzero(frag)), int(np.count_nonzero(hit)), pred_hit, int(frag.sum()), int(onset[hit].sum()),
+            int(offset[hit].sum()))
+
+
+def event_scores_instances(instances, index, meeting_id, chan, min_overlap_ms=1, min_overlap_pct=0):
+    """Host event scorer of one channel: instances as get_laughter_instances / binarize_instances return them -> {key: (n_ref,
+    ref_touched, ref_hit, pred_hit, links, onset_abs_ms, offset_abs_ms)} by the convention above lad_score_events in
+    include/lad_hip.h: the events are the channel's LAUGH intervals (transcribed laughter minus INVALID, merged), a prediction is
+    (to_frames(start), to_frames(end)], a pair is linked iff it shares a millisecond.  An event is hit iff the predictions cover
+    max(1, min_overlap_ms) ms and min_overlap_pct per cent of it, a prediction iff LAUGH covers as much of its part outside INVALID."""
+    min_ms, min_pct = _event_criteria((min_overlap_ms, min_overlap_pct))
+    if min_ms < 0 or not 0 <= min_pct <= 100:
+        raise ValueError(f"min_overlap_ms >= 0 and min_overlap_pct in 0..100, got ({min_ms}, {min_pct})")
+    sets = index.scoring_sets(meeting_id, chan)
+    out = {}
+    for key, spans in instances.items():
+        s = np.asarray(spans, dtype=np.float64).reshape(-1, 2)
+        out[key] = _event_spans(to_frames(s[:, 0]), to_frames(s[:, 1]), sets, min_ms, min_pct)
+    return out
+
+
 def _binarize_axes(offset_drops, min_gaps):
     """None, or the two extra axes as lists (one given: the other is [0.0], which changes nothing)."""
     if offset_drops is None and min_gaps is None:
@@ -280,30 +342,36 @@ def _score_shape(C, thresholds, min_lengths, axes):
     return (C, len(thresholds), *([] if axes is None else [len(a) for a in axes]), len(min_lengths), len(FIELDS))
 
 
-def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None):
+def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None, events=None):
     """laugh_segmenter.get_laughter_instances + score_instances per track -> int64 (C, K, L, 7).  tracks: C arrays (lengths may
     differ); channels: C (meeting_id, chan); fps: a float or C floats.
     offset_drops / min_gaps (either given): laugh_segmenter.binarize_instances instead -- hysteresis with offset = threshold - drop
-    and gap filling -> int64 (C, K, D, G, L, 7)."""
+    and gap filling -> int64 (C, K, D, G, L, 7).
+    events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an array of the same shape with the seven
+    EVENT_FIELDS of event_scores_instances."""
     import laugh_segmenter as ls
     thresholds, min_lengths = list(thresholds), list(min_lengths)
     f = ls._fps_per_channel(fps, len(channels), each=float).tolist()
     axes = _binarize_axes(offset_drops, min_gaps)
     cells = _cells(thresholds, min_lengths, axes)
     out = np.zeros(_score_shape(len(channels), thresholds, min_lengths, axes), np.int64)
+    ev = None if events is None else np.zeros(out.shape, np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
         if axes is None:
             instances = ls.get_laughter_instances(track, thresholds, min_lengths, f[c])
         else:
             instances = ls.binarize_instances(track, thresholds, min_lengths, f[c], *axes)
         got = score_instances(instances, index, *mc)
+        got_ev = None if events is None else event_scores_instances(instances, index, *mc, *events)
         for at, thr, min_l, extra in cells:
             out[(c, *at)] = got[(thr, *extra, min_l)]
-    return out
+            if ev is not None:
+                ev[(c, *at)] = got_ev[(thr, *extra, min_l)]
+    return out if events is None else (out, ev)
 
 
 def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
-                       min_gaps=None):
+                       min_gaps=None, events=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
     TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
@@ -312,7 +380,10 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     lad_runs_count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN).
     offset_drops / min_gaps (either given): hysteresis with offset = threshold - drop and gap filling -> int64 (C, K, D, G, L, 7),
     equal to score_sweep_host with the same two lists: lad_binarize_count + lad_binarize_fill + the same lad_score_runs, at most
-    lad_binarize_max_settings() of the K * D * G settings per round; the low-pass composes in front as above."""
+    lad_binarize_max_settings() of the K * D * G settings per round; the low-pass composes in front as above.
+    events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
+    EVENT_FIELDS, equal to score_sweep_host's: lad_score_events on the same workspace and table as lad_score_runs, in the same
+    round; the two score arrays are all that crosses to the host.  Without it no further launch is made."""
     import torch
 
     import _hip
@@ -326,8 +397,15 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     fps_host = ls._fps_per_channel(fps, C, each=float)
     axes = _binarize_axes(offset_drops, min_gaps)
     out_shape = _score_shape(C, thresholds, min_lengths, axes)
+    criteria = None if events is None else _event_criteria(events)
     if T == 0 or 0 in out_shape:
-        return np.zeros(out_shape, np.int64)
+        if criteria is None:
+            return np.zeros(out_shape, np.int64)
+        ev = np.zeros(out_shape, np.int64)          # (nothing to launch on: no prediction, the events of each channel counted)
+        if 0 not in out_shape:
+            offsets = (index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)).offsets_host
+            ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape((C,) + (1,) * (len(out_shape) - 2))
+        return np.zeros(out_shape, np.int64), ev
     if lowpass is not None:
         probs, dtype, _ = ls._device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
     elif lengths is not None:
@@ -342,7 +420,7 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         settings, step = thresholds, len(thresholds)
     else:
         settings, step = ls._binarize_keys(thresholds, *axes)[1], int(lib.lad_binarize_max_settings())
-    parts = []
+    parts, ev_parts = [], []
     for k0 in range(0, len(settings), step):
         chunk = settings[k0:k0 + step]
         n = len(chunk)
@@ -356,8 +434,20 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
                                           dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
                                           fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(ws[ws.numel() - sws_bytes:]), _hip.ptr(scores),
                                           _hip.stream_handle(probs.device)), "lad_score_runs")
+            if criteria is not None:
+                ews_bytes = lib.lad_score_events_workspace_bytes(C, dix.n_intervals, n, L, len(table))
+                _hip.check(0 if ews_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_events_workspace_bytes")
+                ews = torch.empty(ews_bytes, dtype=torch.uint8, device=probs.device)
+                ev = torch.empty((C, n, L, len(EVENT_FIELDS)), dtype=torch.int64, device=probs.device)
+                _hip.check(lib.lad_score_events(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
+                                                _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
+                                                dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
+                                                fps_host.ctypes.data_as(f64p), mls, L, *criteria, _hip.ptr(ews), _hip.ptr(ev),
+                                                _hip.stream_handle(probs.device)), "lad_score_events")
+                ev_parts.append(ev.cpu().numpy())
         parts.append(scores.cpu().numpy())
-    return np.concatenate(parts, axis=1).reshape(out_shape)
+    scores = np.concatenate(parts, axis=1).reshape(out_shape)
+    return scores if criteria is None else (scores, np.concatenate(ev_parts, axis=1).reshape(out_shape))
 
 
 def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None):
@@ -423,3 +513,57 @@ def calc_sum_stats(rows, binarize=False):
             recall = float(corr / transc)
         out.append([key[1], key[0], *key[2:], prec, recall])
     return out
+
+
+def _event_figures(n_ref, touched, hit, n_valid, pred_hit, links, onset_ms, offset_ms):
+    """The twelve values behind the keys of an event row, from integers: one float64 division per figure."""
+    prec = 1 if n_valid == 0 else pred_hit / n_valid                               # (the reference's rule for time precision)
+    recall = float("nan") if n_ref == 0 else hit / n_ref
+    if recall != recall:
+        f1 = float("nan")
+    else:
+        f1 = 0.0 if prec + recall == 0 else 2 * prec * recall / (prec + recall)
+    nan = float("nan")
+    return [prec, recall, f1, n_ref, touched, hit, n_valid, pred_hit, links, links / touched if touched else nan,
+            onset_ms / (FACTOR * hit) if hit else nan, offset_ms / (FACTOR * hit) if hit else nan]
+
+
+def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None):
+    """Per meeting and setting, in eval_rows' order, the values of EVENT_COLUMNS (EVENT_COLUMNS_BINARIZE with offset_drops / min_gaps)
+    from the two arrays of score_sweep_host / score_sweep_device with events=.  The integers are summed over the meeting's
+    participants first (channels without one are left out).  event_precision = pred_laughs_hit / valid_pred_laughs (scores'
+    n_valid), 1 where there is no valid prediction; event_recall = ref_events_hit / num_ref_events, NaN without an event; event_f1
+    NaN with a NaN recall and 0 where precision + recall is 0; fragments_per_touched_event = links / ref_events_touched, NaN
+    without one; mean_onset_err and mean_offset_err in seconds over the hit events, NaN without one."""
+    scores, events = np.asarray(scores), np.asarray(events)
+    if scores.shape != events.shape:
+        raise ValueError(f"scores {scores.shape} and events {events.shape} are not of one sweep")
+    axes = _binarize_axes(offset_drops, min_gaps)
+    settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
+    per_meeting = {}
+    for c, (m, chan) in enumerate(channels):
+        if index.participant(m, chan) is not None:
+            per_meeting.setdefault(m, []).append(c)
+    rows = []
+    for m in sorted(per_meeting):
+        for at, key in settings:
+            e = [sum(int(events[(c,) + at][f]) for c in per_meeting[m]) for f in range(len(EVENT_FIELDS))]
+            n_valid = sum(int(scores[(c,) + at][1]) for c in per_meeting[m])
+            rows.append([m, *key, *_event_figures(e[0], e[1], e[2], n_valid, e[3], e[4], e[5], e[6])])
+    return rows
+
+
+def event_sum_stats(rows, binarize=False):
+    """The figures of event_rows over all meetings, from the summed integers, grouped and ordered as calc_sum_stats: rows of
+    EVENT_SUM_COLUMNS (EVENT_SUM_COLUMNS_BINARIZE).  A row holds its two error sums as means in seconds; mean * 1000 * hit is
+    within a few units in the last place of the integer it came from, so rint gives that integer back (sums below 2^50 ms)."""
+    n_keys = 4 if binarize else 2
+    sums = {}
+    for r in rows:
+        v = r[1 + n_keys + 3:]                                                     # behind precision, recall and F1
+        hit = v[2]
+        ms = [int(np.rint(mean * FACTOR * hit)) if hit else 0 for mean in v[7:9]]
+        acc = sums.setdefault((r[2], r[1]) + tuple(r[3:1 + n_keys]), [0] * 8)
+        for i, x in enumerate(list(v[:6]) + ms):
+            acc[i] += int(x)
+    return [[key[1], key[0], *key[2:], *_event_figures(*sums[key])] for key in sorted(sums)]
