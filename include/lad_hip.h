@@ -796,6 +796,72 @@ int lad_binarize_fill(const void *probs, int32_t dtype, int64_t channels, int64_
                       int32_t *table, int64_t capacity_runs, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Two-state Viterbi decoding of the probability track (csrc/viterbi.hip): the run tables of the best on/off path for K settings
+ * in one pass.  The sweeps above decide each frame from that frame alone and repair the result with rules in seconds, which
+ * cannot see confidence; here each frame contributes its log-odds, each additional event costs a penalty, and the decoder returns
+ * the set of events with the best total score.  The reference has nothing like it.  The text below IS the specification
+ * (tests/_viterbi_model.py is a second implementation of it, in Python integers, with a brute-force maximiser beside it).
+ *
+ * Everything is integer arithmetic in int64.  The decoded path is then a pure function of its inputs, independent of the order
+ * of the scans, with identical bytes on every call.
+ *
+ * Frames.  v[i] is the fixed probability exactly as in lad_runs_count: p > 1 becomes 1, p <= 0 becomes 1e-7, NaN is kept, and a
+ * float32 sample is widened exactly.  The bucket of a frame is u[i] = (int)floor(v[i] * 65536.0), which lies in 0..65536.  The
+ * product is exact in float64.
+ * Emission table.  The caller supplies S, an int32 array of lad_viterbi_table_entries() = 65537 values with |S[u]| <= 2^24.  It
+ * does not have to be monotone.  The library never computes a logarithm: device `log` is not bit-equal to numpy's, while a
+ * look-up is.
+ * Settings.  Setting k is (bias[k], penalty[k]), both int32, with |bias| <= 2^24 and 0 <= penalty <= 2^26.  The frame score is
+ * s_k[i] = S[u[i]] - bias[k].  At a NaN frame the score is -2^31 instead.  No optimal path is on at such a frame, so NaN padding
+ * of a shorter channel stays off.
+ * Objective.  The states are off (0) and on (1), with off before frame 0.  A path's score is the sum of s[i] over its on frames,
+ * minus `penalty` for every frame that is on while its predecessor is off.  Leaving a run costs nothing.  With T <= 2^30, every
+ * partial sum stays inside +-2^62.
+ * Recursion.  Ties are decided exactly like this.  Start with d0 = 0, d1 = -penalty.  For t = 0..T-1, with (d0, d1) the values
+ * before frame t:
+ *   psi0[t] = (d1 > d0)              the state at t-1 if the state at t is off; a tie means off
+ *   psi1[t] = !(d0 - penalty > d1)   the state at t-1 if the state at t is on; a tie means on
+ *   d0' = max(d0, d1)
+ *   d1' = max(d0 - penalty, d1) + s[t]
+ * The state at T-1 is (d1 > d0), and best = max(d0, d1).  Backtrace with psi.  Frame 0's predecessor is not part of the path.
+ * Consequences.  The path's score equals `best`, and no other path scores more.  With penalty 0, a frame with s > 0 is on and a
+ * frame with s < 0 is off; a frame with s == 0 takes the state of the frame behind it, and is off at the end.
+ * Output.  The maximal on-runs of the path are rows (first_frame, last_frame), ascending, in int32 run tables laid out as
+ * lad_runs_fill lays them out: the (c, k) tables back to back in c * K + k order, with the int32 counts at the start of the
+ * workspace.  The workspace and table can therefore be handed to lad_score_runs and lad_score_events unchanged, with
+ * n_thresholds = K.
+ *
+ * Two steps, seven launches and one whatever K and channels are, no atomics, no float arithmetic behind the bucket:
+ *   lad_viterbi_count -> workspace: the on/off masks of every (channel, setting), 64 frames per word, and int32
+ *                        counts[channels * K] at its start; `best` if asked for.  The caller copies the counts to the host.
+ *   lad_viterbi_fill  -> table: int32[total][2] from the stored masks; the track is not read again.
+ * The tile is lad_runs_tile_frames() frames.
+ * ---------------------------------------------------------------------------------------------- */
+/* largest n_settings of one call (64) */
+int32_t lad_viterbi_max_settings(void);
+/* entries of the emission table (65537: buckets 0..65536) */
+int32_t lad_viterbi_table_entries(void);
+/* bytes of workspace for lad_viterbi_count / lad_viterbi_fill; needs no GPU.  -1 and lad_last_error() for channels outside
+ * 1..65535, frames outside 1..2^30 or n_settings outside 1..lad_viterbi_max_settings(). */
+int64_t lad_viterbi_workspace_bytes(int64_t channels, int64_t frames, int32_t n_settings);
+/* decoding step (seven launches on `stream`).  probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype:
+ * lad_runs_dtype).  emission: DEVICE int32[65537]; emission_host: HOST copy of the same values, range-checked before anything is
+ * launched.  bias, penalty: HOST int32[n_settings].  best: DEVICE int64[channels * n_settings] (c * K + k), or NULL.
+ * LAD_ERR_INVALID with lad_last_error() set and nothing launched for sizes out of range, an unknown dtype, a null pointer other
+ * than `best`, or a table entry, bias or penalty outside its bound. */
+int lad_viterbi_count(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const int32_t *emission,
+                      const int32_t *emission_host, const int32_t *bias, const int32_t *penalty, int32_t n_settings,
+                      void *workspace, int64_t *best, void *stream);
+/* the run tables (one launch on `stream`) from the masks the lad_viterbi_count before it left in `workspace`, with the same
+ * channels, frames and n_settings.  counts_host: HOST int32[channels * n_settings], the counts the caller read back.  table:
+ * DEVICE int32[capacity_runs][2].  LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for sizes out
+ * of range, a null pointer, counts that are not run counts of such a track, or counts that sum to more than capacity_runs.  The
+ * kernel never writes a row at or beyond capacity_runs, whatever the workspace holds.  Counts that sum to 0 return LAD_OK without
+ * a launch. */
+int lad_viterbi_fill(const void *workspace, const int32_t *counts_host, int64_t channels, int64_t frames, int32_t n_settings,
+                     int32_t *table, int64_t capacity_runs, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sampling-rate conversion of one channel by up / down = sr_out / sr_in (reduced), polyphase FIR on the device.
  * Replaces the host resampling of the reference's readers: librosa.load(audio_path, sr=44100) in front of the wav cuts
  * (segment_laughter.py:134) and librosa.load(sr=8000) of the code it descends from (laugh_segmenter.py:157-185).

@@ -186,6 +186,13 @@ SIGNATURES = {
     "lad_binarize_fill": (c_int, [c_void_p, c_i32, c_i64, c_i64] + [ctypes.POINTER(c_double)] * 3
                           + [c_i32, c_void_p, ctypes.POINTER(c_double), c_void_p, ctypes.POINTER(c_i32), c_void_p, c_void_p, c_i64,
                              c_void_p]),
+    # two-state Viterbi decoding of the probability track (csrc/viterbi.hip)
+    "lad_viterbi_max_settings": (c_i32, []),
+    "lad_viterbi_table_entries": (c_i32, []),
+    "lad_viterbi_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "lad_viterbi_count": (c_int, [c_void_p, c_i32, c_i64, c_i64, c_void_p] + [ctypes.POINTER(c_i32)] * 3
+                          + [c_i32, c_void_p, c_void_p, c_void_p]),
+    "lad_viterbi_fill": (c_int, [c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_i64, c_void_p]),
     # sampling-rate conversion (csrc/resample.hip)
     "lad_resample_out_len": (c_i64, [c_i64, c_i32, c_i32]),
     "lad_resample_tile_outputs": (c_i32, []),

@@ -27,6 +27,10 @@ and the summary is grouped by all four.  Without the two flags the files are wha
 onset / offset errors (sweep_eval.event_rows; the convention stands above lad_score_events in include/lad_hip.h), with
 `--event_min_overlap_ms` and `--event_min_overlap_pct` deciding when an event or a prediction counts as hit; under the device
 scorer from csrc/events.hip.  Without the flag the directory holds the two files above and nothing else.
+`--penalties` (default: absent; not in the reference) decodes every track with the two-state Viterbi decoder instead of cutting it
+frame by frame (laugh_segmenter.viterbi_instances under the host scorer, csrc/viterbi.hip under the device scorer): a frame counts
+its log-odds relative to the threshold, every event costs the penalty in nats, and the best set of events is scored.  The CSVs get
+the column penalty behind min_len.  It cannot be combined with --offset_drops / --min_gaps.
 """
 import argparse
 import csv
@@ -102,7 +106,8 @@ def percent(text):
     return value
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None, events=None):
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None, events=None,
+                 penalties=None):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
@@ -110,7 +115,8 @@ def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=
         padded[c, :len(t)] = t
     lengths = [len(t) for t in tracks] if lowpass is not None else None
     return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
-                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps, events=events)
+                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps, events=events,
+                                         penalties=penalties)
 
 
 def write_csv(path, columns, rows):
@@ -142,6 +148,10 @@ def build_parser():
     parser.add_argument('--min_gaps', type=float_list, default=None,
                         help='(not in the reference) comma-separated list of seconds: events separated by a pause of at most this '
                              'become one, before the min_length filter; default: absent (no gap-filling axis)')
+    parser.add_argument('--penalties', type=float_list, default=None,
+                        help='(not in the reference) comma-separated list of nats: two-state Viterbi decoding of every track, a frame '
+                             'counting its log-odds relative to the threshold and every event costing this much; default: absent '
+                             '(the frame-by-frame sweep)')
     parser.add_argument('--events', action='store_true',
                         help='(not in the reference) also write event_df_per_meeting.csv and event_sum_stats.csv: event-level '
                              'precision / recall / F1, fragmentation and onset / offset errors against the merged laugh intervals')
@@ -170,6 +180,13 @@ def main(argv=None):
                 raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
     binarize = args.offset_drops is not None or args.min_gaps is not None
     extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps) if binarize else {}
+    viterbi = args.penalties is not None
+    if viterbi and binarize:
+        raise SystemExit("--penalties cannot be combined with --offset_drops / --min_gaps")
+    if viterbi:
+        extra = dict(penalties=args.penalties)
+    kind = dict(penalties=args.penalties) if viterbi else dict(binarize=binarize)
+    suffix = "_VITERBI" if viterbi else ("_BINARIZE" if binarize else "")
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if args.events else {}
     if args.scorer == "device":
         scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
@@ -183,16 +200,15 @@ def main(argv=None):
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
     os.makedirs(args.out_dir, exist_ok=True)
     write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"),
-              sweep_eval.EVAL_COLUMNS_BINARIZE if binarize else sweep_eval.EVAL_COLUMNS, per_meeting)
-    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), sweep_eval.SUM_COLUMNS_BINARIZE if binarize else sweep_eval.SUM_COLUMNS,
-              sweep_eval.calc_sum_stats(per_meeting, binarize=binarize))
+              getattr(sweep_eval, "EVAL_COLUMNS" + suffix), per_meeting)
+    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), getattr(sweep_eval, "SUM_COLUMNS" + suffix),
+              sweep_eval.calc_sum_stats(per_meeting, **kind))
     if args.events:
         per_meeting_events = sweep_eval.event_rows(scores, events, channels, thresholds, min_lengths, index, **extra)
         write_csv(os.path.join(args.out_dir, "event_df_per_meeting.csv"),
-                  sweep_eval.EVENT_COLUMNS_BINARIZE if binarize else sweep_eval.EVENT_COLUMNS, per_meeting_events)
-        write_csv(os.path.join(args.out_dir, "event_sum_stats.csv"),
-                  sweep_eval.EVENT_SUM_COLUMNS_BINARIZE if binarize else sweep_eval.EVENT_SUM_COLUMNS,
-                  sweep_eval.event_sum_stats(per_meeting_events, binarize=binarize))
+                  getattr(sweep_eval, "EVENT_COLUMNS" + suffix), per_meeting_events)
+        write_csv(os.path.join(args.out_dir, "event_sum_stats.csv"), getattr(sweep_eval, "EVENT_SUM_COLUMNS" + suffix),
+                  sweep_eval.event_sum_stats(per_meeting_events, **kind))
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

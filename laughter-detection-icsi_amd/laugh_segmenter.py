@@ -17,6 +17,12 @@ does not have: hysteresis (an event starts above an onset threshold and lasts un
 threshold) and gap filling (events separated by a short pause become one, before the minimum-length filter).  The convention is
 written out in include/lad_hip.h (lad_binarize_count).  `binarize_frame_spans_device` / `binarize_instances_device` are their
 device forms (csrc/binarize.hip), with the same results and no CPU fallback.
+
+`viterbi_frame_spans` / `viterbi_instances` replace the frame-by-frame decision by two-state Viterbi decoding, which the reference
+does not have either: a frame contributes its log-odds relative to the threshold (an int32 look-up: `viterbi_emission_table`), every
+event costs a penalty, and the best-scoring set of events is returned.  The convention is written out in include/lad_hip.h
+(lad_viterbi_count).  `viterbi_frame_spans_device` / `viterbi_instances_device` are the device forms (csrc/viterbi.hip), with the same
+results and no CPU fallback.
 """
 import math
 import ctypes
@@ -348,3 +354,166 @@ def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=10
     triples, settings = _binarize_keys(thresholds, offset_drops, min_gaps)
     fps = np.float64(_check_fps(fps))
     return _instances_from_spans(triples, binarize_frame_spans_device(probs, settings, fps), min_lengths, fps)
+
+
+# ---- two-state Viterbi decoding (include/lad_hip.h: lad_viterbi_count has the convention) -----------------------------------------
+VITERBI_BUCKETS = 65536        # a frame's bucket is floor(v * 65536): 0..65536, lad_viterbi_table_entries() = 65537 table values
+VITERBI_NAN_SCORE = -2 ** 31
+_VITERBI_MAX_EMISSION, _VITERBI_MAX_PENALTY = 2 ** 24, 2 ** 26
+
+
+def viterbi_emission_table(unit=1024):
+    """The default emission table: int32 (65537,), S[u] = rint(unit * logit((u + 0.5) / 65537)) -- `unit` steps per nat, the log-odds
+    of the middle of bucket u, so both end points are finite (about +-11.8 nats)."""
+    p = (np.arange(VITERBI_BUCKETS + 1, dtype=np.float64) + 0.5) / (VITERBI_BUCKETS + 1)
+    return np.rint(unit * (np.log(p) - np.log1p(-p))).astype(np.int32)
+
+
+def _viterbi_table(table):
+    table = viterbi_emission_table() if table is None else np.ascontiguousarray(table, dtype=np.int32)
+    if table.shape != (VITERBI_BUCKETS + 1,) or np.abs(table.astype(np.int64)).max() > _VITERBI_MAX_EMISSION:
+        raise ValueError(f"the emission table is int32 ({VITERBI_BUCKETS + 1},) with |S[u]| <= 2^24")
+    return table
+
+
+def viterbi_settings(thresholds, penalties, table, unit=1024):
+    """[(bias, penalty)] as the decoder takes them, thresholds-major: bias = table[floor(threshold * 65536)] (a frame at the
+    threshold scores 0), penalty = rint(penalty in nats * unit).  ValueError for a threshold outside (0, 1] or a penalty that is
+    negative or not finite."""
+    out = []
+    for thr in thresholds:
+        if not 0.0 < float(thr) <= 1.0:
+            raise ValueError(f"a threshold of the decoder lies in (0, 1], got {thr}")
+        for pen in penalties:
+            if not (math.isfinite(float(pen)) and float(pen) >= 0):
+                raise ValueError(f"a penalty must be finite and >= 0, got {pen}")
+            penalty = int(np.rint(float(pen) * unit))
+            if penalty > _VITERBI_MAX_PENALTY:
+                raise ValueError(f"penalty {pen} is {penalty} table units, beyond 2^26")
+            out.append((int(table[int(math.floor(float(thr) * VITERBI_BUCKETS))]), penalty))
+    return out
+
+
+def _check_viterbi_settings(settings):
+    settings = [(int(b), int(p)) for b, p in settings]
+    for bias, penalty in settings:
+        if abs(bias) > _VITERBI_MAX_EMISSION or not 0 <= penalty <= _VITERBI_MAX_PENALTY:
+            raise ValueError(f"a setting is (bias, penalty) with |bias| <= 2^24 and 0 <= penalty <= 2^26, got ({bias}, {penalty})")
+    return settings
+
+
+def _viterbi_spans_host(probs, settings, table):
+    """[int64 (n, 2) array per setting (bias, penalty)]: the header's recursion as a loop over frames, vectorised over the settings."""
+    p = fix_probs(probs)
+    T, K = len(p), len(settings)
+    if T == 0 or K == 0:
+        return [np.zeros((0, 2), np.int64) for _ in settings]
+    nan = np.isnan(p)
+    u = np.floor(np.where(nan, 0.0, p) * float(VITERBI_BUCKETS)).astype(np.int64)
+    emitted = table.astype(np.int64)[u]
+    bias = np.asarray([s[0] for s in settings], np.int64)
+    pen = np.asarray([s[1] for s in settings], np.int64)
+    d0, d1 = np.zeros(K, np.int64), -pen
+    psi0, psi1 = np.zeros((T, K), bool), np.zeros((T, K), bool)
+    nan_score = np.full(K, VITERBI_NAN_SCORE, np.int64)
+    for t in range(T):
+        s = nan_score if nan[t] else emitted[t] - bias
+        enter = d0 - pen
+        psi0[t] = d1 > d0
+        psi1[t] = ~(enter > d1)
+        d0, d1 = np.maximum(d0, d1), np.maximum(enter, d1) + s
+    state = d1 > d0
+    on = np.zeros((T, K), bool)
+    for t in range(T - 1, -1, -1):
+        on[t] = state
+        state = np.where(state, psi1[t], psi0[t])
+    return [run_spans(on[:, k]) for k in range(K)]
+
+
+def viterbi_frame_spans(probs, threshold, penalty, table=None, unit=1024):
+    """Integer (first_frame, last_frame) runs of the best on/off path for one setting: log-odds relative to `threshold`, `penalty`
+    nats per event (viterbi_settings).  int64 (n, 2).  This is the parity form of csrc/viterbi.hip -- a Python loop over the frames
+    -- not a fast one: a 60 min track takes seconds."""
+    table = _viterbi_table(table)
+    return _viterbi_spans_host(probs, viterbi_settings([threshold], [penalty], table, unit), table)[0]
+
+
+def _viterbi_keys(thresholds, penalties, table, unit=1024):
+    return [(thr, pen) for thr in thresholds for pen in penalties], viterbi_settings(thresholds, penalties, table, unit)
+
+
+def viterbi_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
+    """{(threshold, penalty, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then penalty, then min_length: the runs of
+    the decoded path as (first / fps, last / fps), kept iff end - start > min_length.  Host form (see viterbi_frame_spans)."""
+    thresholds, min_lengths, penalties = list(thresholds), list(min_lengths), list(penalties)
+    table = _viterbi_table(table)
+    keys, settings = _viterbi_keys(thresholds, penalties, table)
+    return _instances_from_spans(keys, _viterbi_spans_host(probs, settings, table), min_lengths, np.float64(_check_fps(fps)))
+
+
+def _device_viterbi_tables(probs, dtype, settings, table_host, table_dev=None, extra_bytes=0, want_best=False):
+    """lad_viterbi_count + lad_viterbi_fill (include/lad_hip.h) on a (C, T) tensor that _device_track has passed, T >= 1, for at most
+    lad_viterbi_max_settings() settings (bias, penalty): the sibling of _device_tables, with the same (workspace, table, counts)
+    in front -- the counts at the start of the workspace, where the scorers read them, extra_bytes behind it for the caller -- and
+    `best`, the int64 (C * K,) scores on the device (None unless asked for)."""
+    import torch
+
+    import _hip
+    lib = _hip.lib()
+    C, T = probs.shape
+    K = len(settings)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    bias = (ctypes.c_int32 * K)(*[s[0] for s in settings])
+    penalty = (ctypes.c_int32 * K)(*[s[1] for s in settings])
+    ws_bytes = lib.lad_viterbi_workspace_bytes(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_viterbi_workspace_bytes")
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        if table_dev is None:
+            table_dev = torch.from_numpy(table_host).to(probs.device)
+        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
+        best = torch.empty(C * K, dtype=torch.int64, device=probs.device) if want_best else None
+        _hip.check(lib.lad_viterbi_count(_hip.ptr(probs), dtype, C, T, _hip.ptr(table_dev), table_host.ctypes.data_as(i32p), bias, penalty,
+                                         K, _hip.ptr(ws), _hip.ptr(best), stream), "lad_viterbi_count")
+        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
+        total = int(counts.sum(dtype=np.int64))
+        runs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=probs.device)
+        _hip.check(lib.lad_viterbi_fill(_hip.ptr(ws), counts.ctypes.data_as(i32p), C, T, K, _hip.ptr(runs), total, stream),
+                   "lad_viterbi_fill")
+        return ws, runs[:total], counts, best
+
+
+def viterbi_frame_spans_device(probs, settings, table=None):
+    """Device form of the decoder for a list of settings (bias, penalty) as viterbi_settings returns them.  probs: (T,) GPU tensor
+    (float32 / float64, contiguous) -> [int64 (n, 2) array per setting]; (C, T) -> one such list per channel.  More settings than
+    lad_viterbi_max_settings() go in several rounds.  No CPU fallback."""
+    import torch
+
+    import _hip
+    probs, dtype, single = _device_track(probs, "decoder")
+    table = _viterbi_table(table)
+    settings = _check_viterbi_settings(settings)
+    C, T = probs.shape
+    if T == 0 or C == 0 or not settings:
+        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
+    else:
+        out = [[] for _ in range(C)]
+        step = int(_hip.lib().lad_viterbi_max_settings())
+        table_dev = torch.from_numpy(table).to(probs.device)
+        for k0 in range(0, len(settings), step):
+            _, runs, counts, _ = _device_viterbi_tables(probs, dtype, settings[k0:k0 + step], table, table_dev)
+            part = _split_tables(counts.astype(np.int64).reshape(C, -1), runs.cpu().numpy())
+            for c in range(C):
+                out[c] += part[c]
+    return out[0] if single else out
+
+
+def viterbi_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
+    """viterbi_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
+    import _hip
+    if getattr(probs, "ndim", None) != 1:
+        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device decoder has no CPU fallback)")
+    thresholds, min_lengths, penalties = list(thresholds), list(min_lengths), list(penalties)
+    table = _viterbi_table(table)
+    keys, settings = _viterbi_keys(thresholds, penalties, table)
+    return _instances_from_spans(keys, viterbi_frame_spans_device(probs, settings, table), min_lengths, np.float64(_check_fps(fps)))

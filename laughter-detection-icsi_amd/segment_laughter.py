@@ -28,6 +28,10 @@ which segment_laughter.py:107-108 leaves commented out): scipy on the host under
 `--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling (laugh_segmenter.binarize_instances, or
 csrc/binarize.hip under `--segmenter device`): the instances of setting (thr, drop, gap, min_len) go to
 `t_<thr>/l_<min_len>/d_<drop>_g_<gap>/`.  Without the two flags paths and bytes are what they were.
+
+`--penalties` (default: absent) cuts the track with the two-state Viterbi decoder instead (laugh_segmenter.viterbi_instances, or
+csrc/viterbi.hip under `--segmenter device`): log-odds relative to the threshold, a penalty in nats per instance.  The instances of
+setting (thr, penalty, min_len) go to `t_<thr>/l_<min_len>/p_<penalty>/`.  It cannot be combined with the two flags above.
 """
 import argparse
 import os
@@ -112,13 +116,14 @@ def save_audio_instances(instances, audio_path, output_dir, rate=None):
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
-                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None):
+                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
     (None: the file's own).  lowpass: a cutoff (of Nyquist): the track is smoothed before the sweep (segment_laughter.py:107-108), on
     the host or on the device like the sweep itself; save_probs still gets the raw track.
-    offset_drops / min_gaps (either given): hysteresis and gap filling; the dictionary's keys are (thr, drop, gap, min_len)."""
+    offset_drops / min_gaps (either given): hysteresis and gap filling; the dictionary's keys are (thr, drop, gap, min_len).
+    penalties: the Viterbi decoder; the dictionary's keys are (thr, penalty, min_len).  Not together with the two above."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if save_to_audio_files and output_dir is None:
@@ -137,7 +142,13 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
         probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
             laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
     binarize = offset_drops is not None or min_gaps is not None
-    if binarize:
+    viterbi = penalties is not None
+    if viterbi and binarize:
+        raise ValueError("penalties (the Viterbi decoder) cannot be combined with offset_drops or min_gaps")
+    if viterbi:
+        extra = dict(penalties=list(penalties))
+        sweep = laugh_segmenter.viterbi_instances if segmenter == "host" else laugh_segmenter.viterbi_instances_device
+    elif binarize:
         extra = dict(offset_drops=list(offset_drops) if offset_drops is not None else [0.0],
                      min_gaps=list(min_gaps) if min_gaps is not None else [0.0])
         sweep = laugh_segmenter.binarize_instances if segmenter == "host" else laugh_segmenter.binarize_instances_device
@@ -154,11 +165,15 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
             if verbose and binarize:
                 print(f"Found {len(instances)} laughs for threshold {setting[0]}, offset drop {setting[1]}, min_gap {setting[2]} and "
                       f"min_length {setting[3]}.")
+            elif verbose and viterbi:
+                print(f"Found {len(instances)} laughs for threshold {setting[0]}, penalty {setting[1]} and min_length {setting[2]}.")
             elif verbose:
                 print(f"Found {len(instances)} laughs for threshold {setting[0]} and min_length {setting[1]}.")
             out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[-1]}')
             if binarize:
                 out_dir = os.path.join(out_dir, f'd_{setting[1]}_g_{setting[2]}')
+            if viterbi:
+                out_dir = os.path.join(out_dir, f'p_{setting[1]}')
             if save_to_textgrid or (save_to_audio_files and len(instances) > 0):
                 os.makedirs(out_dir, exist_ok=True)
             if save_to_audio_files and len(instances) > 0:
@@ -221,6 +236,9 @@ def build_parser():
     parser.add_argument('--min_gaps', type=float_list, default=None,
                         help="(not in the reference) comma-separated list of seconds: instances separated by a pause of at most this "
                              "become one, before the min_length filter; default: absent")
+    parser.add_argument('--penalties', type=float_list, default=None,
+                        help="(not in the reference) comma-separated list of nats: two-state Viterbi decoding of the track, a frame "
+                             "counting its log-odds relative to the threshold and every instance costing this much; default: absent")
     parser.add_argument('--resample', type=str, default='False',
                         help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
                              "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
@@ -250,7 +268,7 @@ def main(argv=None):
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
                   segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
-                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps)
+                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties)
 
 
 if __name__ == '__main__':

@@ -12,7 +12,8 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
     score_sweep_device     the same array for tracks in GPU memory (csrc/runs.hip + csrc/score.hip): besides the C x K run counts
                            only the scores cross to the host.  No CPU fallback.
                            Both take offset_drops= / min_gaps= (hysteresis and gap filling: laugh_segmenter.binarize_instances,
-                           csrc/binarize.hip) and then return (C, K, D, G, L, 7).
+                           csrc/binarize.hip) and then return (C, K, D, G, L, 7), or penalties= (the two-state Viterbi decoder:
+                           laugh_segmenter.viterbi_instances, csrc/viterbi.hip) and then return (C, K, P, L, 7).
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
     event_scores_instances host event scorer of one channel's dictionary -> {key: 7 ints} (include/lad_hip.h: lad_score_events has
@@ -45,6 +46,11 @@ EVENT_COLUMNS = ["meeting", "threshold", "min_len", "event_precision", "event_re
 EVENT_COLUMNS_BINARIZE = EVENT_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVENT_COLUMNS[3:]
 EVENT_SUM_COLUMNS = EVENT_COLUMNS[1:]
 EVENT_SUM_COLUMNS_BINARIZE = EVENT_COLUMNS_BINARIZE[1:]
+# with the Viterbi decoder's axis (not in the reference): penalty follows min_len
+EVAL_COLUMNS_VITERBI = EVAL_COLUMNS[:3] + ["penalty"] + EVAL_COLUMNS[3:]
+SUM_COLUMNS_VITERBI = SUM_COLUMNS[:2] + ["penalty"] + SUM_COLUMNS[2:]
+EVENT_COLUMNS_VITERBI = EVENT_COLUMNS[:3] + ["penalty"] + EVENT_COLUMNS[3:]
+EVENT_SUM_COLUMNS_VITERBI = EVENT_COLUMNS_VITERBI[1:]
 ROW_COLUMNS = ("meeting_id", "part_id", "chan", "start", "end", "length", "type", "laugh_type")
 CHANNEL_COLUMNS = ("meeting_id", "part_id", "chan", "length")
 FACTOR = 1000.0                # utils.py:14: 1000 / frame_duration, frame_duration = 1 ms (config.py:46-52)
@@ -323,17 +329,24 @@ def event_scores_instances(instances, index, meeting_id, chan, min_overlap_ms=1,
     return out
 
 
-def _binarize_axes(offset_drops, min_gaps):
-    """None, or the two extra axes as lists (one given: the other is [0.0], which changes nothing)."""
+def _extra_axes(offset_drops, min_gaps, penalties=None):
+    """None, or the extra axes as lists: the two of hysteresis and gap filling (one given: the other is [0.0], which changes
+    nothing), or the one of the Viterbi decoder.  The decoder has neither an offset nor a gap rule: both kinds together are refused."""
+    if penalties is not None:
+        if offset_drops is not None or min_gaps is not None:
+            raise ValueError("penalties (the Viterbi decoder) cannot be combined with offset_drops or min_gaps")
+        return (list(penalties),)
     if offset_drops is None and min_gaps is None:
         return None
     return (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
 
 
 def _cells(thresholds, min_lengths, axes):
-    """[(index into a score array behind the channel, threshold, min_length, () or (offset_drop, min_gap))], thresholds-major, then
-    drop, then gap, then min_length."""
-    extras = [((), ())] if axes is None else [((d, g), (drop, gap)) for d, drop in enumerate(axes[0]) for g, gap in enumerate(axes[1])]
+    """[(index into a score array behind the channel, threshold, min_length, (), (offset_drop, min_gap) or (penalty,))],
+    thresholds-major, then the extra axes in their order, then min_length."""
+    extras = [((), ())]
+    for axis in axes or ():
+        extras = [(at + (i,), extra + (v,)) for at, extra in extras for i, v in enumerate(axis)]
     return [((k, *at, l), thr, min_l, extra) for k, thr in enumerate(thresholds) for at, extra in extras
             for l, min_l in enumerate(min_lengths)]
 
@@ -342,23 +355,28 @@ def _score_shape(C, thresholds, min_lengths, axes):
     return (C, len(thresholds), *([] if axes is None else [len(a) for a in axes]), len(min_lengths), len(FIELDS))
 
 
-def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None, events=None):
+def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None, events=None,
+                     penalties=None):
     """laugh_segmenter.get_laughter_instances + score_instances per track -> int64 (C, K, L, 7).  tracks: C arrays (lengths may
     differ); channels: C (meeting_id, chan); fps: a float or C floats.
     offset_drops / min_gaps (either given): laugh_segmenter.binarize_instances instead -- hysteresis with offset = threshold - drop
     and gap filling -> int64 (C, K, D, G, L, 7).
+    penalties: laugh_segmenter.viterbi_instances instead -- the best on/off path for log-odds relative to the threshold and a
+    penalty per event -> int64 (C, K, P, L, 7); ValueError together with offset_drops or min_gaps.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an array of the same shape with the seven
     EVENT_FIELDS of event_scores_instances."""
     import laugh_segmenter as ls
     thresholds, min_lengths = list(thresholds), list(min_lengths)
     f = ls._fps_per_channel(fps, len(channels), each=float).tolist()
-    axes = _binarize_axes(offset_drops, min_gaps)
+    axes = _extra_axes(offset_drops, min_gaps, penalties)
     cells = _cells(thresholds, min_lengths, axes)
     out = np.zeros(_score_shape(len(channels), thresholds, min_lengths, axes), np.int64)
     ev = None if events is None else np.zeros(out.shape, np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
         if axes is None:
             instances = ls.get_laughter_instances(track, thresholds, min_lengths, f[c])
+        elif penalties is not None:
+            instances = ls.viterbi_instances(track, thresholds, min_lengths, f[c], *axes)
         else:
             instances = ls.binarize_instances(track, thresholds, min_lengths, f[c], *axes)
         got = score_instances(instances, index, *mc)
@@ -371,7 +389,7 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offs
 
 
 def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
-                       min_gaps=None, events=None):
+                       min_gaps=None, events=None, penalties=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
     TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
@@ -381,6 +399,9 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     offset_drops / min_gaps (either given): hysteresis with offset = threshold - drop and gap filling -> int64 (C, K, D, G, L, 7),
     equal to score_sweep_host with the same two lists: lad_binarize_count + lad_binarize_fill + the same lad_score_runs, at most
     lad_binarize_max_settings() of the K * D * G settings per round; the low-pass composes in front as above.
+    penalties: the Viterbi decoder -> int64 (C, K, P, L, 7), equal to score_sweep_host with the same list: lad_viterbi_count +
+    lad_viterbi_fill + the same lad_score_runs, at most lad_viterbi_max_settings() of the K * P settings per round; the low-pass
+    composes in front as above.  ValueError together with offset_drops or min_gaps.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
     EVENT_FIELDS, equal to score_sweep_host's: lad_score_events on the same workspace and table as lad_score_runs, in the same
     round; the two score arrays are all that crosses to the host.  Without it no further launch is made."""
@@ -395,7 +416,7 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     if C != len(channels):
         raise ValueError(f"{C} tracks for {len(channels)} channels")
     fps_host = ls._fps_per_channel(fps, C, each=float)
-    axes = _binarize_axes(offset_drops, min_gaps)
+    axes = _extra_axes(offset_drops, min_gaps, penalties)
     out_shape = _score_shape(C, thresholds, min_lengths, axes)
     criteria = None if events is None else _event_criteria(events)
     if T == 0 or 0 in out_shape:
@@ -418,6 +439,10 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
     if axes is None:            # one round whatever K is: the library refuses more thresholds than lad_runs_max_thresholds()
         settings, step = thresholds, len(thresholds)
+    elif penalties is not None:
+        emission = ls._viterbi_table(None)
+        settings, step = ls._viterbi_keys(thresholds, *axes, emission)[1], int(lib.lad_viterbi_max_settings())
+        emission_dev, fps_dev = torch.from_numpy(emission).to(probs.device), torch.from_numpy(fps_host).to(probs.device)
     else:
         settings, step = ls._binarize_keys(thresholds, *axes)[1], int(lib.lad_binarize_max_settings())
     parts, ev_parts = [], []
@@ -426,7 +451,10 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         n = len(chunk)
         sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
         _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
-        ws, table, counts, fps_dev = ls._device_tables(probs, dtype, chunk, fps_host, axes is not None, extra_bytes=sws_bytes)
+        if penalties is not None:
+            ws, table, counts, _ = ls._device_viterbi_tables(probs, dtype, chunk, emission, emission_dev, extra_bytes=sws_bytes)
+        else:
+            ws, table, counts, fps_dev = ls._device_tables(probs, dtype, chunk, fps_host, axes is not None, extra_bytes=sws_bytes)
         with torch.cuda.device(probs.device):
             scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
             _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
@@ -450,14 +478,15 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     return scores if criteria is None else (scores, np.concatenate(ev_parts, axis=1).reshape(out_shape))
 
 
-def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None):
+def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None, penalties=None):
     """eval_preds (analyse.py:152-225) for every meeting and setting: a list of 14-value rows in EVAL_COLUMNS order, meetings
     ascending, thresholds-major.  scores: (C, K, L, 7) of score_sweep_host / score_sweep_device for `channels`.  Channels without a
     participant are left out (analyse.py:27-28); the float sums run over participants in ascending part_id order (:173-197).
     offset_drops / min_gaps (either given): scores is (C, K, D, G, L, 7) and a row has the 16 values of EVAL_COLUMNS_BINARIZE
-    (offset_drop and min_gap behind min_len), thresholds-major, then drop, then gap, then min_len."""
+    (offset_drop and min_gap behind min_len), thresholds-major, then drop, then gap, then min_len.
+    penalties: scores is (C, K, P, L, 7) and a row has the 15 values of EVAL_COLUMNS_VITERBI (penalty behind min_len)."""
     scores = np.asarray(scores)
-    axes = _binarize_axes(offset_drops, min_gaps)
+    axes = _extra_axes(offset_drops, min_gaps, penalties)
     settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
@@ -492,13 +521,14 @@ def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=Non
     return rows
 
 
-def calc_sum_stats(rows, binarize=False):
+def calc_sum_stats(rows, binarize=False, penalties=None):
     """analyse.py:269-298: per (min_len, threshold) the sums of corr_pred_time, tot_pred_time and tot_transc_laugh_time over the
     meetings (in row order), precision = corr / pred (1 where pred is 0), recall = corr / transcribed (float division: NaN or inf
     where that is 0).  Rows of SUM_COLUMNS, ordered by (min_len, threshold) as the groupby.
     binarize: the rows are eval_rows' 16-value ones; grouped by (min_len, threshold, offset_drop, min_gap), rows of
-    SUM_COLUMNS_BINARIZE."""
-    n_keys = 4 if binarize else 2
+    SUM_COLUMNS_BINARIZE.
+    penalties (not None): the rows are eval_rows' 15-value ones; grouped by (min_len, threshold, penalty), rows of SUM_COLUMNS_VITERBI."""
+    n_keys = _n_keys(binarize, penalties)
     sums = {}
     for r in rows:
         acc = sums.setdefault((r[2], r[1]) + tuple(r[3:1 + n_keys]), [0, 0, 0])
@@ -515,6 +545,13 @@ def calc_sum_stats(rows, binarize=False):
     return out
 
 
+def _n_keys(binarize, penalties):
+    """Setting columns of a row behind the meeting: threshold and min_len, plus the extra axes."""
+    if binarize and penalties is not None:
+        raise ValueError("rows are of the hysteresis sweep or of the Viterbi decoder, not both")
+    return 4 if binarize else (3 if penalties is not None else 2)
+
+
 def _event_figures(n_ref, touched, hit, n_valid, pred_hit, links, onset_ms, offset_ms):
     """The twelve values behind the keys of an event row, from integers: one float64 division per figure."""
     prec = 1 if n_valid == 0 else pred_hit / n_valid                               # (the reference's rule for time precision)
@@ -528,8 +565,9 @@ def _event_figures(n_ref, touched, hit, n_valid, pred_hit, links, onset_ms, offs
             onset_ms / (FACTOR * hit) if hit else nan, offset_ms / (FACTOR * hit) if hit else nan]
 
 
-def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None):
-    """Per meeting and setting, in eval_rows' order, the values of EVENT_COLUMNS (EVENT_COLUMNS_BINARIZE with offset_drops / min_gaps)
+def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None, penalties=None):
+    """Per meeting and setting, in eval_rows' order, the values of EVENT_COLUMNS (EVENT_COLUMNS_BINARIZE with offset_drops / min_gaps,
+    EVENT_COLUMNS_VITERBI with penalties)
     from the two arrays of score_sweep_host / score_sweep_device with events=.  The integers are summed over the meeting's
     participants first (channels without one are left out).  event_precision = pred_laughs_hit / valid_pred_laughs (scores'
     n_valid), 1 where there is no valid prediction; event_recall = ref_events_hit / num_ref_events, NaN without an event; event_f1
@@ -538,7 +576,7 @@ def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_
     scores, events = np.asarray(scores), np.asarray(events)
     if scores.shape != events.shape:
         raise ValueError(f"scores {scores.shape} and events {events.shape} are not of one sweep")
-    axes = _binarize_axes(offset_drops, min_gaps)
+    axes = _extra_axes(offset_drops, min_gaps, penalties)
     settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
@@ -553,11 +591,12 @@ def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_
     return rows
 
 
-def event_sum_stats(rows, binarize=False):
+def event_sum_stats(rows, binarize=False, penalties=None):
     """The figures of event_rows over all meetings, from the summed integers, grouped and ordered as calc_sum_stats: rows of
-    EVENT_SUM_COLUMNS (EVENT_SUM_COLUMNS_BINARIZE).  A row holds its two error sums as means in seconds; mean * 1000 * hit is
-    within a few units in the last place of the integer it came from, so rint gives that integer back (sums below 2^50 ms)."""
-    n_keys = 4 if binarize else 2
+    EVENT_SUM_COLUMNS (EVENT_SUM_COLUMNS_BINARIZE; EVENT_SUM_COLUMNS_VITERBI with penalties).  A row holds its two error sums as
+    means in seconds; mean * 1000 * hit is within a few units in the last place of the integer it came from, so rint gives that
+    integer back (sums below 2^50 ms)."""
+    n_keys = _n_keys(binarize, penalties)
     sums = {}
     for r in rows:
         v = r[1 + n_keys + 3:]                                                     # behind precision, recall and F1
