@@ -44,6 +44,7 @@ for _p in (os.path.join(_PKG, "utils"), _PKG):
 
 import numpy as np  # noqa: E402
 
+import laugh_segmenter  # noqa: E402
 import sweep_eval  # noqa: E402
 
 
@@ -106,8 +107,7 @@ def percent(text):
     return value
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, offset_drops=None, min_gaps=None, events=None,
-                 penalties=None):
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, **axes_and_events):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
@@ -115,8 +115,7 @@ def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=
         padded[c, :len(t)] = t
     lengths = [len(t) for t in tracks] if lowpass is not None else None
     return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
-                                         lowpass=lowpass, lengths=lengths, offset_drops=offset_drops, min_gaps=min_gaps, events=events,
-                                         penalties=penalties)
+                                         lowpass=lowpass, lengths=lengths, **axes_and_events)
 
 
 def write_csv(path, columns, rows):
@@ -178,37 +177,31 @@ def main(argv=None):
         for (meeting, chan), t in zip(channels, tracks):
             if len(t) <= 9:
                 raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
-    binarize = args.offset_drops is not None or args.min_gaps is not None
-    extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps) if binarize else {}
-    viterbi = args.penalties is not None
-    if viterbi and binarize:
+    extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties)
+    try:
+        decoder, _ = laugh_segmenter.decoder_for(**extra)
+    except ValueError:
         raise SystemExit("--penalties cannot be combined with --offset_drops / --min_gaps")
-    if viterbi:
-        extra = dict(penalties=args.penalties)
-    kind = dict(penalties=args.penalties) if viterbi else dict(binarize=binarize)
-    suffix = "_VITERBI" if viterbi else ("_BINARIZE" if binarize else "")
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if args.events else {}
     if args.scorer == "device":
         scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
     else:
         if args.lowpass is not None:
-            import laugh_segmenter
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
         scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
     if args.events:
         scores, events = scores
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
     os.makedirs(args.out_dir, exist_ok=True)
-    write_csv(os.path.join(args.out_dir, "eval_df_per_meeting.csv"),
-              getattr(sweep_eval, "EVAL_COLUMNS" + suffix), per_meeting)
-    write_csv(os.path.join(args.out_dir, "sum_stats.csv"), getattr(sweep_eval, "SUM_COLUMNS" + suffix),
-              sweep_eval.calc_sum_stats(per_meeting, **kind))
+
+    def write(name, base_columns, rows):
+        write_csv(os.path.join(args.out_dir, name), sweep_eval.columns(base_columns, decoder), rows)
+    write("eval_df_per_meeting.csv", sweep_eval.EVAL_COLUMNS, per_meeting)
+    write("sum_stats.csv", sweep_eval.SUM_COLUMNS, sweep_eval.calc_sum_stats(per_meeting, **extra))
     if args.events:
         per_meeting_events = sweep_eval.event_rows(scores, events, channels, thresholds, min_lengths, index, **extra)
-        write_csv(os.path.join(args.out_dir, "event_df_per_meeting.csv"),
-                  getattr(sweep_eval, "EVENT_COLUMNS" + suffix), per_meeting_events)
-        write_csv(os.path.join(args.out_dir, "event_sum_stats.csv"), getattr(sweep_eval, "EVENT_SUM_COLUMNS" + suffix),
-                  sweep_eval.event_sum_stats(per_meeting_events, **kind))
+        write("event_df_per_meeting.csv", sweep_eval.EVENT_COLUMNS, per_meeting_events)
+        write("event_sum_stats.csv", sweep_eval.EVENT_SUM_COLUMNS, sweep_eval.event_sum_stats(per_meeting_events, **extra))
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

@@ -2,32 +2,34 @@
 
 Reference: laugh_segmenter.py:57-71 (fix_over_underflow), :19-24 (collapse / frame_span_to_time_span), :35-42
 (cut_laughter_segments), :74-111 (get_laughter_instances), :141-149 (format_outputs).  Same function names, arguments and result
-({(threshold, min_length): [(start_s, end_s), ...]}); the per-frame Python loop (87 passes over 360,000 frames in
-the evaluation sweeps, cluster_scripts/gen_eval_exp.py:30-36) is replaced by one vectorised run-length pass per
-threshold.  Integer run boundaries are bit-exact with the reference (tests/test_host_logic.py against vectors produced
-by the reference itself); this is host-side integer bookkeeping on a (T,) vector, not part of the GPU arithmetic.
-The Gillick-era MFCC code below laugh_segmenter.py:115 is dead in the reference and is not reproduced.
+({(threshold, min_length): [(start_s, end_s), ...]}); the per-frame Python loop (87 passes over 360,000 frames in the evaluation
+sweeps, cluster_scripts/gen_eval_exp.py:30-36) is replaced by one vectorised run-length pass per threshold.  Integer run boundaries
+are bit-exact with the reference (tests/test_host_logic.py against vectors produced by the reference itself).  The Gillick-era MFCC
+code below laugh_segmenter.py:115 is dead in the reference and is not reproduced.
 
-`get_laughter_instances_device` / `get_laughter_frame_spans_device` are the opt-in device form of the same sweep for a track that
-is already in GPU memory (csrc/runs.hip: the run tables of all thresholds, and of several channels, in four launches): only the
-compact tables cross to the host, and the dictionary is the host function's bit for bit.  They have no CPU fallback.
-
-`binarize_frame_spans` / `binarize_instances` add the two further controls of event-detection post-processing, which the reference
-does not have: hysteresis (an event starts above an onset threshold and lasts until the track falls to or below a lower offset
-threshold) and gap filling (events separated by a short pause become one, before the minimum-length filter).  The convention is
-written out in include/lad_hip.h (lad_binarize_count).  `binarize_frame_spans_device` / `binarize_instances_device` are their
-device forms (csrc/binarize.hip), with the same results and no CPU fallback.
-
-`viterbi_frame_spans` / `viterbi_instances` replace the frame-by-frame decision by two-state Viterbi decoding, which the reference
-does not have either: a frame contributes its log-odds relative to the threshold (an int32 look-up: `viterbi_emission_table`), every
-event costs a penalty, and the best-scoring set of events is returned.  The convention is written out in include/lad_hip.h
-(lad_viterbi_count).  `viterbi_frame_spans_device` / `viterbi_instances_device` are the device forms (csrc/viterbi.hip), with the same
-results and no CPU fallback.
+Three decoders turn the track into integer (first_frame, last_frame) spans, each described once by a `Decoder` record:
+    THRESHOLD    the reference's rule: frame i is laughter iff p[i] > threshold (csrc/runs.hip)
+    HYSTERESIS   an event starts above an onset threshold and lasts until the track falls to or below a lower offset threshold;
+                 events separated by a short pause become one, before the minimum-length filter (csrc/binarize.hip; the convention
+                 is written out above lad_binarize_count in include/lad_hip.h).  Not in the reference.
+    VITERBI      two-state Viterbi decoding: a frame contributes its log-odds relative to the threshold (an int32 look-up:
+                 `viterbi_emission_table`), every event costs a penalty, and the best-scoring set of events is returned
+                 (csrc/viterbi.hip; lad_viterbi_count in include/lad_hip.h).  Not in the reference.
+A record names its extra axes, validates its settings, holds its host form and the ctypes calls of its device form, and says how
+segment_laughter.py names its directories.  Everything else is written once over a record: `_instances` (the dictionaries),
+`_device_frame_spans` (rounds of at most the library's settings per call) and `_device_tables` (count, one read-back of the counts,
+fill; sweep_eval's scorers read the tables where they lie).  `decoder_for` picks the record from the optional axes.  The public
+functions -- get_laughter_* (THRESHOLD), binarize_* (HYSTERESIS), viterbi_* (VITERBI), each as `*_frame_spans` and `*_instances`,
+on the host and as `*_device` for a track in GPU memory -- are wrappers.  A device form returns what its host form returns, bit for
+bit; only the compact tables cross to the host; there is no CPU fallback.  torch and _hip are imported by the device forms only.
 """
 import math
 import ctypes
+from typing import Callable, NamedTuple
 
 import numpy as np
+
+_I32P, _F64P = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
 
 
 def frame_span_to_time_span(frame_span, fps=100.):
@@ -98,20 +100,6 @@ def run_spans(mask):
     return np.stack([starts, ends], axis=1).astype(np.int64)
 
 
-def get_laughter_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
-    """{(threshold, min_length): [(start_s, end_s), ...]} exactly as laugh_segmenter.py:74-111:
-    frame i is laughter iff p[i] > threshold; maximal runs -> (first/fps, last/fps); kept iff end - start > min_length."""
-    p = fix_probs(probs)
-    instance_dict = {}
-    for thr in thresholds:
-        spans = run_spans(p > thr)
-        inst_all = [(int(a) / fps, int(b) / fps) for a, b in spans]
-        for min_l in min_lengths:
-            instance_dict[(thr, min_l)] = [inst for inst in inst_all if inst[1] - inst[0] > min_l]
-    # the reference iterates thresholds-major, min_lengths-minor: restore that key order
-    return {(thr, min_l): instance_dict[(thr, min_l)] for thr in thresholds for min_l in min_lengths}
-
-
 def format_outputs(instances, wav_paths=None):
     """[{'start', 'end'}] (+ 'filename' when the instances were cut into wav files): laugh_segmenter.py:141-149, what
     segment_laughter.py:148 prints after writing `laugh_<i>.wav`."""
@@ -124,12 +112,39 @@ def format_outputs(instances, wav_paths=None):
     return outs
 
 
-def get_laughter_frame_spans(probs, threshold):
-    """Integer (first_frame, last_frame) runs for one threshold: the bit-exact core of get_laughter_instances."""
-    return run_spans(fix_probs(probs) > threshold)
+# ---- what the decoders share -----------------------------------------------------------------------------------------------------
+class Decoder(NamedTuple):
+    """One way from a probability track to spans.  `ctx` is the dictionary of what a call prepares once: "fps_host" (float64 numpy
+    (C,)), "table" (the emission table) and, through on_device, their copies in GPU memory."""
+    axes: tuple                 # names of the extra axes in key order: a key is (threshold, *axes, min_length)
+    what: str                   # the word in device_track's message
+    lib: str                    # the family's prefix in include/lad_hip.h
+    keys: Callable              # (thresholds, axis_values, ctx) -> ([(threshold, *axis values)], [setting]), thresholds-major; validates
+    host_spans: Callable        # (probs, settings, fps, ctx) -> [int64 (n, 2) per setting]
+    round_size: Callable        # (lib, n_settings) -> settings per device call
+    count: Callable             # (lib, track, chunk, ws, stream, ctx): lad_*_count of the settings `chunk`
+    fill: Callable              # (lib, track, chunk, ws, counts, total, stream, ctx) -> (the table the scorers read, its counts)
+    dir_suffix: Callable        # key -> the directories segment_laughter.py adds below t_<thr>/l_<min_len>
+    found_line: Callable        # (n, key) -> what segment_laughter.py prints per setting
 
 
-def _device_track(probs, what="sweep"):
+def _check_fps(fps):
+    fps = float(fps)
+    if not (math.isfinite(fps) and fps > 0):
+        raise ValueError(f"fps must be positive and finite, got {fps}")
+    return fps
+
+
+def fps_per_channel(fps, C, each=_check_fps):
+    """One fps or C of them -> float64 numpy (C,).  each=float leaves a value that is not positive and finite to whoever divides by
+    it (the library refuses it: LadHipError)."""
+    f = [fps] * C if np.ndim(fps) == 0 else list(fps)
+    if len(f) != C:
+        raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
+    return np.asarray([each(x) for x in f], dtype=np.float64)
+
+
+def device_track(probs, what="sweep"):
     """What every device form asks of its probability tensor: (T,) or (C, T), in GPU memory, contiguous, float32 or float64.
     Returns (the (C, T) tensor, its lad_runs_dtype, whether it was a (T,) one)."""
     import torch
@@ -146,87 +161,27 @@ def _device_track(probs, what="sweep"):
     return probs, 0 if probs.dtype == torch.float32 else 1, single
 
 
-def _device_tables(probs, dtype, settings, fps_host=None, binarize=False, extra_bytes=0):
-    """Count + fill of one family (include/lad_hip.h) on a (C, T) tensor that _device_track has passed, T >= 1: lad_runs_* for K
-    thresholds, or with binarize lad_binarize_* for K (onset, offset, min_gap), at most lad_binarize_max_settings() of them, with
-    fps_host a float64 numpy (C,).  Everything stays on the device: returns (workspace, table, counts, fps_dev) with `workspace` a
-    uint8 tensor whose first lad_*_workspace_bytes bytes are the family's workspace (the tables' counts at its start, where
-    lad_score_runs reads them) followed by extra_bytes for the caller, `table` the (total, 2) int32 tables back to back in
-    c * K + k order, counts their row counts, int32 numpy (C * K,), and fps_dev fps_host on the device (None without one)."""
+def on_device(ctx, name, device):
+    """ctx[name], a numpy array, in GPU memory: uploaded at its first use in a call, not once per round."""
     import torch
-
-    import _hip
-    lib = _hip.lib()
-    name = "lad_binarize" if binarize else "lad_runs"
-    C, T = probs.shape
-    K = len(settings)
-    cols = [(ctypes.c_double * K)(*[float(v) for v in col]) for col in (zip(*settings) if binarize else [settings])]
-    ws_bytes = getattr(lib, name + "_workspace_bytes")(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, name + "_workspace_bytes")
-    with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
-        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
-        fps_dev = None if fps_host is None else torch.from_numpy(fps_host).to(probs.device)
-        track = (_hip.ptr(probs), dtype, C, T)
-
-        def counts_now():
-            return np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
-        _hip.check(getattr(lib, name + "_count")(*track, *cols[:2], K, _hip.ptr(ws), stream), name + "_count")
-        counts = counts_now()
-        total = int(counts.sum(dtype=np.int64))
-        cptr = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        tables = torch.empty((2 if binarize else 1, max(total, 1), 2), dtype=torch.int32, device=probs.device)
-        if binarize:            # the hysteresis runs go to tables[0], the merged ones to tables[1] and their counts over the raw ones
-            _hip.check(lib.lad_binarize_fill(*track, *cols, K, _hip.ptr(fps_dev), fps_host.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                             _hip.ptr(ws), cptr, _hip.ptr(tables[0]), _hip.ptr(tables[1]), total, stream),
-                       "lad_binarize_fill")
-            counts = counts_now()
-        else:
-            _hip.check(lib.lad_runs_fill(*track, *cols, K, _hip.ptr(ws), cptr, _hip.ptr(tables[0]), total, stream), "lad_runs_fill")
-        return ws, tables[-1][:int(counts.sum(dtype=np.int64))], counts, fps_dev
+    if name + "_dev" not in ctx:
+        ctx[name + "_dev"] = torch.from_numpy(ctx[name]).to(device)
+    return ctx[name + "_dev"]
 
 
-def _device_run_tables(probs, thresholds):
-    """probs: (C, T) float32 / float64 GPU tensor, T >= 1.  Returns (counts (C, K) int64, table (total, 2) int32 numpy): the
-    (c, k) tables back to back in c * K + k order."""
-    probs, dtype, _ = _device_track(probs)
-    _, table, counts, _ = _device_tables(probs, dtype, list(thresholds))
-    return counts.astype(np.int64).reshape(len(probs), -1), table.cpu().numpy()
+def _doubles(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
 
 
-def _split_tables(counts, table):
-    """[[ (n, 2) int64 array per threshold ] per channel] from the back-to-back tables."""
-    edges = np.concatenate([[0], np.cumsum(counts.reshape(-1))])
-    C, K = counts.shape
-    return [[table[edges[c * K + k]:edges[c * K + k + 1]].astype(np.int64) for k in range(K)] for c in range(C)]
+def _read_counts(ws, n):
+    """The n int32 row counts at the start of a family's workspace (synchronises)."""
+    import torch
+    return np.ascontiguousarray(ws[:4 * n].view(torch.int32).cpu().numpy())
 
 
-def _device_frame_spans(probs, settings, fps=None, binarize=False):
-    """[int64 (n, 2) array per setting] for a (T,) tensor, one such list per channel for a (C, T) one: the tables of
-    _device_tables on the host.  The plain sweep is one call whatever the number of thresholds (the library refuses more than
-    lad_runs_max_thresholds()); settings go in rounds of at most lad_binarize_max_settings()."""
-    import _hip
-    probs, dtype, single = _device_track(probs)
-    C, T = probs.shape
-    fps_host = _fps_per_channel(fps, C) if binarize else None
-    if T == 0 or C == 0 or not settings:
-        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
-    else:
-        out = [[] for _ in range(C)]
-        step = int(_hip.lib().lad_binarize_max_settings()) if binarize else len(settings)
-        for k0 in range(0, len(settings), step):
-            _, table, counts, _ = _device_tables(probs, dtype, settings[k0:k0 + step], fps_host, binarize)
-            part = _split_tables(counts.astype(np.int64).reshape(C, -1), table.cpu().numpy())
-            for c in range(C):
-                out[c] += part[c]
-    return out[0] if single else out
-
-
-def get_laughter_frame_spans_device(probs, thresholds):
-    """Device form of get_laughter_frame_spans for a list of thresholds.  probs: (T,) GPU tensor (float32 / float64, contiguous) ->
-    [int64 (n, 2) array of (first_frame, last_frame) per threshold], each equal to get_laughter_frame_spans(probs.cpu(), thr);
-    (C, T) -> one such list per channel, from the same four launches."""
-    return _device_frame_spans(probs, list(thresholds))
+def _table(total, device, n=None):
+    import torch
+    return torch.empty((max(total, 1), 2) if n is None else (n, max(total, 1), 2), dtype=torch.int32, device=device)
 
 
 def _instances_from_spans(keys, spans_list, min_lengths, fps):
@@ -242,17 +197,36 @@ def _instances_from_spans(keys, spans_list, min_lengths, fps):
     return instance_dict
 
 
-def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
-    """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats).
-    The run tables come from the device; the seconds and the min_length filter are evaluated on them on the host."""
+# ---- THRESHOLD: the reference's frame-by-frame rule (include/lad_hip.h: lad_runs_count) ------------------------------------------
+def _runs_spans_host(probs, settings, fps, ctx):
+    p = fix_probs(probs)
+    return [run_spans(p > thr) for thr in settings]
+
+
+def _runs_count(lib, track, chunk, ws, stream, ctx):
     import _hip
-    if getattr(probs, "ndim", None) != 1:
-        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
-    thresholds = list(thresholds)
-    return _instances_from_spans([(thr,) for thr in thresholds], get_laughter_frame_spans_device(probs, thresholds), min_lengths, fps)
+    _hip.check(lib.lad_runs_count(*track, _doubles(chunk), len(chunk), _hip.ptr(ws), stream), "lad_runs_count")
 
 
-# ---- hysteresis and gap filling (include/lad_hip.h: lad_binarize_count has the convention) ----------------------------------------
+def _runs_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+    import _hip
+    table = _table(total, ws.device)
+    _hip.check(lib.lad_runs_fill(*track, _doubles(chunk), len(chunk), _hip.ptr(ws), counts.ctypes.data_as(_I32P), _hip.ptr(table), total,
+                                 stream), "lad_runs_fill")
+    return table[:total], counts
+
+
+THRESHOLD = Decoder(
+    axes=(), what="sweep", lib="lad_runs",
+    keys=lambda thresholds, axis_values, ctx: ([(thr,) for thr in thresholds], thresholds),
+    host_spans=_runs_spans_host,
+    round_size=lambda lib, n: n,        # one round whatever n is: the library refuses more than lad_runs_max_thresholds()
+    count=_runs_count, fill=_runs_fill,
+    dir_suffix=lambda key: (),
+    found_line=lambda n, key: f"Found {n} laughs for threshold {key[0]} and min_length {key[1]}.")
+
+
+# ---- HYSTERESIS: hysteresis and gap filling (include/lad_hip.h: lad_binarize_count has the convention) ---------------------------
 def _check_setting(onset, offset, min_gap):
     onset, offset, min_gap = float(onset), float(offset), float(min_gap)
     if not (math.isfinite(onset) and math.isfinite(offset) and math.isfinite(min_gap)):
@@ -262,13 +236,6 @@ def _check_setting(onset, offset, min_gap):
     if min_gap < 0:
         raise ValueError(f"min_gap must be >= 0, got {min_gap}")
     return onset, offset, min_gap
-
-
-def _check_fps(fps):
-    fps = float(fps)
-    if not (math.isfinite(fps) and fps > 0):
-        raise ValueError(f"fps must be positive and finite, got {fps}")
-    return fps
 
 
 def _hysteresis_spans(p, onset, offset):
@@ -293,15 +260,8 @@ def _fill_gaps(spans, min_gap, fps):
     return np.stack([spans[head, 0], spans[tail, 1]], axis=1)
 
 
-def binarize_frame_spans(probs, onset, offset, min_gap=0.0, fps=100.):
-    """Integer (first_frame, last_frame) events of one setting: hysteresis between `onset` and `offset` (offset <= onset), then
-    gap filling by `min_gap` seconds at `fps` frames per second.  int64 (n, 2).  offset == onset and min_gap == 0 is
-    get_laughter_frame_spans(probs, onset)."""
-    onset, offset, min_gap = _check_setting(onset, offset, min_gap)
-    return _fill_gaps(_hysteresis_spans(fix_probs(probs), onset, offset), min_gap, np.float64(_check_fps(fps)))
-
-
-def _binarize_keys(thresholds, offset_drops, min_gaps):
+def _binarize_keys(thresholds, axis_values, ctx):
+    offset_drops, min_gaps = axis_values
     for drop in offset_drops:
         if not (math.isfinite(float(drop)) and float(drop) >= 0):
             raise ValueError(f"an offset drop must be finite and >= 0, got {drop}")
@@ -310,14 +270,7 @@ def _binarize_keys(thresholds, offset_drops, min_gaps):
     return triples, settings
 
 
-def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
-    """{(threshold, offset_drop, min_gap, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then drop, then gap, then
-    min_length.  The onset is the threshold and the offset is threshold - offset_drop (drop >= 0); events are (first / fps,
-    last / fps) and kept iff end - start > min_length, after gap filling.  drop = 0 and gap = 0 give the lists of
-    get_laughter_instances."""
-    thresholds, min_lengths, offset_drops, min_gaps = list(thresholds), list(min_lengths), list(offset_drops), list(min_gaps)
-    triples, settings = _binarize_keys(thresholds, offset_drops, min_gaps)
-    fps = np.float64(_check_fps(fps))
+def _binarize_spans_host(probs, settings, fps, ctx):
     p = fix_probs(probs)
     held = {}
     spans_list = []
@@ -325,38 +278,35 @@ def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., off
         if (onset, offset) not in held:
             held[(onset, offset)] = _hysteresis_spans(p, onset, offset)
         spans_list.append(_fill_gaps(held[(onset, offset)], gap, fps))
-    return _instances_from_spans(triples, spans_list, min_lengths, fps)
+    return spans_list
 
 
-def _fps_per_channel(fps, C, each=_check_fps):
-    """One fps or C of them -> float64 numpy (C,).  each=float leaves a value that is not positive and finite to whoever divides by
-    it (the library refuses it: LadHipError)."""
-    f = [fps] * C if np.ndim(fps) == 0 else list(fps)
-    if len(f) != C:
-        raise ValueError(f"fps: one value or one per channel ({C}), got {len(f)}")
-    return np.asarray([each(x) for x in f], dtype=np.float64)
-
-
-def binarize_frame_spans_device(probs, settings, fps=100.):
-    """Device form of binarize_frame_spans for a list of settings (onset, offset, min_gap).  probs: (T,) GPU tensor (float32 /
-    float64, contiguous) -> [int64 (n, 2) array per setting], each equal to binarize_frame_spans(probs.cpu(), *setting, fps);
-    (C, T) -> one such list per channel, fps a float or one per channel.  More settings than lad_binarize_max_settings() are
-    split into several calls.  No CPU fallback."""
-    return _device_frame_spans(probs, [_check_setting(*s) for s in settings], fps, binarize=True)
-
-
-def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
-    """binarize_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
+def _binarize_count(lib, track, chunk, ws, stream, ctx):
     import _hip
-    if getattr(probs, "ndim", None) != 1:
-        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device sweep has no CPU fallback)")
-    thresholds, min_lengths, offset_drops, min_gaps = list(thresholds), list(min_lengths), list(offset_drops), list(min_gaps)
-    triples, settings = _binarize_keys(thresholds, offset_drops, min_gaps)
-    fps = np.float64(_check_fps(fps))
-    return _instances_from_spans(triples, binarize_frame_spans_device(probs, settings, fps), min_lengths, fps)
+    onset, offset, _ = zip(*chunk)
+    _hip.check(lib.lad_binarize_count(*track, _doubles(onset), _doubles(offset), len(chunk), _hip.ptr(ws), stream), "lad_binarize_count")
 
 
-# ---- two-state Viterbi decoding (include/lad_hip.h: lad_viterbi_count has the convention) -----------------------------------------
+def _binarize_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+    import _hip
+    tables = _table(total, ws.device, 2)    # the hysteresis runs go to tables[0], the merged ones to tables[1] and their counts over the raw ones
+    _hip.check(lib.lad_binarize_fill(*track, *[_doubles(col) for col in zip(*chunk)], len(chunk), _hip.ptr(on_device(ctx, "fps_host", ws.device)),
+                                     ctx["fps_host"].ctypes.data_as(_F64P), _hip.ptr(ws), counts.ctypes.data_as(_I32P), _hip.ptr(tables[0]),
+                                     _hip.ptr(tables[1]), total, stream), "lad_binarize_fill")
+    counts = _read_counts(ws, len(counts))
+    return tables[1][:int(counts.sum(dtype=np.int64))], counts
+
+
+HYSTERESIS = Decoder(
+    axes=("offset_drop", "min_gap"), what="sweep", lib="lad_binarize",
+    keys=_binarize_keys, host_spans=_binarize_spans_host,
+    round_size=lambda lib, n: int(lib.lad_binarize_max_settings()),
+    count=_binarize_count, fill=_binarize_fill,
+    dir_suffix=lambda key: (f"d_{key[1]}_g_{key[2]}",),
+    found_line=lambda n, key: f"Found {n} laughs for threshold {key[0]}, offset drop {key[1]}, min_gap {key[2]} and min_length {key[3]}.")
+
+
+# ---- VITERBI: two-state Viterbi decoding (include/lad_hip.h: lad_viterbi_count has the convention) -------------------------------
 VITERBI_BUCKETS = 65536        # a frame's bucket is floor(v * 65536): 0..65536, lad_viterbi_table_entries() = 65537 table values
 VITERBI_NAN_SCORE = -2 ** 31
 _VITERBI_MAX_EMISSION, _VITERBI_MAX_PENALTY = 2 ** 24, 2 ** 26
@@ -402,6 +352,13 @@ def _check_viterbi_settings(settings):
     return settings
 
 
+def _viterbi_keys(thresholds, axis_values, ctx):
+    """Also settles ctx["table"]: the table given, checked, or the default one."""
+    table = ctx["table"] = _viterbi_table(ctx.get("table"))
+    penalties, = axis_values
+    return [(thr, pen) for thr in thresholds for pen in penalties], viterbi_settings(thresholds, penalties, table)
+
+
 def _viterbi_spans_host(probs, settings, table):
     """[int64 (n, 2) array per setting (bias, penalty)]: the header's recursion as a loop over frames, vectorised over the settings."""
     p = fix_probs(probs)
@@ -430,6 +387,168 @@ def _viterbi_spans_host(probs, settings, table):
     return [run_spans(on[:, k]) for k in range(K)]
 
 
+def _viterbi_count(lib, track, chunk, ws, stream, ctx):
+    import _hip
+    bias, penalty = ((ctypes.c_int32 * len(chunk))(*col) for col in zip(*chunk))
+    _hip.check(lib.lad_viterbi_count(*track, _hip.ptr(on_device(ctx, "table", ws.device)), ctx["table"].ctypes.data_as(_I32P), bias, penalty,
+                                     len(chunk), _hip.ptr(ws), _hip.ptr(ctx.get("best")), stream), "lad_viterbi_count")
+
+
+def _viterbi_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+    import _hip
+    runs = _table(total, ws.device)
+    _hip.check(lib.lad_viterbi_fill(_hip.ptr(ws), counts.ctypes.data_as(_I32P), *track[2:], len(chunk), _hip.ptr(runs), total, stream),
+               "lad_viterbi_fill")
+    return runs[:total], counts
+
+
+VITERBI = Decoder(
+    axes=("penalty",), what="decoder", lib="lad_viterbi",
+    keys=_viterbi_keys, host_spans=lambda probs, settings, fps, ctx: _viterbi_spans_host(probs, settings, ctx["table"]),
+    round_size=lambda lib, n: int(lib.lad_viterbi_max_settings()),
+    count=_viterbi_count, fill=_viterbi_fill,
+    dir_suffix=lambda key: (f"p_{key[1]}",),
+    found_line=lambda n, key: f"Found {n} laughs for threshold {key[0]}, penalty {key[1]} and min_length {key[2]}.")
+
+
+# ---- written once over a record --------------------------------------------------------------------------------------------------
+def decoder_for(offset_drops=None, min_gaps=None, penalties=None):
+    """(decoder, the values of its axes as lists) from the optional axes of the public functions and the command lines: penalties ->
+    VITERBI; offset_drops or min_gaps -> HYSTERESIS (one given: the other is [0.0], which changes nothing); none -> THRESHOLD.  The
+    Viterbi decoder has neither an offset nor a gap rule: both kinds together are refused."""
+    if penalties is not None:
+        if offset_drops is not None or min_gaps is not None:
+            raise ValueError("penalties (the Viterbi decoder) cannot be combined with offset_drops or min_gaps")
+        return VITERBI, (list(penalties),)
+    if offset_drops is None and min_gaps is None:
+        return THRESHOLD, ()
+    return HYSTERESIS, (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
+
+
+def _device_tables(decoder, probs, dtype, chunk, ctx, extra_bytes=0, want_best=False):
+    """Count + fill of one round (include/lad_hip.h) on a (C, T) tensor that device_track has passed, T >= 1, for the settings
+    `chunk`, at most decoder.round_size of them.  Everything stays on the device: returns (workspace, table, counts, best) with
+    `workspace` a uint8 tensor whose first lad_*_workspace_bytes bytes are the family's workspace (the tables' counts at its start,
+    where the scorers read them) followed by extra_bytes for the caller, `table` the (total, 2) int32 tables back to back in
+    c * K + k order, counts their row counts, int32 numpy (C * K,), and best the int64 (C * K,) path scores of the Viterbi decoder
+    on the device (None unless asked for).  The counts cross to the host once, after the count (HYSTERESIS: and after its fill)."""
+    import torch
+
+    import _hip
+    lib = _hip.lib()
+    C, T = probs.shape
+    K = len(chunk)
+    ws_bytes = getattr(lib, decoder.lib + "_workspace_bytes")(C, T, K)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, decoder.lib + "_workspace_bytes")
+    with torch.cuda.device(probs.device):
+        stream = _hip.stream_handle(probs.device)
+        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
+        ctx["best"] = best = torch.empty(C * K, dtype=torch.int64, device=probs.device) if want_best else None
+        track = (_hip.ptr(probs), dtype, C, T)
+        decoder.count(lib, track, chunk, ws, stream, ctx)
+        counts = _read_counts(ws, C * K)
+        table, counts = decoder.fill(lib, track, chunk, ws, counts, int(counts.sum(dtype=np.int64)), stream, ctx)
+        return ws, table, counts, best
+
+
+def _device_run_tables(probs, thresholds):
+    """(counts (C, K) int64, table (total, 2) int32 numpy) of one THRESHOLD round on a (C, T) tensor: kept for tests/test_runs_gpu.py."""
+    probs, dtype, _ = device_track(probs)
+    _, table, counts, _ = _device_tables(THRESHOLD, probs, dtype, list(thresholds), {})
+    return counts.astype(np.int64).reshape(len(probs), -1), table.cpu().numpy()
+
+
+def _device_frame_spans(decoder, probs, settings, ctx):
+    """[int64 (n, 2) array per setting] for a (T,) tensor, one such list per channel for a (C, T) one: the tables of
+    _device_tables on the host, in rounds of at most decoder.round_size settings.  ctx["fps"], if there: one value or one per
+    channel."""
+    import _hip
+    probs, dtype, single = device_track(probs, decoder.what)
+    C, T = probs.shape
+    if "fps" in ctx:
+        ctx["fps_host"] = fps_per_channel(ctx["fps"], C)
+    if T == 0 or C == 0 or not settings:
+        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
+    else:
+        out = [[] for _ in range(C)]
+        step = decoder.round_size(_hip.lib(), len(settings))
+        for k0 in range(0, len(settings), step):
+            _, table, counts, _ = _device_tables(decoder, probs, dtype, settings[k0:k0 + step], ctx)
+            rows, edges = table.cpu().numpy(), np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+            for i in range(len(counts)):                # the tables lie back to back in c * K + k order
+                out[i // (len(counts) // C)].append(rows[edges[i]:edges[i + 1]].astype(np.int64))
+    return out[0] if single else out
+
+
+def _instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device, table=None):
+    """{(threshold, *axis values, min_length): [(start_s, end_s), ...]}, thresholds-major, then the axes in their order, then
+    min_length: the decoder's spans as (first / fps, last / fps), kept iff end - start > min_length.  device: probs is a (T,) track
+    in GPU memory and the spans come from there; the seconds and the filter are evaluated on the host either way."""
+    if device and getattr(probs, "ndim", None) != 1:
+        import _hip
+        raise _hip.LadHipError(f"probs must be a (T,) GPU tensor (the device {decoder.what} has no CPU fallback)")
+    ctx = {"table": table}
+    keys, settings = decoder.keys(list(thresholds), [list(values) for values in axis_values], ctx)
+    min_lengths = list(min_lengths)
+    if decoder is not THRESHOLD:            # (the reference's own sweep takes fps as it comes)
+        fps = ctx["fps"] = np.float64(_check_fps(fps))
+    spans = _device_frame_spans(decoder, probs, settings, ctx) if device else decoder.host_spans(probs, settings, fps, ctx)
+    return _instances_from_spans(keys, spans, min_lengths, fps)
+
+
+# ---- the public forms ------------------------------------------------------------------------------------------------------------
+def get_laughter_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+    """{(threshold, min_length): [(start_s, end_s), ...]} exactly as laugh_segmenter.py:74-111: frame i is laughter iff
+    p[i] > threshold; maximal runs -> (first/fps, last/fps); kept iff end - start > min_length.  Keys thresholds-major, as the
+    reference iterates."""
+    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=False)
+
+
+def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+    """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats)."""
+    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=True)
+
+
+def get_laughter_frame_spans(probs, threshold):
+    """Integer (first_frame, last_frame) runs for one threshold: the bit-exact core of get_laughter_instances."""
+    return THRESHOLD.host_spans(probs, [threshold], None, {})[0]
+
+
+def get_laughter_frame_spans_device(probs, thresholds):
+    """Device form of get_laughter_frame_spans for a list of thresholds.  probs: (T,) GPU tensor (float32 / float64, contiguous) ->
+    [int64 (n, 2) array of (first_frame, last_frame) per threshold], each equal to get_laughter_frame_spans(probs.cpu(), thr);
+    (C, T) -> one such list per channel, from the same four launches."""
+    return _device_frame_spans(THRESHOLD, probs, list(thresholds), {})
+
+
+def binarize_frame_spans(probs, onset, offset, min_gap=0.0, fps=100.):
+    """Integer (first_frame, last_frame) events of one setting: hysteresis between `onset` and `offset` (offset <= onset), then
+    gap filling by `min_gap` seconds at `fps` frames per second.  int64 (n, 2).  offset == onset and min_gap == 0 is
+    get_laughter_frame_spans(probs, onset)."""
+    return HYSTERESIS.host_spans(probs, [_check_setting(onset, offset, min_gap)], np.float64(_check_fps(fps)), {})[0]
+
+
+def binarize_frame_spans_device(probs, settings, fps=100.):
+    """Device form of binarize_frame_spans for a list of settings (onset, offset, min_gap).  probs: (T,) GPU tensor (float32 /
+    float64, contiguous) -> [int64 (n, 2) array per setting], each equal to binarize_frame_spans(probs.cpu(), *setting, fps);
+    (C, T) -> one such list per channel, fps a float or one per channel.  More settings than lad_binarize_max_settings() are
+    split into several calls.  No CPU fallback."""
+    return _device_frame_spans(HYSTERESIS, probs, [_check_setting(*s) for s in settings], {"fps": fps})
+
+
+def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+    """{(threshold, offset_drop, min_gap, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then drop, then gap, then
+    min_length.  The onset is the threshold and the offset is threshold - offset_drop (drop >= 0); events are (first / fps,
+    last / fps) and kept iff end - start > min_length, after gap filling.  drop = 0 and gap = 0 give the lists of
+    get_laughter_instances."""
+    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=False)
+
+
+def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+    """binarize_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
+    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=True)
+
+
 def viterbi_frame_spans(probs, threshold, penalty, table=None, unit=1024):
     """Integer (first_frame, last_frame) runs of the best on/off path for one setting: log-odds relative to `threshold`, `penalty`
     nats per event (viterbi_settings).  int64 (n, 2).  This is the parity form of csrc/viterbi.hip -- a Python loop over the frames
@@ -438,82 +557,21 @@ def viterbi_frame_spans(probs, threshold, penalty, table=None, unit=1024):
     return _viterbi_spans_host(probs, viterbi_settings([threshold], [penalty], table, unit), table)[0]
 
 
-def _viterbi_keys(thresholds, penalties, table, unit=1024):
-    return [(thr, pen) for thr in thresholds for pen in penalties], viterbi_settings(thresholds, penalties, table, unit)
+def viterbi_frame_spans_device(probs, settings, table=None):
+    """Device form of the decoder for a list of settings (bias, penalty) as viterbi_settings returns them.  probs: (T,) GPU tensor
+    (float32 / float64, contiguous) -> [int64 (n, 2) array per setting]; (C, T) -> one such list per channel.  More settings than
+    lad_viterbi_max_settings() go in several rounds.  No CPU fallback."""
+    device_track(probs, VITERBI.what)       # (refused before the table and the settings are looked at)
+    ctx = {"table": _viterbi_table(table)}
+    return _device_frame_spans(VITERBI, probs, _check_viterbi_settings(settings), ctx)
 
 
 def viterbi_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
     """{(threshold, penalty, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then penalty, then min_length: the runs of
     the decoded path as (first / fps, last / fps), kept iff end - start > min_length.  Host form (see viterbi_frame_spans)."""
-    thresholds, min_lengths, penalties = list(thresholds), list(min_lengths), list(penalties)
-    table = _viterbi_table(table)
-    keys, settings = _viterbi_keys(thresholds, penalties, table)
-    return _instances_from_spans(keys, _viterbi_spans_host(probs, settings, table), min_lengths, np.float64(_check_fps(fps)))
-
-
-def _device_viterbi_tables(probs, dtype, settings, table_host, table_dev=None, extra_bytes=0, want_best=False):
-    """lad_viterbi_count + lad_viterbi_fill (include/lad_hip.h) on a (C, T) tensor that _device_track has passed, T >= 1, for at most
-    lad_viterbi_max_settings() settings (bias, penalty): the sibling of _device_tables, with the same (workspace, table, counts)
-    in front -- the counts at the start of the workspace, where the scorers read them, extra_bytes behind it for the caller -- and
-    `best`, the int64 (C * K,) scores on the device (None unless asked for)."""
-    import torch
-
-    import _hip
-    lib = _hip.lib()
-    C, T = probs.shape
-    K = len(settings)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    bias = (ctypes.c_int32 * K)(*[s[0] for s in settings])
-    penalty = (ctypes.c_int32 * K)(*[s[1] for s in settings])
-    ws_bytes = lib.lad_viterbi_workspace_bytes(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_viterbi_workspace_bytes")
-    with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
-        if table_dev is None:
-            table_dev = torch.from_numpy(table_host).to(probs.device)
-        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
-        best = torch.empty(C * K, dtype=torch.int64, device=probs.device) if want_best else None
-        _hip.check(lib.lad_viterbi_count(_hip.ptr(probs), dtype, C, T, _hip.ptr(table_dev), table_host.ctypes.data_as(i32p), bias, penalty,
-                                         K, _hip.ptr(ws), _hip.ptr(best), stream), "lad_viterbi_count")
-        counts = np.ascontiguousarray(ws[:4 * C * K].view(torch.int32).cpu().numpy())     # (synchronises)
-        total = int(counts.sum(dtype=np.int64))
-        runs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=probs.device)
-        _hip.check(lib.lad_viterbi_fill(_hip.ptr(ws), counts.ctypes.data_as(i32p), C, T, K, _hip.ptr(runs), total, stream),
-                   "lad_viterbi_fill")
-        return ws, runs[:total], counts, best
-
-
-def viterbi_frame_spans_device(probs, settings, table=None):
-    """Device form of the decoder for a list of settings (bias, penalty) as viterbi_settings returns them.  probs: (T,) GPU tensor
-    (float32 / float64, contiguous) -> [int64 (n, 2) array per setting]; (C, T) -> one such list per channel.  More settings than
-    lad_viterbi_max_settings() go in several rounds.  No CPU fallback."""
-    import torch
-
-    import _hip
-    probs, dtype, single = _device_track(probs, "decoder")
-    table = _viterbi_table(table)
-    settings = _check_viterbi_settings(settings)
-    C, T = probs.shape
-    if T == 0 or C == 0 or not settings:
-        out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
-    else:
-        out = [[] for _ in range(C)]
-        step = int(_hip.lib().lad_viterbi_max_settings())
-        table_dev = torch.from_numpy(table).to(probs.device)
-        for k0 in range(0, len(settings), step):
-            _, runs, counts, _ = _device_viterbi_tables(probs, dtype, settings[k0:k0 + step], table, table_dev)
-            part = _split_tables(counts.astype(np.int64).reshape(C, -1), runs.cpu().numpy())
-            for c in range(C):
-                out[c] += part[c]
-    return out[0] if single else out
+    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=False, table=table)
 
 
 def viterbi_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
     """viterbi_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
-    import _hip
-    if getattr(probs, "ndim", None) != 1:
-        raise _hip.LadHipError("probs must be a (T,) GPU tensor (the device decoder has no CPU fallback)")
-    thresholds, min_lengths, penalties = list(thresholds), list(min_lengths), list(penalties)
-    table = _viterbi_table(table)
-    keys, settings = _viterbi_keys(thresholds, penalties, table)
-    return _instances_from_spans(keys, viterbi_frame_spans_device(probs, settings, table), min_lengths, np.float64(_check_fps(fps)))
+    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=True, table=table)

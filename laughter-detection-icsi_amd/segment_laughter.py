@@ -48,6 +48,7 @@ import torch  # noqa: E402
 
 import audio_utils  # noqa: E402
 import config as config_mod  # noqa: E402
+from evaluate_sweep import cutoff_arg, float_list  # noqa: E402  (the argparse types of --lowpass and of the decoders' lists)
 import laugh_segmenter  # noqa: E402
 import load_data  # noqa: E402
 import parallel  # noqa: E402
@@ -141,39 +142,17 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     if lowpass is not None and (segmenter == "host" or rank == 0):
         probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
             laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
-    binarize = offset_drops is not None or min_gaps is not None
-    viterbi = penalties is not None
-    if viterbi and binarize:
-        raise ValueError("penalties (the Viterbi decoder) cannot be combined with offset_drops or min_gaps")
-    if viterbi:
-        extra = dict(penalties=list(penalties))
-        sweep = laugh_segmenter.viterbi_instances if segmenter == "host" else laugh_segmenter.viterbi_instances_device
-    elif binarize:
-        extra = dict(offset_drops=list(offset_drops) if offset_drops is not None else [0.0],
-                     min_gaps=list(min_gaps) if min_gaps is not None else [0.0])
-        sweep = laugh_segmenter.binarize_instances if segmenter == "host" else laugh_segmenter.binarize_instances_device
-    else:
-        extra = {}
-        sweep = laugh_segmenter.get_laughter_instances if segmenter == "host" else laugh_segmenter.get_laughter_instances_device
+    decoder, axis_values = laugh_segmenter.decoder_for(offset_drops, min_gaps, penalties)
     if segmenter == "host" or rank == 0:
-        instance_dict = sweep(probs, thresholds=thresholds, min_lengths=min_lengths, fps=fps, **extra)
+        instance_dict = laugh_segmenter._instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device=segmenter == "device")
     else:
         instance_dict = {}
     sweep_time = time.time() - start_time - predict_time
     if rank == 0:
         for setting, instances in instance_dict.items():
-            if verbose and binarize:
-                print(f"Found {len(instances)} laughs for threshold {setting[0]}, offset drop {setting[1]}, min_gap {setting[2]} and "
-                      f"min_length {setting[3]}.")
-            elif verbose and viterbi:
-                print(f"Found {len(instances)} laughs for threshold {setting[0]}, penalty {setting[1]} and min_length {setting[2]}.")
-            elif verbose:
-                print(f"Found {len(instances)} laughs for threshold {setting[0]} and min_length {setting[1]}.")
-            out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[-1]}')
-            if binarize:
-                out_dir = os.path.join(out_dir, f'd_{setting[1]}_g_{setting[2]}')
-            if viterbi:
-                out_dir = os.path.join(out_dir, f'p_{setting[1]}')
+            if verbose:
+                print(decoder.found_line(len(instances), setting))
+            out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[-1]}', *decoder.dir_suffix(setting))
             if save_to_textgrid or (save_to_audio_files and len(instances) > 0):
                 os.makedirs(out_dir, exist_ok=True)
             if save_to_audio_files and len(instances) > 0:
@@ -189,22 +168,6 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
               f'{precision}: read + featurise + {len(probs)} windows {predict_time:.3f}s, '
               f'{len(instance_dict)}-setting sweep {sweep_time:.3f}s, output {time_taken - predict_time - sweep_time:.3f}s)')
     return time_taken, instance_dict
-
-
-def cutoff_arg(text):
-    """--lowpass: a cutoff of Nyquist strictly between 0 and 1 (scipy.signal.butter's range)."""
-    value = float(text)
-    if not 0.0 < value < 1.0:
-        raise argparse.ArgumentTypeError(f"the cutoff must lie strictly between 0 and 1 (of Nyquist), got {text}")
-    return value
-
-
-def float_list(text):
-    """--offset_drops / --min_gaps: a comma-separated list of non-negative numbers."""
-    values = [float(t) for t in text.split(',')]
-    if not all(np.isfinite(v) and v >= 0 for v in values):
-        raise argparse.ArgumentTypeError(f"finite values >= 0, got {text}")
-    return values
 
 
 def build_parser():

@@ -11,9 +11,10 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
     score_sweep_host       the host sweep + score_instances for several tracks -> int64 (C, K, L, 7)
     score_sweep_device     the same array for tracks in GPU memory (csrc/runs.hip + csrc/score.hip): besides the C x K run counts
                            only the scores cross to the host.  No CPU fallback.
-                           Both take offset_drops= / min_gaps= (hysteresis and gap filling: laugh_segmenter.binarize_instances,
-                           csrc/binarize.hip) and then return (C, K, D, G, L, 7), or penalties= (the two-state Viterbi decoder:
-                           laugh_segmenter.viterbi_instances, csrc/viterbi.hip) and then return (C, K, P, L, 7).
+                           Both take offset_drops= / min_gaps= (laugh_segmenter.HYSTERESIS) and then return (C, K, D, G, L, 7),
+                           or penalties= (laugh_segmenter.VITERBI) and then return (C, K, P, L, 7): the family comes from
+                           laugh_segmenter.decoder_for, once per call, and its Decoder record supplies the axes (columns, array
+                           shape, key tuples), the settings and the device tables.
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
     event_scores_instances host event scorer of one channel's dictionary -> {key: 7 ints} (include/lad_hip.h: lad_score_events has
@@ -30,27 +31,32 @@ import operator
 
 import numpy as np
 
+import laugh_segmenter as ls
+
 CLASSES = ("invalid", "laugh", "speech", "noise", "silence")          # include/lad_hip.h: enum lad_score_class
 FIELDS = ("n_pred", "n_valid", "pred_ms", "corr_ms", "fp_speech_ms", "fp_noise_ms", "fp_silence_ms")   # enum lad_score_field
 EVAL_COLUMNS = ["meeting", "threshold", "min_len", "precision", "recall", "corr_pred_time", "tot_pred_time", "tot_transc_laugh_time",
                 "num_of_pred_laughs", "valid_pred_laughs", "num_of_transc_laughs", "tot_fp_speech_time", "tot_fp_noise_time",
                 "tot_fp_silence_time"]                                # analyse.py:255-257
 SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.py:290
-# with the hysteresis / gap-filling axes (not in the reference): offset_drop and min_gap follow min_len
-EVAL_COLUMNS_BINARIZE = EVAL_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVAL_COLUMNS[3:]
-SUM_COLUMNS_BINARIZE = SUM_COLUMNS[:2] + ["offset_drop", "min_gap"] + SUM_COLUMNS[2:]
 EVENT_FIELDS = ("n_ref", "ref_touched", "ref_hit", "pred_hit", "links", "onset_abs_ms", "offset_abs_ms")      # enum lad_event_field
 EVENT_COLUMNS = ["meeting", "threshold", "min_len", "event_precision", "event_recall", "event_f1", "num_ref_events",
                  "ref_events_touched", "ref_events_hit", "valid_pred_laughs", "pred_laughs_hit", "links",
                  "fragments_per_touched_event", "mean_onset_err", "mean_offset_err"]
-EVENT_COLUMNS_BINARIZE = EVENT_COLUMNS[:3] + ["offset_drop", "min_gap"] + EVENT_COLUMNS[3:]
 EVENT_SUM_COLUMNS = EVENT_COLUMNS[1:]
-EVENT_SUM_COLUMNS_BINARIZE = EVENT_COLUMNS_BINARIZE[1:]
-# with the Viterbi decoder's axis (not in the reference): penalty follows min_len
-EVAL_COLUMNS_VITERBI = EVAL_COLUMNS[:3] + ["penalty"] + EVAL_COLUMNS[3:]
-SUM_COLUMNS_VITERBI = SUM_COLUMNS[:2] + ["penalty"] + SUM_COLUMNS[2:]
-EVENT_COLUMNS_VITERBI = EVENT_COLUMNS[:3] + ["penalty"] + EVENT_COLUMNS[3:]
-EVENT_SUM_COLUMNS_VITERBI = EVENT_COLUMNS_VITERBI[1:]
+
+
+def columns(base, decoder):
+    """One of EVAL_COLUMNS, SUM_COLUMNS, EVENT_COLUMNS, EVENT_SUM_COLUMNS for a laugh_segmenter.Decoder: its extra axes (not in the
+    reference) follow min_len."""
+    at = base.index("min_len") + 1
+    return base[:at] + list(decoder.axes) + base[at:]
+
+
+EVAL_COLUMNS_BINARIZE, EVAL_COLUMNS_VITERBI = columns(EVAL_COLUMNS, ls.HYSTERESIS), columns(EVAL_COLUMNS, ls.VITERBI)
+SUM_COLUMNS_BINARIZE, SUM_COLUMNS_VITERBI = columns(SUM_COLUMNS, ls.HYSTERESIS), columns(SUM_COLUMNS, ls.VITERBI)
+EVENT_COLUMNS_BINARIZE, EVENT_COLUMNS_VITERBI = columns(EVENT_COLUMNS, ls.HYSTERESIS), columns(EVENT_COLUMNS, ls.VITERBI)
+EVENT_SUM_COLUMNS_BINARIZE, EVENT_SUM_COLUMNS_VITERBI = columns(EVENT_SUM_COLUMNS, ls.HYSTERESIS), columns(EVENT_SUM_COLUMNS, ls.VITERBI)
 ROW_COLUMNS = ("meeting_id", "part_id", "chan", "start", "end", "length", "type", "laugh_type")
 CHANNEL_COLUMNS = ("meeting_id", "part_id", "chan", "length")
 FACTOR = 1000.0                # utils.py:14: 1000 / frame_duration, frame_duration = 1 ms (config.py:46-52)
@@ -329,56 +335,36 @@ def event_scores_instances(instances, index, meeting_id, chan, min_overlap_ms=1,
     return out
 
 
-def _extra_axes(offset_drops, min_gaps, penalties=None):
-    """None, or the extra axes as lists: the two of hysteresis and gap filling (one given: the other is [0.0], which changes
-    nothing), or the one of the Viterbi decoder.  The decoder has neither an offset nor a gap rule: both kinds together are refused."""
-    if penalties is not None:
-        if offset_drops is not None or min_gaps is not None:
-            raise ValueError("penalties (the Viterbi decoder) cannot be combined with offset_drops or min_gaps")
-        return (list(penalties),)
-    if offset_drops is None and min_gaps is None:
-        return None
-    return (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
-
-
 def _cells(thresholds, min_lengths, axes):
-    """[(index into a score array behind the channel, threshold, min_length, (), (offset_drop, min_gap) or (penalty,))],
-    thresholds-major, then the extra axes in their order, then min_length."""
+    """[(index into a score array behind the channel, threshold, min_length, the values of the decoder's axes)], thresholds-major,
+    then the axes in their order, then min_length.  axes: their value lists, as laugh_segmenter.decoder_for returns them."""
     extras = [((), ())]
-    for axis in axes or ():
+    for axis in axes:
         extras = [(at + (i,), extra + (v,)) for at, extra in extras for i, v in enumerate(axis)]
     return [((k, *at, l), thr, min_l, extra) for k, thr in enumerate(thresholds) for at, extra in extras
             for l, min_l in enumerate(min_lengths)]
 
 
 def _score_shape(C, thresholds, min_lengths, axes):
-    return (C, len(thresholds), *([] if axes is None else [len(a) for a in axes]), len(min_lengths), len(FIELDS))
+    return (C, len(thresholds), *[len(a) for a in axes], len(min_lengths), len(FIELDS))
 
 
 def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offset_drops=None, min_gaps=None, events=None,
                      penalties=None):
     """laugh_segmenter.get_laughter_instances + score_instances per track -> int64 (C, K, L, 7).  tracks: C arrays (lengths may
     differ); channels: C (meeting_id, chan); fps: a float or C floats.
-    offset_drops / min_gaps (either given): laugh_segmenter.binarize_instances instead -- hysteresis with offset = threshold - drop
-    and gap filling -> int64 (C, K, D, G, L, 7).
-    penalties: laugh_segmenter.viterbi_instances instead -- the best on/off path for log-odds relative to the threshold and a
-    penalty per event -> int64 (C, K, P, L, 7); ValueError together with offset_drops or min_gaps.
+    offset_drops / min_gaps (either given) or penalties: the dictionaries of laugh_segmenter.HYSTERESIS or VITERBI instead, and
+    the lengths of their axes behind K: (C, K, D, G, L, 7) or (C, K, P, L, 7); ValueError for both kinds together.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an array of the same shape with the seven
     EVENT_FIELDS of event_scores_instances."""
-    import laugh_segmenter as ls
     thresholds, min_lengths = list(thresholds), list(min_lengths)
-    f = ls._fps_per_channel(fps, len(channels), each=float).tolist()
-    axes = _extra_axes(offset_drops, min_gaps, penalties)
+    f = ls.fps_per_channel(fps, len(channels), each=float).tolist()
+    decoder, axes = ls.decoder_for(offset_drops, min_gaps, penalties)
     cells = _cells(thresholds, min_lengths, axes)
     out = np.zeros(_score_shape(len(channels), thresholds, min_lengths, axes), np.int64)
     ev = None if events is None else np.zeros(out.shape, np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
-        if axes is None:
-            instances = ls.get_laughter_instances(track, thresholds, min_lengths, f[c])
-        elif penalties is not None:
-            instances = ls.viterbi_instances(track, thresholds, min_lengths, f[c], *axes)
-        else:
-            instances = ls.binarize_instances(track, thresholds, min_lengths, f[c], *axes)
+        instances = ls._instances(decoder, track, thresholds, min_lengths, f[c], axes, device=False)
         got = score_instances(instances, index, *mc)
         got_ev = None if events is None else event_scores_instances(instances, index, *mc, *events)
         for at, thr, min_l, extra in cells:
@@ -392,31 +378,26 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
                        min_gaps=None, events=None, penalties=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
-    TranscriptIndex (or the DeviceIndex of these channels).  lad_runs_count + lad_runs_fill + lad_score_runs (include/lad_hip.h):
-    the run tables never leave the device.
+    TranscriptIndex (or the DeviceIndex of these channels).  The decoder's count + fill (laugh_segmenter._device_tables) + lad_score_runs
+    (include/lad_hip.h) per round of at most decoder.round_size settings: the run tables never leave the device.
     lowpass: a cutoff (of Nyquist): every track is smoothed on the device first (laugh_segmenter.lowpass_device: lad_lowpass before
-    lad_runs_count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN).
-    offset_drops / min_gaps (either given): hysteresis with offset = threshold - drop and gap filling -> int64 (C, K, D, G, L, 7),
-    equal to score_sweep_host with the same two lists: lad_binarize_count + lad_binarize_fill + the same lad_score_runs, at most
-    lad_binarize_max_settings() of the K * D * G settings per round; the low-pass composes in front as above.
-    penalties: the Viterbi decoder -> int64 (C, K, P, L, 7), equal to score_sweep_host with the same list: lad_viterbi_count +
-    lad_viterbi_fill + the same lad_score_runs, at most lad_viterbi_max_settings() of the K * P settings per round; the low-pass
-    composes in front as above.  ValueError together with offset_drops or min_gaps.
+    the count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN).
+    offset_drops / min_gaps (either given) or penalties: HYSTERESIS or VITERBI instead of THRESHOLD -> (C, K, D, G, L, 7) or
+    (C, K, P, L, 7), equal to score_sweep_host with the same lists; ValueError for both kinds together.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
     EVENT_FIELDS, equal to score_sweep_host's: lad_score_events on the same workspace and table as lad_score_runs, in the same
     round; the two score arrays are all that crosses to the host.  Without it no further launch is made."""
     import torch
 
     import _hip
-    import laugh_segmenter as ls
-    probs, dtype, _ = ls._device_track(probs, "scorer")
+    probs, dtype, _ = ls.device_track(probs, "scorer")
     channels, thresholds, min_lengths = list(channels), list(thresholds), list(min_lengths)
     C, T = probs.shape
     L = len(min_lengths)
     if C != len(channels):
         raise ValueError(f"{C} tracks for {len(channels)} channels")
-    fps_host = ls._fps_per_channel(fps, C, each=float)
-    axes = _extra_axes(offset_drops, min_gaps, penalties)
+    ctx = {"fps_host": ls.fps_per_channel(fps, C, each=float)}
+    decoder, axes = ls.decoder_for(offset_drops, min_gaps, penalties)
     out_shape = _score_shape(C, thresholds, min_lengths, axes)
     criteria = None if events is None else _event_criteria(events)
     if T == 0 or 0 in out_shape:
@@ -428,7 +409,7 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
             ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape((C,) + (1,) * (len(out_shape) - 2))
         return np.zeros(out_shape, np.int64), ev
     if lowpass is not None:
-        probs, dtype, _ = ls._device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
+        probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
     elif lengths is not None:
         raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
@@ -436,42 +417,30 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     if dix.channels != channels or dix.device != probs.device:
         raise ValueError("the DeviceIndex was built for other channels or another device")
     mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
-    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    if axes is None:            # one round whatever K is: the library refuses more thresholds than lad_runs_max_thresholds()
-        settings, step = thresholds, len(thresholds)
-    elif penalties is not None:
-        emission = ls._viterbi_table(None)
-        settings, step = ls._viterbi_keys(thresholds, *axes, emission)[1], int(lib.lad_viterbi_max_settings())
-        emission_dev, fps_dev = torch.from_numpy(emission).to(probs.device), torch.from_numpy(fps_host).to(probs.device)
-    else:
-        settings, step = ls._binarize_keys(thresholds, *axes)[1], int(lib.lad_binarize_max_settings())
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    settings = decoder.keys(thresholds, axes, ctx)[1]
+    step = decoder.round_size(lib, len(settings))
     parts, ev_parts = [], []
     for k0 in range(0, len(settings), step):
         chunk = settings[k0:k0 + step]
         n = len(chunk)
         sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
         _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
-        if penalties is not None:
-            ws, table, counts, _ = ls._device_viterbi_tables(probs, dtype, chunk, emission, emission_dev, extra_bytes=sws_bytes)
-        else:
-            ws, table, counts, fps_dev = ls._device_tables(probs, dtype, chunk, fps_host, axes is not None, extra_bytes=sws_bytes)
+        ws, table, counts, _ = ls._device_tables(decoder, probs, dtype, chunk, ctx, extra_bytes=sws_bytes)
         with torch.cuda.device(probs.device):
+            stream = _hip.stream_handle(probs.device)
+            scored = (_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
+                      dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
+                      _hip.ptr(ls.on_device(ctx, "fps_host", probs.device)), ctx["fps_host"].ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                      mls, L)                       # what the two scorers are given alike: the tables, the index, fps and min_lengths
             scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
-            _hip.check(lib.lad_score_runs(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
-                                          _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
-                                          dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
-                                          fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(ws[ws.numel() - sws_bytes:]), _hip.ptr(scores),
-                                          _hip.stream_handle(probs.device)), "lad_score_runs")
+            _hip.check(lib.lad_score_runs(*scored, _hip.ptr(ws[ws.numel() - sws_bytes:]), _hip.ptr(scores), stream), "lad_score_runs")
             if criteria is not None:
                 ews_bytes = lib.lad_score_events_workspace_bytes(C, dix.n_intervals, n, L, len(table))
                 _hip.check(0 if ews_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_events_workspace_bytes")
                 ews = torch.empty(ews_bytes, dtype=torch.uint8, device=probs.device)
                 ev = torch.empty((C, n, L, len(EVENT_FIELDS)), dtype=torch.int64, device=probs.device)
-                _hip.check(lib.lad_score_events(_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds),
-                                                _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
-                                                dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
-                                                fps_host.ctypes.data_as(f64p), mls, L, *criteria, _hip.ptr(ews), _hip.ptr(ev),
-                                                _hip.stream_handle(probs.device)), "lad_score_events")
+                _hip.check(lib.lad_score_events(*scored, *criteria, _hip.ptr(ews), _hip.ptr(ev), stream), "lad_score_events")
                 ev_parts.append(ev.cpu().numpy())
         parts.append(scores.cpu().numpy())
     scores = np.concatenate(parts, axis=1).reshape(out_shape)
@@ -486,7 +455,7 @@ def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=Non
     (offset_drop and min_gap behind min_len), thresholds-major, then drop, then gap, then min_len.
     penalties: scores is (C, K, P, L, 7) and a row has the 15 values of EVAL_COLUMNS_VITERBI (penalty behind min_len)."""
     scores = np.asarray(scores)
-    axes = _extra_axes(offset_drops, min_gaps, penalties)
+    axes = ls.decoder_for(offset_drops, min_gaps, penalties)[1]
     settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
@@ -521,14 +490,15 @@ def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=Non
     return rows
 
 
-def calc_sum_stats(rows, binarize=False, penalties=None):
+def calc_sum_stats(rows, binarize=False, penalties=None, offset_drops=None, min_gaps=None):
     """analyse.py:269-298: per (min_len, threshold) the sums of corr_pred_time, tot_pred_time and tot_transc_laugh_time over the
     meetings (in row order), precision = corr / pred (1 where pred is 0), recall = corr / transcribed (float division: NaN or inf
     where that is 0).  Rows of SUM_COLUMNS, ordered by (min_len, threshold) as the groupby.
     binarize: the rows are eval_rows' 16-value ones; grouped by (min_len, threshold, offset_drop, min_gap), rows of
     SUM_COLUMNS_BINARIZE.
-    penalties (not None): the rows are eval_rows' 15-value ones; grouped by (min_len, threshold, penalty), rows of SUM_COLUMNS_VITERBI."""
-    n_keys = _n_keys(binarize, penalties)
+    penalties (not None): the rows are eval_rows' 15-value ones; grouped by (min_len, threshold, penalty), rows of SUM_COLUMNS_VITERBI.
+    offset_drops / min_gaps (either given) say what binarize=True says, so that eval_rows' keywords can be passed on as they are."""
+    n_keys = 2 + len(_rows_decoder(binarize, penalties, offset_drops, min_gaps).axes)
     sums = {}
     for r in rows:
         acc = sums.setdefault((r[2], r[1]) + tuple(r[3:1 + n_keys]), [0, 0, 0])
@@ -545,11 +515,13 @@ def calc_sum_stats(rows, binarize=False, penalties=None):
     return out
 
 
-def _n_keys(binarize, penalties):
-    """Setting columns of a row behind the meeting: threshold and min_len, plus the extra axes."""
-    if binarize and penalties is not None:
-        raise ValueError("rows are of the hysteresis sweep or of the Viterbi decoder, not both")
-    return 4 if binarize else (3 if penalties is not None else 2)
+def _rows_decoder(binarize, penalties, offset_drops=None, min_gaps=None):
+    """The decoder whose rows calc_sum_stats / event_sum_stats were given: a row has the meeting, threshold and min_len, then the
+    decoder's axes."""
+    try:
+        return ls.decoder_for([] if binarize else offset_drops, min_gaps, penalties)[0]
+    except ValueError:
+        raise ValueError("rows are of the hysteresis sweep or of the Viterbi decoder, not both") from None
 
 
 def _event_figures(n_ref, touched, hit, n_valid, pred_hit, links, onset_ms, offset_ms):
@@ -576,7 +548,7 @@ def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_
     scores, events = np.asarray(scores), np.asarray(events)
     if scores.shape != events.shape:
         raise ValueError(f"scores {scores.shape} and events {events.shape} are not of one sweep")
-    axes = _extra_axes(offset_drops, min_gaps, penalties)
+    axes = ls.decoder_for(offset_drops, min_gaps, penalties)[1]
     settings = [(at, (thr, min_l, *extra)) for at, thr, min_l, extra in _cells(thresholds, min_lengths, axes)]
     per_meeting = {}
     for c, (m, chan) in enumerate(channels):
@@ -591,12 +563,12 @@ def event_rows(scores, events, channels, thresholds, min_lengths, index, offset_
     return rows
 
 
-def event_sum_stats(rows, binarize=False, penalties=None):
+def event_sum_stats(rows, binarize=False, penalties=None, offset_drops=None, min_gaps=None):
     """The figures of event_rows over all meetings, from the summed integers, grouped and ordered as calc_sum_stats: rows of
     EVENT_SUM_COLUMNS (EVENT_SUM_COLUMNS_BINARIZE; EVENT_SUM_COLUMNS_VITERBI with penalties).  A row holds its two error sums as
     means in seconds; mean * 1000 * hit is within a few units in the last place of the integer it came from, so rint gives that
     integer back (sums below 2^50 ms)."""
-    n_keys = _n_keys(binarize, penalties)
+    n_keys = 2 + len(_rows_decoder(binarize, penalties, offset_drops, min_gaps).axes)
     sums = {}
     for r in rows:
         v = r[1 + n_keys + 3:]                                                     # behind precision, recall and F1

@@ -62,7 +62,7 @@ def launches_ms(probs2d, samples, warmup):
     total = int(counts.sum(dtype=np.int64))
     table = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
     # one round of the binarized sweep: the first lad_binarize_max_settings() of the 261 settings
-    _, settings = ls._binarize_keys(THRESHOLDS, OFFSET_DROPS, MIN_GAPS)
+    _, settings = ls.HYSTERESIS.keys(THRESHOLDS, (OFFSET_DROPS, MIN_GAPS), {})
     settings = settings[:int(lib.lad_binarize_max_settings())]
     B = len(settings)
     cols = [(ctypes.c_double * B)(*[s[j] for s in settings]) for j in range(3)]
