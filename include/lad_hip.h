@@ -862,6 +862,52 @@ int lad_viterbi_fill(const void *workspace, const int32_t *counts_host, int64_t 
                      int32_t *table, int64_t capacity_runs, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dense threshold sweep (csrc/surface.hip): the scores of lad_score_runs for up to 4096 ascending levels in one pass over the
+ * track, without any run table.  The reference evaluates 29 thresholds (cluster_scripts/gen_eval_exp.py:30-36); a precision /
+ * recall surface, or an average precision, needs hundreds or thousands, and lad_runs_* + lad_score_runs cost a round per 64.
+ * The run tables of different thresholds are nested (the component tree of the 1-D signal): every row appears unchanged in the
+ * tables of a contiguous range of levels, and a track of T frames has at most T distinct rows.  The text below IS the
+ * specification; sweep_eval.score_surface_host is a second implementation of it, and by construction the result equals
+ * lad_runs_count + lad_runs_fill + lad_score_runs called level by level.
+ *
+ * Frame value.  q[i] is the fixed probability in float64 exactly as lad_runs_count: p > 1 -> 1, p <= 0 -> 1e-7, NaN kept, NaN
+ * beyond the track.
+ * Levels.  HOST double[n_levels], finite and strictly ascending, 1 <= n_levels <= lad_surface_max_levels().  bin[i] = the number
+ * of levels strictly below q[i], 0 for NaN: frame i is on at level j iff q[i] > levels[j] iff j < bin[i] (lad_runs_count's
+ * comparison).
+ * Nodes.  One for every maximal frame interval [first, last] with top = min(bin[first..last]) > 0 whose two outside neighbours,
+ * where they exist, have a bin below top; base = the larger of the two neighbours' bins, 0 for a neighbour beyond the track.  The
+ * interval is a row of the run table of exactly the levels base <= j < top.
+ * A node's integers.  Those of lad_score_runs for the run (first, last) of channel c: start = first / fps[c], end = last / fps[c],
+ * kept for min_length l iff end - start > l, (a, b] = (rint(start * 1000), rint(end * 1000)], w = { 1, valid, pred_ms, corr_ms,
+ * fp_speech_ms, fp_noise_ms, fp_silence_ms } with valid = pred_ms > 0 or the channel has no INVALID interval.
+ * Output.  scores[c][j][l][f] = the sum of w[f] over the nodes of channel c that are kept for l and have base <= j < top: DEVICE
+ * int64[channels][n_levels][n_min_lengths][7], every value written by every call.  A channel with five empty sets still counts
+ * n_pred and n_valid.
+ * Integer sums only, accumulated with vector atomics on int64 and one prefix sum over the levels: identical bytes on every call.
+ * One host-to-device copy (the levels), one memset and SIX launches on `stream`, whatever channels, n_levels and n_min_lengths
+ * are.  A frame's two nearest-smaller searches read at most 2 * ceil(log2(frames)) minima each, whatever the track looks like.
+ * ---------------------------------------------------------------------------------------------- */
+/* largest n_levels of one call (4096) */
+int32_t lad_surface_max_levels(void);
+/* frames one workgroup handles (2048; the tests place their edge cases from it) */
+int32_t lad_surface_tile_frames(void);
+/* bytes of workspace for lad_score_surface; needs no GPU.  -1 and lad_last_error() for channels outside 1..65535, frames outside
+ * 1..2^30, n_intervals outside 0..2^30, n_levels outside 1..lad_surface_max_levels() or n_min_lengths outside
+ * 1..lad_score_max_min_lengths(). */
+int64_t lad_surface_workspace_bytes(int64_t channels, int64_t frames, int64_t n_intervals, int32_t n_levels, int32_t n_min_lengths);
+/* probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype).  levels: HOST.  The index, fps and
+ * min_lengths as for lad_score_runs: bounds, offsets, fps DEVICE; bounds_host, offsets_host, fps_host HOST copies, checked before
+ * anything is launched; min_lengths HOST double[n_min_lengths].  workspace: DEVICE, lad_surface_workspace_bytes of the same sizes.
+ * LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for everything lad_score_runs refuses (sizes, a
+ * null buffer, the index, fps, millisecond overflow, a NaN min_length), an unknown dtype, and levels that are not finite or do not
+ * ascend strictly. */
+int lad_score_surface(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *levels, int32_t n_levels,
+                      const int32_t *bounds, const int32_t *offsets, const int32_t *bounds_host, const int32_t *offsets_host,
+                      int64_t n_intervals, const double *fps, const double *fps_host, const double *min_lengths,
+                      int32_t n_min_lengths, void *workspace, int64_t *scores, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sampling-rate conversion of one channel by up / down = sr_out / sr_in (reduced), polyphase FIR on the device.
  * Replaces the host resampling of the reference's readers: librosa.load(audio_path, sr=44100) in front of the wav cuts
  * (segment_laughter.py:134) and librosa.load(sr=8000) of the code it descends from (laugh_segmenter.py:157-185).

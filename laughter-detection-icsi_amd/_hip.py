@@ -193,6 +193,13 @@ SIGNATURES = {
     "lad_viterbi_count": (c_int, [c_void_p, c_i32, c_i64, c_i64, c_void_p] + [ctypes.POINTER(c_i32)] * 3
                           + [c_i32, c_void_p, c_void_p, c_void_p]),
     "lad_viterbi_fill": (c_int, [c_void_p, ctypes.POINTER(c_i32), c_i64, c_i64, c_i32, c_void_p, c_i64, c_void_p]),
+    # dense threshold sweep: the scores of every level from the track's component tree (csrc/surface.hip)
+    "lad_surface_max_levels": (c_i32, []),
+    "lad_surface_tile_frames": (c_i32, []),
+    "lad_surface_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "lad_score_surface": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p,
+                                  ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
+                                  ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
     # sampling-rate conversion (csrc/resample.hip)
     "lad_resample_out_len": (c_i64, [c_i64, c_i32, c_i32]),
     "lad_resample_tile_outputs": (c_i32, []),

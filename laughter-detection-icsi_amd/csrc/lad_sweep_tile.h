@@ -199,6 +199,31 @@ __device__ inline void coverage_pairs(int64_t c, const int32_t (&x)[2], const in
     }
 }
 
+// the seven integers of lad_score_runs for the run (first, last) of channel c (enum lad_score_field) and its keep bits; a run of
+// one frame is the empty interval (a, a]: it covers nothing, so no look-up is made for it
+constexpr int SCORE_FIELDS = 7;
+__device__ inline unsigned run_fields(int64_t c, int32_t first, int32_t last, double fps, const MinLengths &ml, int L,
+                                      const int32_t *__restrict__ bounds, const int32_t *__restrict__ cum,
+                                      const int32_t *__restrict__ offsets, int64_t n_intervals, int32_t (&v)[SCORE_FIELDS]) {
+    int32_t x[2];
+    const unsigned keep = run_ms(first, last, fps, ml, L, x);
+#pragma unroll
+    for (int f = 0; f < SCORE_FIELDS; ++f) v[f] = 0;
+    v[0] = 1;
+    if (first == last) {
+        v[1] = offsets[c * CLASSES + 1] > offsets[c * CLASSES] ? 0 : 1;      // pred_ms = 0: valid iff there is no INVALID interval
+        return keep;
+    }
+    int32_t F[2 * CLASSES], size[CLASSES];
+    coverage_pairs<CLASSES>(c, x, bounds, cum, offsets, n_intervals, F, size);
+    const int32_t pred = (x[1] - x[0]) - (F[1] - F[0]);                      // |(a, b] \ INVALID|
+    v[1] = size[0] > 0 ? (pred > 0 ? 1 : 0) : 1;                              // analyse.py:185-187
+    v[2] = pred;
+#pragma unroll
+    for (int j = 1; j < CLASSES; ++j) v[2 + j] = F[2 * j + 1] - F[2 * j];
+    return keep;
+}
+
 // ---- host side: `who` is the entry point, `what` its name for the K axis -------------------------------------------------------
 inline int check_sizes(const char *who, const char *what, int64_t channels, int64_t frames, int32_t K) {
     LAD_REQUIRE(channels >= 1 && channels <= MAX_C && frames >= 1 && frames <= MAX_T && K >= 1 && K <= MAX_K,

@@ -31,6 +31,12 @@ scorer from csrc/events.hip.  Without the flag the directory holds the two files
 frame by frame (laugh_segmenter.viterbi_instances under the host scorer, csrc/viterbi.hip under the device scorer): a frame counts
 its log-odds relative to the threshold, every event costs the penalty in nats, and the best set of events is scored.  The CSVs get
 the column penalty behind min_len.  It cannot be combined with --offset_drops / --min_gaps.
+`--threshold_grid N` (default: absent) evaluates the dense grid of thresholds i / N, i = 0..N, instead of a list: every threshold
+from one component tree per track (sweep_eval.score_surface_host under the host scorer, csrc/surface.hip through
+sweep_eval.score_surface_device under the device scorer, `--lowpass` as above).  The two CSVs keep their columns, and
+`pr_summary.csv` (min_len, average_precision, best_f1, best_f1_threshold: sweep_eval.pr_summary) is written next to them.  It
+cannot be combined with an explicit --thresholds, nor with --offset_drops, --min_gaps, --penalties or --events, whose tables are not
+nested in the threshold.  Without the flag the files are what they were.
 """
 import argparse
 import csv
@@ -46,6 +52,8 @@ import numpy as np  # noqa: E402
 
 import laugh_segmenter  # noqa: E402
 import sweep_eval  # noqa: E402
+
+SURFACE_MAX_LEVELS = 4096      # include/lad_hip.h: lad_surface_max_levels() (the host scorer takes the same grids)
 
 
 def read_csv(path, columns, numeric):
@@ -107,15 +115,24 @@ def percent(text):
     return value
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, **axes_and_events):
+def grid_size(text):
+    """--threshold_grid: N steps from 0 to 1, N + 1 levels, at most as many as one call of lad_score_surface takes."""
+    value = int(text)
+    if not 1 <= value <= SURFACE_MAX_LEVELS - 1:
+        raise argparse.ArgumentTypeError(f"an integer in 1..{SURFACE_MAX_LEVELS - 1}, got {text}")
+    return value
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, **axes_and_events):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
     for c, t in enumerate(tracks):
         padded[c, :len(t)] = t
     lengths = [len(t) for t in tracks] if lowpass is not None else None
-    return sweep_eval.score_sweep_device(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index,
-                                         lowpass=lowpass, lengths=lengths, **axes_and_events)
+    score = sweep_eval.score_surface_device if surface else sweep_eval.score_sweep_device
+    return score(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index, lowpass=lowpass, lengths=lengths,
+                 **axes_and_events)
 
 
 def write_csv(path, columns, rows):
@@ -131,7 +148,12 @@ def build_parser():
     parser.add_argument('--probs_dir', required=True, type=str, help='<meeting>/<chan>.npy, as segment_laughter.py --save_probs writes')
     parser.add_argument('--transcripts', required=True, type=str, help='CSV: meeting_id,part_id,chan,start,end,length,type,laugh_type')
     parser.add_argument('--channels', required=True, type=str, help='CSV: meeting_id,part_id,chan,length')
-    parser.add_argument('--thresholds', type=str, default='0.5', help='Single value or comma-separated list of thresholds to evaluate')
+    parser.add_argument('--thresholds', type=str, default=None,
+                        help='Single value or comma-separated list of thresholds to evaluate; default: 0.5')
+    parser.add_argument('--threshold_grid', type=grid_size, default=None, metavar='N',
+                        help=f'(not in the reference) evaluate the thresholds i / N, i = 0..N, N in 1..{SURFACE_MAX_LEVELS - 1}, all from one '
+                             'component tree per track, and also write pr_summary.csv (average precision and the best F1 per min_len); '
+                             'not with --thresholds, --offset_drops, --min_gaps, --penalties or --events; default: absent')
     parser.add_argument('--min_lengths', type=str, default='0.2', help='Single value or comma-separated list of min_lengths to evaluate')
     parser.add_argument('--fps', type=float, default=None, help='frames per second of every track (default: frames / channel length)')
     parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
@@ -165,7 +187,15 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    thresholds = [float(t) for t in args.thresholds.split(',')]
+    if args.threshold_grid is not None:
+        if args.thresholds is not None:
+            raise SystemExit("--threshold_grid cannot be combined with an explicit --thresholds")
+        for flag in ("offset_drops", "min_gaps", "penalties", "events"):
+            if getattr(args, flag):
+                raise SystemExit(f"--threshold_grid cannot be combined with --{flag}: its tables are not nested in the threshold")
+        thresholds = [i / args.threshold_grid for i in range(args.threshold_grid + 1)]
+    else:
+        thresholds = [float(t) for t in (args.thresholds or '0.5').split(',')]
     min_lengths = [float(t) for t in args.min_lengths.split(',')]
     rows = read_csv(args.transcripts, sweep_eval.ROW_COLUMNS, ("start", "end", "length"))
     chans = read_csv(args.channels, sweep_eval.CHANNEL_COLUMNS, ("length",))
@@ -183,7 +213,14 @@ def main(argv=None):
     except ValueError:
         raise SystemExit("--penalties cannot be combined with --offset_drops / --min_gaps")
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if args.events else {}
-    if args.scorer == "device":
+    if args.threshold_grid is not None:
+        if args.scorer == "device":
+            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True)
+        else:
+            if args.lowpass is not None:
+                tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
+            scores = sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index)
+    elif args.scorer == "device":
         scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
     else:
         if args.lowpass is not None:
@@ -197,7 +234,10 @@ def main(argv=None):
     def write(name, base_columns, rows):
         write_csv(os.path.join(args.out_dir, name), sweep_eval.columns(base_columns, decoder), rows)
     write("eval_df_per_meeting.csv", sweep_eval.EVAL_COLUMNS, per_meeting)
-    write("sum_stats.csv", sweep_eval.SUM_COLUMNS, sweep_eval.calc_sum_stats(per_meeting, **extra))
+    sum_stats = sweep_eval.calc_sum_stats(per_meeting, **extra)
+    write("sum_stats.csv", sweep_eval.SUM_COLUMNS, sum_stats)
+    if args.threshold_grid is not None:
+        write_csv(os.path.join(args.out_dir, "pr_summary.csv"), sweep_eval.PR_COLUMNS, sweep_eval.pr_summary(sum_stats))
     if args.events:
         per_meeting_events = sweep_eval.event_rows(scores, events, channels, thresholds, min_lengths, index, **extra)
         write("event_df_per_meeting.csv", sweep_eval.EVENT_COLUMNS, per_meeting_events)

@@ -15,6 +15,11 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
                            or penalties= (laugh_segmenter.VITERBI) and then return (C, K, P, L, 7): the family comes from
                            laugh_segmenter.decoder_for, once per call, and its Decoder record supplies the axes (columns, array
                            shape, key tuples), the settings and the device tables.
+    score_surface_host     the array of score_sweep_host for ascending levels without a loop over them: each node of the track's
+                           component tree scored once, a difference array over the levels, one cumulative sum
+    score_surface_device   the same array for tracks in GPU memory and up to 4096 levels in one call (csrc/surface.hip).  No CPU
+                           fallback.
+    pr_summary             average precision and the best F1 per min_len from calc_sum_stats' rows of one dense grid
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
     event_scores_instances host event scorer of one channel's dictionary -> {key: 7 ints} (include/lad_hip.h: lad_score_events has
@@ -39,6 +44,7 @@ EVAL_COLUMNS = ["meeting", "threshold", "min_len", "precision", "recall", "corr_
                 "num_of_pred_laughs", "valid_pred_laughs", "num_of_transc_laughs", "tot_fp_speech_time", "tot_fp_noise_time",
                 "tot_fp_silence_time"]                                # analyse.py:255-257
 SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.py:290
+PR_COLUMNS = ["min_len", "average_precision", "best_f1", "best_f1_threshold"]     # pr_summary (not in the reference)
 EVENT_FIELDS = ("n_ref", "ref_touched", "ref_hit", "pred_hit", "links", "onset_abs_ms", "offset_abs_ms")      # enum lad_event_field
 EVENT_COLUMNS = ["meeting", "threshold", "min_len", "event_precision", "event_recall", "event_f1", "num_ref_events",
                  "ref_events_touched", "ref_events_hit", "valid_pred_laughs", "pred_laughs_hit", "links",
@@ -445,6 +451,139 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         parts.append(scores.cpu().numpy())
     scores = np.concatenate(parts, axis=1).reshape(out_shape)
     return scores if criteria is None else (scores, np.concatenate(ev_parts, axis=1).reshape(out_shape))
+
+
+def _surface_levels(levels):
+    """The levels of the dense sweep as float64: finite and strictly ascending (what lad_score_surface asks of them)."""
+    lv = np.asarray([float(t) for t in levels], dtype=np.float64)
+    if not np.isfinite(lv).all() or (np.diff(lv) <= 0).any():
+        raise ValueError("the levels of the dense sweep must be finite and ascend strictly")
+    return lv
+
+
+def _surface_nodes(track, levels):
+    """The component tree of one track (include/lad_hip.h: lad_score_surface has the convention): int64 arrays first, last, base,
+    top, one entry per node -- the frame interval [first, last] is a row of the run table of the levels base <= j < top.  One loop
+    over the frames with a stack of the frames that still wait for a smaller bin to their right."""
+    q = ls.fix_probs(track)
+    bins = np.searchsorted(levels, q, side="left")                                  # levels strictly below q
+    bins[np.isnan(q)] = 0
+    b = bins.tolist()
+    T = len(b)
+    right = [T] * T                                                                # the nearest frame to the right with a smaller bin
+    left = [0] * T                                                                 # the nearest frame to the left with a bin <= this one
+    stack = []
+    for i, x in enumerate(b):
+        while stack and b[stack[-1]] > x:
+            right[stack.pop()] = i
+        left[i] = stack[-1] if stack else -1
+        stack.append(i)
+    left, right = np.asarray(left, np.int64), np.asarray(right, np.int64)
+    padded = np.concatenate([bins, [0]])                                           # (index -1 and T: a neighbour beyond the track)
+    lb, rb = padded[left], padded[right]
+    rep = np.flatnonzero((bins > 0) & (lb < bins))                                 # the leftmost minimum of its interval
+    return left[rep] + 1, right[rep] - 1, np.maximum(lb[rep], rb[rep]), bins[rep]
+
+
+def score_surface_host(tracks, channels, levels, min_lengths, fps, index):
+    """The array of score_sweep_host(tracks, channels, levels, min_lengths, fps, index), int64 (C, K, L, 7), for ascending levels
+    without a loop over them: every node of a track's component tree (_surface_nodes) is scored once, its seven integers go to a
+    difference array over the levels, +w at row base and -w at row top, and one cumulative sum gives all K rows.  The parity form
+    of score_surface_device."""
+    lv, min_lengths = _surface_levels(levels), list(min_lengths)
+    f = ls.fps_per_channel(fps, len(channels), each=float).tolist()
+    K, L = len(lv), len(min_lengths)
+    out = np.zeros((len(channels), K, L, len(FIELDS)), np.int64)
+    for c, (track, mc) in enumerate(zip(tracks, channels)):
+        first, last, base, top = _surface_nodes(track, lv)
+        sets = index.scoring_sets(*mc)
+        starts, ends = first / f[c], last / f[c]
+        a, b = to_frames(starts), to_frames(ends)
+        cover = [coverage(s, b) - coverage(s, a) for s in sets]
+        pred = (b - a) - cover[0]
+        valid = pred > 0 if len(sets[0]) else np.ones(len(a), bool)                # analyse.py:185-187
+        w = np.stack([np.ones(len(a), np.int64), valid.astype(np.int64), pred, *cover[1:]], axis=1)
+        length = ends - starts
+        diff = np.zeros((K + 1, L, len(FIELDS)), np.int64)
+        for l, min_l in enumerate(min_lengths):
+            keep = length > min_l
+            np.add.at(diff[:, l], base[keep], w[keep])
+            np.subtract.at(diff[:, l], top[keep], w[keep])
+        out[c] = np.cumsum(diff, axis=0)[:K]
+    return out
+
+
+def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpass=None, lengths=None):
+    """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN -> int64 numpy (C, K, L, 7), equal to
+    score_surface_host (and so to score_sweep_host) of the same tracks, for up to lad_surface_max_levels() ascending levels in one
+    call of lad_score_surface (include/lad_hip.h; csrc/surface.hip): no run table is built and only the scores cross to the host.
+    channels, fps, index, lowpass and lengths as for score_sweep_device.  No CPU fallback."""
+    import torch
+
+    import _hip
+    probs, dtype, _ = ls.device_track(probs, "surface scorer")
+    channels, min_lengths = list(channels), list(min_lengths)
+    lv = _surface_levels(levels)
+    C, T = probs.shape
+    K, L = len(lv), len(min_lengths)
+    if C != len(channels):
+        raise ValueError(f"{C} tracks for {len(channels)} channels")
+    fps_host = ls.fps_per_channel(fps, C, each=float)
+    out_shape = (C, K, L, len(FIELDS))
+    if T == 0 or 0 in out_shape:
+        return np.zeros(out_shape, np.int64)
+    if lowpass is not None:
+        probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "surface scorer")
+    elif lengths is not None:
+        raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
+    lib = _hip.lib()
+    dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
+    if dix.channels != channels or dix.device != probs.device:
+        raise ValueError("the DeviceIndex was built for other channels or another device")
+    ws_bytes = lib.lad_surface_workspace_bytes(C, T, dix.n_intervals, K, L)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_surface_workspace_bytes")
+    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
+    with torch.cuda.device(probs.device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
+        scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
+        fps_dev = torch.from_numpy(fps_host).to(probs.device)
+        _hip.check(lib.lad_score_surface(_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(f64p), K, _hip.ptr(dix.bounds),
+                                         _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
+                                         dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
+                                         fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(ws), _hip.ptr(scores),
+                                         _hip.stream_handle(probs.device)), "lad_score_surface")
+        return scores.cpu().numpy()
+
+
+def pr_summary(sum_rows):
+    """Per min_len of one dense grid, from the rows of calc_sum_stats (threshold, min_len, precision, recall; thresholds ascending
+    within a min_len): rows [min_len, average_precision, best_f1, best_f1_threshold].  With P_j, R_j the precision and recall at
+    threshold j of K, average_precision = sum_j (R_j - R_{j+1}) * P_j with R_K = 0 (recall does not grow with the threshold, so no
+    term is negative); F1_j = 2 P_j R_j / (P_j + R_j), 0 where both are 0, the best one the largest, at the lowest threshold that
+    reaches it.  A min_len whose recall is NaN or inf (nothing transcribed) has NaN for all three."""
+    groups = {}
+    for thr, min_len, prec, recall in sum_rows:
+        groups.setdefault(min_len, []).append((thr, float(prec), float(recall)))
+    out = []
+    nan = float("nan")
+    for min_len in sorted(groups):
+        rows = sorted(groups[min_len])
+        P, R = [r[1] for r in rows], [r[2] for r in rows]
+        if not all(np.isfinite(R)):
+            out.append([min_len, nan, nan, nan])
+            continue
+        ap = 0.0
+        for j in range(len(rows)):
+            ap += (R[j] - (R[j + 1] if j + 1 < len(rows) else 0.0)) * P[j]
+        best, best_thr = -1.0, nan
+        for (thr, _, _), p, r in zip(rows, P, R):
+            f1 = 0.0 if p + r == 0 else 2 * p * r / (p + r)
+            if f1 > best:
+                best, best_thr = f1, thr
+        out.append([min_len, ap, best, best_thr])
+    return out
+
 
 
 def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None, penalties=None):
