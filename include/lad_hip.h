@@ -908,6 +908,43 @@ int lad_score_surface(const void *probs, int32_t dtype, int64_t channels, int64_
                       int32_t n_min_lengths, void *workspace, int64_t *scores, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Event-level scores on the dense sweep (csrc/surface_events.hip): the seven values of lad_score_events for every level of
+ * lad_score_surface, together with that call's own seven, from one set of bins and one tree.  The block above lad_score_events
+ * stays the specification of the seven event fields (ties and a == b runs included), the block above lad_score_surface that of
+ * frame values, levels and nodes; this block only says what the predictions are.  sweep_eval.score_surface_host(..., events=) is a
+ * second implementation.
+ *
+ * Predictions.  For channel c, level j and min_length l: the nodes of lad_score_surface's component tree with base <= j < top that
+ * are kept for l, in frame order -- exactly the kept rows of the run table of level j, each the millisecond interval (a, b] of its
+ * (first, last).
+ * Output.  scores[c][j][l][7] (enum lad_score_field) as lad_score_surface writes it, and events[c][j][l][7] (enum lad_event_field):
+ * both DEVICE int64[channels][n_levels][n_min_lengths][7], every value written by every call.  events equals what lad_runs_count +
+ * lad_runs_fill + lad_score_events give level by level, bit for bit.
+ * How.  PRED_HIT and LINKS are sums over nodes (a node's links: the LAUGH intervals with lo < b minus those with hi <= a, none for
+ * a == b) and go through the difference array over the levels with the seven time fields.  REF_TOUCHED, REF_HIT and the two error
+ * sums are sums over (event, level): since rint(f / fps * 1000) does not decrease with the frame f, a run [s, e] is linked to the
+ * event (lo, hi] iff s <= F1, e >= F0 and a < b, with F0 the first frame whose millisecond is > lo and F1 the last whose
+ * millisecond is < hi; those frames are walked once per 64 adjacent levels.  Work: frames * levels / 64 wave steps for events that
+ * tile the track, whatever their number; an event longer than the track, or one as long as it, is exact and is walked by one wave
+ * per 64 levels.
+ * Integer sums only, accumulated with vector atomics on int64 and one prefix sum over the levels: identical bytes on every call.
+ * One host-to-device copy (the levels), two memsets and SEVEN launches on `stream`, whatever channels, n_levels, n_min_lengths and
+ * the number of events are; no loop over levels or events on the host.
+ * ---------------------------------------------------------------------------------------------- */
+/* bytes of workspace for lad_score_surface_events; needs no GPU.  -1 and lad_last_error() for what lad_surface_workspace_bytes
+ * refuses. */
+int64_t lad_surface_events_workspace_bytes(int64_t channels, int64_t frames, int64_t n_intervals, int32_t n_levels,
+                                           int32_t n_min_lengths);
+/* Arguments as lad_score_surface, then min_overlap_ms >= 0 and min_overlap_pct in 0..100 as lad_score_events; workspace: DEVICE,
+ * lad_surface_events_workspace_bytes of the same sizes.  LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing
+ * written, for everything lad_score_surface refuses and for min_overlap_ms < 0 or min_overlap_pct outside 0..100. */
+int lad_score_surface_events(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *levels,
+                             int32_t n_levels, const int32_t *bounds, const int32_t *offsets, const int32_t *bounds_host,
+                             const int32_t *offsets_host, int64_t n_intervals, const double *fps, const double *fps_host,
+                             const double *min_lengths, int32_t n_min_lengths, int32_t min_overlap_ms, int32_t min_overlap_pct,
+                             void *workspace, int64_t *scores, int64_t *events, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sampling-rate conversion of one channel by up / down = sr_out / sr_in (reduced), polyphase FIR on the device.
  * Replaces the host resampling of the reference's readers: librosa.load(audio_path, sr=44100) in front of the wav cuts
  * (segment_laughter.py:134) and librosa.load(sr=8000) of the code it descends from (laugh_segmenter.py:157-185).

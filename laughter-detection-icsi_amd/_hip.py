@@ -200,6 +200,11 @@ SIGNATURES = {
     "lad_score_surface": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p,
                                   ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
                                   ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p, c_void_p]),
+    # event-level scores on the dense sweep: both score arrays of every level from one tree (csrc/surface_events.hip)
+    "lad_surface_events_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "lad_score_surface_events": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_double), c_i32, c_void_p, c_void_p,
+                                         ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double),
+                                         ctypes.POINTER(c_double), c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     # sampling-rate conversion (csrc/resample.hip)
     "lad_resample_out_len": (c_i64, [c_i64, c_i32, c_i32]),
     "lad_resample_tile_outputs": (c_i32, []),

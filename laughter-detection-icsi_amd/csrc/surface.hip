@@ -7,17 +7,11 @@
 // is scored once (lad_sweep_tile.h: run_fields, the arithmetic of score.hip) and its seven integers go to a difference array over
 // the levels: +w at row base, -w at row top; one prefix sum over the levels gives the array lad_score_runs returns level by level.
 //
-// Frame value and comparison are lad_runs_count's: q = load_fixed(p) in float64, frame i is on at level j iff q > levels[j], i.e.
-// iff j < bin[i], bin[i] = the number of levels strictly below q (0 for NaN and beyond the track).
+// Frame value and comparison, the bins, the tree of minima over them and the two nearest-smaller searches (at most
+// 2 ceil(log2 T) reads each, whatever the track looks like) are lad_surface_tree.h's, shared with surface_events.hip.
 // The node of an interval is found at its leftmost minimum r: the nearest frame left of r with bin <= bin[r] has bin < bin[r] (or
-// there is none); that frame is first - 1, and the nearest frame right of r with bin < bin[r] is last + 1.
-//
-// Nearest smaller values: a binary tree of minima over the bins, level h of it holding min(bin[p 2^h .. (p + 1) 2^h - 1]) at p,
-// ceil(T / 2^h) nodes.  A search walks up from its frame, looking at the one sibling on its side of each ancestor, until a sibling's
-// minimum qualifies, then down into that sibling, taking the child nearer to the frame whenever it qualifies.  At most
-// ceil(log2 T) steps up and as many down, ONE read of the tree per step: at most 2 ceil(log2 T) (60 for the largest track, 38 for
-// 360,000 frames) whatever the track looks like -- a monotone ramp, a constant track and a plateau with one dip included.  A frame
-// whose left search ends at an equal bin is no representative and makes no second search.
+// there is none); that frame is first - 1, and the nearest frame right of r with bin < bin[r] is last + 1.  A frame whose left
+// search ends at an equal bin is no representative and makes no second search.
 //
 // Shape: one copy (the levels), one memset (the difference array) and six launches whatever C, K and L are:
 //   surface_bins_kernel    one workgroup per 2048 frames: bins by binary search in the levels held in LDS (level 0 of the tree) and
@@ -32,153 +26,15 @@
 // Integer sums on int64 only: whatever order the waves arrive in, the bytes are the same.  Every read of the tree is below its
 // level's node count, every index read is clamped to the index (coverage_pairs).  No scratch.
 #pragma clang fp contract(off)
-#include "lad_sweep_tile.h"
+#include "lad_surface_tree.h"
 
 namespace {
 using namespace lad::sweep;
+using namespace lad::surface;
 using lad::ceil_div;
 using lad::up256;
 
-constexpr int MAX_LEVELS = 4096;                 // lad_surface_max_levels(): the levels of a call fill 32 KB of LDS
-constexpr int CHUNK_BITS = 11;
-constexpr int CHUNK = 1 << CHUNK_BITS;           // frames per workgroup: lad_surface_tile_frames(); tree levels per launch: 11
-constexpr int TREE_LEVELS = 1 + 3 * CHUNK_BITS;  // levels 0..33 are written; a search never leaves level ceil(log2 T) <= 30
 constexpr int MAX_PRIVATE_BYTES = 48 * 1024;     // the difference array of one channel in LDS, if it fits
-typedef unsigned short bin_t;                    // 0..4096
-constexpr bin_t ABSENT = 0xffff;                 // beyond a level's last node: never a minimum
-
-// nodes of level h, and the entries a level occupies in a channel's tree (at least its nodes, whatever T)
-__host__ __device__ inline int64_t nodes_at(int64_t T, int h) { return (T + ((int64_t)1 << h) - 1) >> h; }
-__host__ __device__ inline int64_t pitch_at(int64_t T, int h) { return (T >> h) + 2; }
-inline int64_t tree_entries(int64_t T) {
-    int64_t n = 0;
-    for (int h = 0; h < TREE_LEVELS; ++h) n += pitch_at(T, h);
-    return n;
-}
-
-// s holds 2048 entries of level h0 (chunk `chunk` of it, ABSENT beyond the level's nodes): levels h0 + 1 .. h0 + 11 of the chunk
-// into the tree; t: a second buffer of 1024 entries
-__device__ inline void reduce_chunk(bin_t *s, bin_t *t, bin_t *__restrict__ tree, int64_t T, int h0, int64_t chunk) {
-    int64_t off = 0;
-    for (int h = 0; h <= h0; ++h) off += pitch_at(T, h);
-    bin_t *src = s, *dst = t;
-    for (int d = 1; d <= CHUNK_BITS; ++d) {
-        const int cnt = CHUNK >> d;
-        const int64_t n = nodes_at(T, h0 + d), first = chunk * cnt;
-        __syncthreads();
-        for (int i = threadIdx.x; i < cnt; i += THREADS) {
-            const bin_t a = src[2 * i], b = src[2 * i + 1];
-            const bin_t m = a < b ? a : b;
-            dst[i] = m;
-            if (first + i < n) tree[off + first + i] = m;
-        }
-        off += pitch_at(T, h0 + d);
-        bin_t *x = src;
-        src = dst;
-        dst = x;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(THREADS) void surface_bins_kernel(const T *__restrict__ probs, int64_t n, const double *__restrict__ levels,
-                                                               int K, bin_t *__restrict__ trees, int64_t tree_pitch) {
-    __shared__ double lev[MAX_LEVELS];
-    __shared__ bin_t s[CHUNK], t[CHUNK / 2];
-    for (int k = threadIdx.x; k < K; k += THREADS) lev[k] = levels[k];
-    __syncthreads();
-    const int64_t c = blockIdx.y, chunk0 = (int64_t)blockIdx.x * CHUNK;
-    const T *chan = probs + c * n;
-    bin_t *tree = trees + c * tree_pitch;
-    for (int j = threadIdx.x; j < CHUNK; j += THREADS) {
-        const int64_t i = chunk0 + j;
-        bin_t b = ABSENT;
-        if (i < n) {
-            const double q = load_fixed(chan, i, n);
-            int lo = 0, len = K;                     // levels strictly below q: NaN compares false and stays at 0
-            while (len > 0) {
-                const int half = len >> 1;
-                if (lev[lo + half] < q) {
-                    lo += half + 1;
-                    len -= half + 1;
-                } else {
-                    len = half;
-                }
-            }
-            b = (bin_t)lo;
-            tree[i] = b;
-        }
-        s[j] = b;
-    }
-    reduce_chunk(s, t, tree, n, 0, blockIdx.x);
-}
-
-__global__ __launch_bounds__(THREADS) void surface_tree_kernel(bin_t *__restrict__ trees, int64_t tree_pitch, int64_t n, int h0) {
-    __shared__ bin_t s[CHUNK], t[CHUNK / 2];
-    bin_t *tree = trees + (int64_t)blockIdx.y * tree_pitch;
-    int64_t off = 0;
-    for (int h = 0; h < h0; ++h) off += pitch_at(n, h);
-    const int64_t nodes = nodes_at(n, h0), chunk0 = (int64_t)blockIdx.x * CHUNK;
-    for (int j = threadIdx.x; j < CHUNK; j += THREADS) s[j] = chunk0 + j < nodes ? tree[off + chunk0 + j] : ABSENT;
-    reduce_chunk(s, t, tree, n, h0, blockIdx.x);
-}
-
-__global__ __launch_bounds__(THREADS) void surface_cum_kernel(const int32_t *__restrict__ bounds, const int32_t *__restrict__ offsets,
-                                                              int64_t n_intervals, int32_t *__restrict__ cum, int64_t segments) {
-    scan_index_and_counts(bounds, offsets, n_intervals, cum, segments, nullptr, 0, nullptr);     // (no workgroup `segments`)
-}
-
-// the nearest frame left of i whose bin is <= x, or -1; found: its bin (0 for -1)
-__device__ inline int64_t nearest_left_le(const bin_t *__restrict__ tree, int64_t T, int64_t i, int x, int &found) {
-    int64_t p = i, off = 0;
-    int h = 0;
-    found = 0;
-    for (;;) {
-        if (p == 0 || h >= TREE_LEVELS - 1) return -1;
-        if ((p & 1) && tree[off + p - 1] <= x) {
-            --p;
-            break;
-        }
-        off += pitch_at(T, h);
-        p >>= 1;
-        ++h;
-    }
-    while (h > 0) {                                  // node p of level h lies wholly inside the track: both children exist
-        --h;
-        off -= pitch_at(T, h);
-        const int64_t r = 2 * p + 1;
-        p = (r < nodes_at(T, h) && tree[off + r] <= x) ? r : 2 * p;
-    }
-    found = tree[p];
-    return p;
-}
-
-// the nearest frame right of i whose bin is < x (x > 0), or T: the frames beyond the track have bin 0; found: its bin (0 for T)
-__device__ inline int64_t nearest_right_lt(const bin_t *__restrict__ tree, int64_t T, int64_t i, int x, int &found) {
-    int64_t p = i, off = 0;
-    int h = 0;
-    found = 0;
-    for (;;) {
-        if (h >= TREE_LEVELS - 1) return T;
-        if (!(p & 1)) {
-            if (p + 1 >= nodes_at(T, h)) return T;   // the last node of its level, and so are its ancestors
-            if (tree[off + p + 1] < x) {
-                ++p;
-                break;
-            }
-        }
-        off += pitch_at(T, h);
-        p >>= 1;
-        ++h;
-    }
-    while (h > 0) {                                  // the last node of a level may lack its right child: then the left one qualifies
-        --h;
-        off -= pitch_at(T, h);
-        const int64_t l = 2 * p;
-        p = (tree[off + l] < x || l + 1 >= nodes_at(T, h)) ? l : l + 1;
-    }
-    found = tree[p];
-    return p;
-}
 
 __global__ __launch_bounds__(THREADS) void surface_nodes_kernel(const bin_t *__restrict__ trees, int64_t tree_pitch, int64_t T, int K,
                                                                 const double *__restrict__ fps, MinLengths ml, int L,
@@ -247,14 +103,6 @@ __global__ __launch_bounds__(THREADS) void surface_prefix_kernel(const long long
     block_scan<long long>(0, K, [&](int64_t j) { return in[j * LF]; }, [&](int64_t j, long long v) { out[j * LF] = v + in[j * LF]; });
 }
 
-bool surface_sizes_ok(int64_t C, int64_t T, int64_t n_intervals, int64_t K, int64_t L) {
-    return C >= 1 && C <= MAX_C && T >= 1 && T <= MAX_T && n_intervals >= 0 && n_intervals <= MAX_INTERVALS && K >= 1 &&
-           K <= MAX_LEVELS && L >= 1 && L <= MAX_L;
-}
-#define SURFACE_SIZES_MESSAGE(who)                                                                                                 \
-    who ": channels 1..%d, frames 1..2^30, intervals 0..2^30, levels 1..%d, min_lengths 1..%d (got %lld, %lld, %lld, %d, %d)", MAX_C, \
-        MAX_LEVELS, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_levels, n_min_lengths
-
 struct Workspace {
     int64_t levels, cum, diff, trees, tree_pitch, bytes;
 };
@@ -264,7 +112,7 @@ Workspace layout(int64_t C, int64_t T, int64_t n_intervals, int64_t K, int64_t L
     w.cum = up256(K * 8);
     w.diff = w.cum + up256(n_intervals * 4);
     w.trees = w.diff + up256(C * (K + 1) * L * SCORE_FIELDS * 8);
-    w.tree_pitch = up256(tree_entries(T) * (int64_t)sizeof(bin_t)) / (int64_t)sizeof(bin_t);
+    w.tree_pitch = tree_pitch_of(T);
     w.bytes = w.trees + C * w.tree_pitch * (int64_t)sizeof(bin_t) + 256;
     return w;
 }
@@ -293,11 +141,7 @@ extern "C" int lad_score_surface(const void *probs, int32_t dtype, int64_t chann
     LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "lad_score_surface: null interval bounds");
     if (int rc = check_dtype("lad_score_surface", dtype)) return rc;
     const int K = n_levels, L = n_min_lengths;
-    for (int k = 0; k < K; ++k) {
-        LAD_REQUIRE(std::isfinite(levels[k]), "lad_score_surface: levels[%d] = %g is not finite", k, levels[k]);
-        LAD_REQUIRE(k == 0 || levels[k] > levels[k - 1], "lad_score_surface: levels must ascend strictly: levels[%d] = %.17g, levels[%d] = %.17g",
-                    k - 1, levels[k - 1], k, levels[k]);
-    }
+    if (int rc = check_levels("lad_score_surface", levels, K)) return rc;
     MinLengths ml;
     if (int rc = load_min_lengths("lad_score_surface", min_lengths, L, ml)) return rc;
     if (int rc = check_index("lad_score_surface", channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
@@ -310,24 +154,10 @@ extern "C" int lad_score_surface(const void *probs, int32_t dtype, int64_t chann
     bin_t *trees = (bin_t *)(ws + w.trees);
     const hipStream_t st = (hipStream_t)stream;
     const int64_t cells = (int64_t)(K + 1) * L * SCORE_FIELDS;
-    LAD_HIP_CHECK(hipMemcpyAsync(levels_dev, levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
     LAD_HIP_CHECK(hipMemsetAsync(diff, 0, (size_t)(channels * cells) * sizeof(long long), st));
+    if (int rc = build_trees(probs, dtype, channels, frames, levels, K, levels_dev, trees, w.tree_pitch, bounds, offsets, n_intervals, cum, st))
+        return rc;
     const dim3 grid((unsigned)ceil_div(frames, CHUNK), (unsigned)channels);
-    with_track_type(dtype, [&](auto z) {
-        using T = decltype(z);
-        hipLaunchKernelGGL(surface_bins_kernel<T>, grid, dim3(THREADS), 0, st, (const T *)probs, frames, (const double *)levels_dev, K, trees,
-                           w.tree_pitch);
-    });
-    if (int rc = check_launch("surface_bins_kernel")) return rc;
-    for (int h0 = CHUNK_BITS; h0 < TREE_LEVELS - 1; h0 += CHUNK_BITS) {
-        const int64_t nodes = (frames + ((int64_t)1 << h0) - 1) >> h0;
-        hipLaunchKernelGGL(surface_tree_kernel, dim3((unsigned)ceil_div(nodes, CHUNK), (unsigned)channels), dim3(THREADS), 0, st, trees,
-                           w.tree_pitch, frames, h0);
-        if (int rc = check_launch("surface_tree_kernel")) return rc;
-    }
-    const int64_t segments = channels * CLASSES;
-    hipLaunchKernelGGL(surface_cum_kernel, dim3((unsigned)segments), dim3(THREADS), 0, st, bounds, offsets, n_intervals, cum, segments);
-    if (int rc = check_launch("surface_cum_kernel")) return rc;
     const int64_t private_bytes = cells * (int64_t)sizeof(long long);
     const int use_lds = private_bytes <= MAX_PRIVATE_BYTES;
     hipLaunchKernelGGL(surface_nodes_kernel, grid, dim3(THREADS), use_lds ? (size_t)private_bytes : 0, st, (const bin_t *)trees, w.tree_pitch,

@@ -37,6 +37,12 @@ sweep_eval.score_surface_device under the device scorer, `--lowpass` as above). 
 `pr_summary.csv` (min_len, average_precision, best_f1, best_f1_threshold: sweep_eval.pr_summary) is written next to them.  It
 cannot be combined with an explicit --thresholds, nor with --offset_drops, --min_gaps, --penalties or --events, whose tables are not
 nested in the threshold.  Without the flag the files are what they were.
+`--event_grid N` (default: absent) is the dense grid with the event-level scores: the thresholds i / N as above, the three files of
+`--threshold_grid N`, the two event files of `--thresholds <the same list> --events` (criteria from `--event_min_overlap_ms` /
+`--event_min_overlap_pct`) and `event_pr_summary.csv` (min_len, event_average_precision, best_event_f1, best_event_f1_threshold:
+sweep_eval.event_pr_summary), both score arrays from the same component tree (sweep_eval.score_surface_host(..., events=) under
+the host scorer, csrc/surface_events.hip through sweep_eval.score_surface_device(..., events=) under the device scorer).  It
+cannot be combined with --thresholds, --threshold_grid, --events, --offset_drops, --min_gaps or --penalties.
 """
 import argparse
 import csv
@@ -154,6 +160,11 @@ def build_parser():
                         help=f'(not in the reference) evaluate the thresholds i / N, i = 0..N, N in 1..{SURFACE_MAX_LEVELS - 1}, all from one '
                              'component tree per track, and also write pr_summary.csv (average precision and the best F1 per min_len); '
                              'not with --thresholds, --offset_drops, --min_gaps, --penalties or --events; default: absent')
+    parser.add_argument('--event_grid', type=grid_size, default=None, metavar='N',
+                        help='(not in the reference) --threshold_grid N with the event-level scores of every threshold from the same '
+                             'component tree: also writes event_df_per_meeting.csv, event_sum_stats.csv and event_pr_summary.csv (event '
+                             'average precision and the best event F1 per min_len); not with --thresholds, --threshold_grid, --events, '
+                             '--offset_drops, --min_gaps or --penalties; default: absent')
     parser.add_argument('--min_lengths', type=str, default='0.2', help='Single value or comma-separated list of min_lengths to evaluate')
     parser.add_argument('--fps', type=float, default=None, help='frames per second of every track (default: frames / channel length)')
     parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
@@ -187,7 +198,14 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.threshold_grid is not None:
+    grid = args.threshold_grid
+    if args.event_grid is not None:
+        for flag in ("thresholds", "threshold_grid", "events", "offset_drops", "min_gaps", "penalties"):
+            if getattr(args, flag):
+                raise SystemExit(f"--event_grid cannot be combined with --{flag}")
+        grid = args.event_grid
+        thresholds = [i / grid for i in range(grid + 1)]
+    elif args.threshold_grid is not None:
         if args.thresholds is not None:
             raise SystemExit("--threshold_grid cannot be combined with an explicit --thresholds")
         for flag in ("offset_drops", "min_gaps", "penalties", "events"):
@@ -212,21 +230,22 @@ def main(argv=None):
         decoder, _ = laugh_segmenter.decoder_for(**extra)
     except ValueError:
         raise SystemExit("--penalties cannot be combined with --offset_drops / --min_gaps")
-    criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if args.events else {}
-    if args.threshold_grid is not None:
+    with_events = args.events or args.event_grid is not None
+    criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if with_events else {}
+    if grid is not None:
         if args.scorer == "device":
-            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True)
+            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True, **criteria)
         else:
             if args.lowpass is not None:
                 tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
-            scores = sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index)
+            scores = sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index, **criteria)
     elif args.scorer == "device":
         scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
     else:
         if args.lowpass is not None:
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
         scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
-    if args.events:
+    if with_events:
         scores, events = scores
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
     os.makedirs(args.out_dir, exist_ok=True)
@@ -236,12 +255,16 @@ def main(argv=None):
     write("eval_df_per_meeting.csv", sweep_eval.EVAL_COLUMNS, per_meeting)
     sum_stats = sweep_eval.calc_sum_stats(per_meeting, **extra)
     write("sum_stats.csv", sweep_eval.SUM_COLUMNS, sum_stats)
-    if args.threshold_grid is not None:
+    if grid is not None:
         write_csv(os.path.join(args.out_dir, "pr_summary.csv"), sweep_eval.PR_COLUMNS, sweep_eval.pr_summary(sum_stats))
-    if args.events:
+    if with_events:
         per_meeting_events = sweep_eval.event_rows(scores, events, channels, thresholds, min_lengths, index, **extra)
         write("event_df_per_meeting.csv", sweep_eval.EVENT_COLUMNS, per_meeting_events)
-        write("event_sum_stats.csv", sweep_eval.EVENT_SUM_COLUMNS, sweep_eval.event_sum_stats(per_meeting_events, **extra))
+        event_stats = sweep_eval.event_sum_stats(per_meeting_events, **extra)
+        write("event_sum_stats.csv", sweep_eval.EVENT_SUM_COLUMNS, event_stats)
+        if args.event_grid is not None:
+            write_csv(os.path.join(args.out_dir, "event_pr_summary.csv"), sweep_eval.EVENT_PR_COLUMNS,
+                      sweep_eval.event_pr_summary(event_stats))
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

@@ -19,7 +19,10 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
                            component tree scored once, a difference array over the levels, one cumulative sum
     score_surface_device   the same array for tracks in GPU memory and up to 4096 levels in one call (csrc/surface.hip).  No CPU
                            fallback.
+                           Both take events=(min_overlap_ms, min_overlap_pct) and then return (scores, events): the event fields
+                           of every level from the same nodes (csrc/surface_events.hip: lad_score_surface_events)
     pr_summary             average precision and the best F1 per min_len from calc_sum_stats' rows of one dense grid
+    event_pr_summary       the same three figures from event_sum_stats' rows (event precision / recall) of one dense grid
     eval_rows              per (meeting, threshold, min_len) the 14 columns of create_evaluation_df
     calc_sum_stats         threshold, min_len, precision, recall over all meetings
     event_scores_instances host event scorer of one channel's dictionary -> {key: 7 ints} (include/lad_hip.h: lad_score_events has
@@ -45,6 +48,7 @@ EVAL_COLUMNS = ["meeting", "threshold", "min_len", "precision", "recall", "corr_
                 "tot_fp_silence_time"]                                # analyse.py:255-257
 SUM_COLUMNS = ["threshold", "min_len", "precision", "recall"]         # analyse.py:290
 PR_COLUMNS = ["min_len", "average_precision", "best_f1", "best_f1_threshold"]     # pr_summary (not in the reference)
+EVENT_PR_COLUMNS = ["min_len", "event_average_precision", "best_event_f1", "best_event_f1_threshold"]        # event_pr_summary
 EVENT_FIELDS = ("n_ref", "ref_touched", "ref_hit", "pred_hit", "links", "onset_abs_ms", "offset_abs_ms")      # enum lad_event_field
 EVENT_COLUMNS = ["meeting", "threshold", "min_len", "event_precision", "event_recall", "event_f1", "num_ref_events",
                  "ref_events_touched", "ref_events_hit", "valid_pred_laughs", "pred_laughs_hit", "links",
@@ -485,15 +489,79 @@ def _surface_nodes(track, levels):
     return left[rep] + 1, right[rep] - 1, np.maximum(lb[rep], rb[rep]), bins[rep]
 
 
-def score_surface_host(tracks, channels, levels, min_lengths, fps, index):
+def _surface_event_fields(nodes, a, b, kept, sets, n_frames, fps, K, min_ms, min_pct):
+    """The seven EVENT_FIELDS of one track for every (level, min_length), int64 (K, L, 7), from its component tree: nodes = (first,
+    last, base, top) of _surface_nodes, (a, b] their millisecond intervals, kept bool (nodes, L).  PRED_HIT and LINKS are sums over
+    nodes and go through a difference array over the levels.  The rest is per event (lo, hi]: to_frames(f / fps) does not decrease
+    with the frame f, so with F0 the first frame whose millisecond is > lo and F1 the last whose millisecond is < hi, a node is linked
+    to the event iff first <= F1, last >= F0 and a < b; the linked nodes of one level are disjoint and in order, so the first one has
+    the smallest a and the last one the largest b."""
+    first, last, base, top = nodes
+    invalid, laugh = sets[0], sets[1]
+    L = kept.shape[1]
+    need = max(1, min_ms)
+    out = np.zeros((K, L, len(EVENT_FIELDS)), np.int64)
+    out[:, :, 0] = len(laugh)
+    if len(laugh) == 0 or len(first) == 0:
+        return out                                                                 # no event: no link, no prediction overlaps LAUGH
+    lov = coverage(laugh, b) - coverage(laugh, a)
+    pred = (b - a) - (coverage(invalid, b) - coverage(invalid, a))
+    pred_hit = ((lov >= need) & (100 * lov >= min_pct * pred)).astype(np.int64)
+    lo, hi = laugh[:, 0], laugh[:, 1]
+    links = np.where(b > a, np.searchsorted(lo, b, side="left") - np.searchsorted(hi, a, side="right"), 0)
+    w = np.stack([pred_hit, links], axis=1)
+    diff = np.zeros((K + 1, L, 2), np.int64)
+    for l in range(L):
+        np.add.at(diff[:, l], base[kept[:, l]], w[kept[:, l]])
+        np.subtract.at(diff[:, l], top[kept[:, l]], w[kept[:, l]])
+    out[:, :, 3:5] = np.cumsum(diff, axis=0)[:K]
+    ms = to_frames(np.arange(n_frames) / fps)
+    real = b > a
+    far = np.iinfo(np.int64).max
+    for e_lo, e_hi in laugh.tolist():
+        f0, f1 = int(np.searchsorted(ms, e_lo, side="right")), int(np.searchsorted(ms, e_hi, side="left")) - 1
+        if f0 >= n_frames or f1 < 0:
+            continue
+        linked = np.flatnonzero(real & (first <= f1) & (last >= f0))
+        if len(linked) == 0:
+            continue
+        cov, frag = np.zeros((K + 1, L), np.int64), np.zeros((K + 1, L), np.int64)
+        first_a, last_b = np.full((K, L), far, np.int64), np.full((K, L), -1, np.int64)
+        ov = np.minimum(b[linked], e_hi) - np.maximum(a[linked], e_lo)
+        for n, o in zip(linked.tolist(), ov.tolist()):
+            k = kept[n]
+            rows = slice(int(base[n]), int(top[n]))
+            cov[rows] += np.where(k, o, 0)
+            frag[rows] += k
+            first_a[rows] = np.minimum(first_a[rows], np.where(k, a[n], far))
+            last_b[rows] = np.maximum(last_b[rows], np.where(k, b[n], -1))
+        cov, frag = cov[:K], frag[:K]
+        touched = frag > 0
+        hit = touched & (cov >= need) & (100 * cov >= min_pct * (e_hi - e_lo))
+        out[:, :, 1] += touched
+        out[:, :, 2] += hit
+        out[:, :, 5] += np.where(hit, np.abs(first_a - e_lo), 0)
+        out[:, :, 6] += np.where(hit, np.abs(last_b - e_hi), 0)
+    return out
+
+
+def score_surface_host(tracks, channels, levels, min_lengths, fps, index, events=None):
     """The array of score_sweep_host(tracks, channels, levels, min_lengths, fps, index), int64 (C, K, L, 7), for ascending levels
     without a loop over them: every node of a track's component tree (_surface_nodes) is scored once, its seven integers go to a
     difference array over the levels, +w at row base and -w at row top, and one cumulative sum gives all K rows.  The parity form
-    of score_surface_device."""
+    of score_surface_device.
+    events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second the array of score_sweep_host(..., events=) with
+    the seven EVENT_FIELDS, from the same nodes (_surface_event_fields; include/lad_hip.h: lad_score_surface_events) and without a
+    call of the per-level scorers.  Event recall (ref_hit / n_ref) does not grow with the level: a kept run of a higher level lies
+    inside a kept run of every lower one, so what covers an event at level j + 1 covers it at level j."""
     lv, min_lengths = _surface_levels(levels), list(min_lengths)
     f = ls.fps_per_channel(fps, len(channels), each=float).tolist()
     K, L = len(lv), len(min_lengths)
+    criteria = None if events is None else _event_criteria(events)
+    if criteria is not None and (criteria[0] < 0 or not 0 <= criteria[1] <= 100):
+        raise ValueError(f"min_overlap_ms >= 0 and min_overlap_pct in 0..100, got {criteria}")
     out = np.zeros((len(channels), K, L, len(FIELDS)), np.int64)
+    ev = None if criteria is None else np.zeros((len(channels), K, L, len(EVENT_FIELDS)), np.int64)
     for c, (track, mc) in enumerate(zip(tracks, channels)):
         first, last, base, top = _surface_nodes(track, lv)
         sets = index.scoring_sets(*mc)
@@ -510,14 +578,20 @@ def score_surface_host(tracks, channels, levels, min_lengths, fps, index):
             np.add.at(diff[:, l], base[keep], w[keep])
             np.subtract.at(diff[:, l], top[keep], w[keep])
         out[c] = np.cumsum(diff, axis=0)[:K]
-    return out
+        if ev is not None and K and L:
+            kept = length[:, None] > np.asarray(min_lengths, np.float64)[None, :]
+            ev[c] = _surface_event_fields((first, last, base, top), a, b, kept, sets, len(track), f[c], K, *criteria)
+    return out if ev is None else (out, ev)
 
 
-def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpass=None, lengths=None):
+def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpass=None, lengths=None, events=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN -> int64 numpy (C, K, L, 7), equal to
     score_surface_host (and so to score_sweep_host) of the same tracks, for up to lad_surface_max_levels() ascending levels in one
     call of lad_score_surface (include/lad_hip.h; csrc/surface.hip): no run table is built and only the scores cross to the host.
-    channels, fps, index, lowpass and lengths as for score_sweep_device.  No CPU fallback."""
+    channels, fps, index, lowpass and lengths as for score_sweep_device.  No CPU fallback.
+    events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
+    EVENT_FIELDS, equal to score_surface_host's: both from one call of lad_score_surface_events (csrc/surface_events.hip), one set
+    of bins and one tree."""
     import torch
 
     import _hip
@@ -530,8 +604,15 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
         raise ValueError(f"{C} tracks for {len(channels)} channels")
     fps_host = ls.fps_per_channel(fps, C, each=float)
     out_shape = (C, K, L, len(FIELDS))
+    criteria = None if events is None else _event_criteria(events)
     if T == 0 or 0 in out_shape:
-        return np.zeros(out_shape, np.int64)
+        if criteria is None:
+            return np.zeros(out_shape, np.int64)
+        ev = np.zeros(out_shape, np.int64)          # (nothing to launch on: no prediction, the events of each channel counted)
+        if 0 not in out_shape:
+            offsets = (index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)).offsets_host
+            ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape(C, 1, 1)
+        return np.zeros(out_shape, np.int64), ev
     if lowpass is not None:
         probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "surface scorer")
     elif lengths is not None:
@@ -540,20 +621,26 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
     dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
     if dix.channels != channels or dix.device != probs.device:
         raise ValueError("the DeviceIndex was built for other channels or another device")
-    ws_bytes = lib.lad_surface_workspace_bytes(C, T, dix.n_intervals, K, L)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_surface_workspace_bytes")
+    size_query = "lad_surface_workspace_bytes" if criteria is None else "lad_surface_events_workspace_bytes"
+    ws_bytes = getattr(lib, size_query)(C, T, dix.n_intervals, K, L)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, size_query)
     i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
     mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
     with torch.cuda.device(probs.device):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
         scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
         fps_dev = torch.from_numpy(fps_host).to(probs.device)
-        _hip.check(lib.lad_score_surface(_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(f64p), K, _hip.ptr(dix.bounds),
-                                         _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p),
-                                         dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals, _hip.ptr(fps_dev),
-                                         fps_host.ctypes.data_as(f64p), mls, L, _hip.ptr(ws), _hip.ptr(scores),
-                                         _hip.stream_handle(probs.device)), "lad_score_surface")
-        return scores.cpu().numpy()
+        track_and_index = (_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(f64p), K, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
+                           dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
+                           _hip.ptr(fps_dev), fps_host.ctypes.data_as(f64p), mls, L)
+        stream = _hip.stream_handle(probs.device)
+        if criteria is None:
+            _hip.check(lib.lad_score_surface(*track_and_index, _hip.ptr(ws), _hip.ptr(scores), stream), "lad_score_surface")
+            return scores.cpu().numpy()
+        ev = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
+        _hip.check(lib.lad_score_surface_events(*track_and_index, *criteria, _hip.ptr(ws), _hip.ptr(scores), _hip.ptr(ev), stream),
+                   "lad_score_surface_events")
+        return scores.cpu().numpy(), ev.cpu().numpy()
 
 
 def pr_summary(sum_rows):
@@ -584,6 +671,14 @@ def pr_summary(sum_rows):
         out.append([min_len, ap, best, best_thr])
     return out
 
+
+def event_pr_summary(event_sum_rows):
+    """pr_summary's rule on the event-level figures of one dense grid: from the rows of event_sum_stats (EVENT_SUM_COLUMNS:
+    threshold, min_len, event_precision, event_recall, ...) rows of EVENT_PR_COLUMNS per min_len: the event average precision
+    sum_j (R_j - R_{j+1}) * P_j, the best event F1 and the lowest threshold that reaches it.  Event recall does not grow with the
+    threshold (a kept run of a higher level lies inside a kept run of every lower one), so no term is negative.  A min_len without
+    an event (NaN recall) has NaN for all three."""
+    return pr_summary([r[:4] for r in event_sum_rows])
 
 
 def eval_rows(scores, channels, thresholds, min_lengths, index, offset_drops=None, min_gaps=None, penalties=None):
