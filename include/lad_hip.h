@@ -1015,6 +1015,39 @@ int lad_lowpass(const void *probs, int32_t dtype, int64_t channels, int64_t fram
                 void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rank filtering of probability tracks on the device (csrc/rankfilt.hip): median, minimum, maximum or any other order statistic
+ * of a sliding window.  Not in the reference, whose only smoother is lowpass (laugh_segmenter.py:49-55); it stands at the same
+ * place, in front of the thresholds.
+ * Convention: for channel c with length n = lengths[c] (or `frames` when lengths_host is NULL) and h = (window - 1) / 2
+ *   out[c][i] = sort_ascending( probs[c][clamp(i - h + j, 0, n - 1)]  for j in 0 .. window-1 )[rank]    for 0 <= i < n
+ *   out[c][i] = NaN                                                                                      for n <= i < frames
+ * i.e. edge replication at the channel's own length (scipy.ndimage's mode='nearest'): the pad of a ragged tensor never enters
+ * a window.  rank = h is the median, rank = 0 the minimum, rank = window - 1 the maximum.  n <= h is legal, every index then
+ * clamps.  The result is a selected input value in the dtype of probs, never an arithmetic result.  -0.0 and 0.0 compare
+ * equal, and which of the two comes back is unspecified.  The input must hold no NaN inside a channel's length; if it does,
+ * only the outputs whose window contains the NaN are unspecified, no other frame and no other channel is affected.
+ * One workgroup per (channel, lad_rank_filter_tile_frames() output frames), one lane per frame: a bitwise binary search on
+ * order-preserving keys in LDS, 32 or 64 passes of `window` reads per frame whatever the data holds.  One launch whatever the
+ * sizes, no workgroup waits for another, no atomics (identical bytes on every call).
+ * ---------------------------------------------------------------------------------------------- */
+/* output frames per workgroup tile (the tests place their edge cases from it) */
+int32_t lad_rank_filter_tile_frames(void);
+/* the largest window: 1023 frames */
+int32_t lad_rank_filter_max_window(void);
+/* bytes of workspace for lad_rank_filter; needs no GPU.  -1 and lad_last_error() for channels outside 1..65535, frames outside
+ * 1..2^30, or a window that is even or outside 1..lad_rank_filter_max_window(). */
+int64_t lad_rank_filter_workspace_bytes(int64_t channels, int64_t frames, int32_t window);
+/* probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype); frames is the row stride of probs and
+ * out.  lengths_host: HOST int64[channels], each 1..frames, or NULL for `frames` everywhere (it has been copied when the call
+ * returns).  window: odd, 1..lad_rank_filter_max_window(); rank: 0..window - 1.  out: DEVICE [channels][frames] of the dtype of
+ * probs.  workspace: DEVICE, lad_rank_filter_workspace_bytes.  LAD_ERR_INVALID with lad_last_error() set, nothing launched and
+ * nothing written, for a size, window, rank or length out of range, an even window, a null pointer, an unknown dtype, or out
+ * overlapping probs or the workspace (or probs overlapping the workspace).  The input is never written; every store is guarded
+ * by the row stride. */
+int lad_rank_filter(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const int64_t *lengths_host,
+                    int32_t window, int32_t rank, void *out, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Redrawing the segment table (csrc/sample.hip): which frames of which channel form each training example, drawn afresh for
  * every epoch from regions and pools of regions.  Replaces, on the device, the sampling of the reference's create_data_df.py
  * (get_subsample :84-95, get_random_segment_from_df :65-81, the rejection loops of get_random_non_laughter_segment :32-63) and

@@ -219,6 +219,11 @@ SIGNATURES = {
     "lad_lowpass_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "lad_lowpass": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64)] + [ctypes.POINTER(c_double)] * 3
                     + [c_void_p, c_void_p, c_void_p]),
+    # median / rank filter of the probability track (csrc/rankfilt.hip)
+    "lad_rank_filter_tile_frames": (c_i32, []),
+    "lad_rank_filter_max_window": (c_i32, []),
+    "lad_rank_filter_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "lad_rank_filter": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64), c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     # redrawing the segment table, transcript coverage of windows (csrc/sample.hip)
     "lad_sample_segments": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i32,
                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),

@@ -19,6 +19,9 @@ Writes `eval_df_per_meeting.csv` (the 14 columns of analyse.py:255-257) and `sum
 (csrc/runs.hip + csrc/score.hip through sweep_eval.score_sweep_device); both scorers write the same bytes.
 `--lowpass CUTOFF` (default: off) smooths every track first, as the reference's lowpass (laugh_segmenter.py:49-55) does before
 its thresholds: on the host with scipy, under the device scorer on the GPU (csrc/lowpass.hip) with each track's true length.
+`--median FRAMES` (default: off; not in the reference) passes every track through a median filter of FRAMES frames first (odd,
+1..1023; the ends replicated): laugh_segmenter.median_filter under the host scorer, csrc/rankfilt.hip under the device scorer with
+each track's true length -- the same values bit for bit, so both scorers still write the same bytes.  Not together with --lowpass.
 `--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling to the sweep (laugh_segmenter.binarize_instances
 under the host scorer, csrc/binarize.hip under the device scorer): the CSVs get the columns offset_drop and min_gap behind min_len
 and the summary is grouped by all four.  Without the two flags the files are what they were.
@@ -99,6 +102,17 @@ def cutoff_arg(text):
     return value
 
 
+def window_arg(text):
+    """--median: an odd number of frames from 1 to 1023 (include/lad_hip.h: lad_rank_filter_max_window())."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"an odd integer from 1 to 1023, got {text}")
+    if not 1 <= value <= 1023 or value % 2 == 0:
+        raise argparse.ArgumentTypeError(f"an odd integer from 1 to 1023, got {text}")
+    return value
+
+
 def float_list(text):
     """--offset_drops / --min_gaps: a comma-separated list of non-negative numbers."""
     values = [float(t) for t in text.split(',')]
@@ -129,16 +143,16 @@ def grid_size(text):
     return value
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, **axes_and_events):
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, median=None, **axes_and_events):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
     for c, t in enumerate(tracks):
         padded[c, :len(t)] = t
-    lengths = [len(t) for t in tracks] if lowpass is not None else None
+    lengths = [len(t) for t in tracks] if lowpass is not None or median is not None else None
     score = sweep_eval.score_surface_device if surface else sweep_eval.score_sweep_device
     return score(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index, lowpass=lowpass, lengths=lengths,
-                 **axes_and_events)
+                 **({} if median is None else {"median": median}), **axes_and_events)
 
 
 def write_csv(path, columns, rows):
@@ -174,6 +188,10 @@ def build_parser():
                         help='smooth every track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards and '
                              'backwards (laugh_segmenter.lowpass under the host scorer, csrc/lowpass.hip under the device scorer; the '
                              "reference's own cutoff is 0.01); default: off")
+    parser.add_argument('--median', type=window_arg, default=None, metavar='FRAMES',
+                        help='(not in the reference) pass every track through a median filter of FRAMES frames before the sweep (odd, '
+                             '1..1023, the ends replicated: laugh_segmenter.median_filter under the host scorer, csrc/rankfilt.hip under '
+                             'the device scorer); not with --lowpass; default: off')
     parser.add_argument('--offset_drops', type=float_list, default=None,
                         help='(not in the reference) comma-separated list: hysteresis, an event that starts above a threshold lasts '
                              'until the track falls to or below threshold - drop; default: absent (no hysteresis axis)')
@@ -198,6 +216,8 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.median is not None and args.lowpass is not None:
+        raise SystemExit("--median cannot be combined with --lowpass: they are two smoothers for the same place")
     grid = args.threshold_grid
     if args.event_grid is not None:
         for flag in ("thresholds", "threshold_grid", "events", "offset_drops", "min_gaps", "penalties"):
@@ -234,16 +254,20 @@ def main(argv=None):
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if with_events else {}
     if grid is not None:
         if args.scorer == "device":
-            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True, **criteria)
+            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True, median=args.median, **criteria)
         else:
             if args.lowpass is not None:
                 tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
+            elif args.median is not None:
+                tracks = [laugh_segmenter.median_filter(t, args.median) for t in tracks]
             scores = sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index, **criteria)
     elif args.scorer == "device":
-        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, **extra, **criteria)
+        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, median=args.median, **extra, **criteria)
     else:
         if args.lowpass is not None:
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
+        elif args.median is not None:
+            tracks = [laugh_segmenter.median_filter(t, args.median) for t in tracks]
         scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
     if with_events:
         scores, events = scores

@@ -68,6 +68,50 @@ def lowpass_device(probs, cutoff=0.01, lengths=None):
     return lowpass_mod.lowpass_device(probs, cutoff=cutoff, lengths=lengths)
 
 
+def rank_filter(sig, window, rank):
+    """Element `rank` of the sorted window of `window` frames (odd, 1..1023) around every frame of a 1-D track, its ends replicated
+    (scipy.ndimage.rank_filter with mode='nearest'; the convention is written out above lad_rank_filter in include/lad_hip.h).
+    Not in the reference.  float32 / float64 in, the same dtype out (anything else is taken as float64): the result is one of the
+    track's own values.  Host parity form of csrc/rankfilt.hip: every window is sorted, O(T window log window)."""
+    import rankfilt
+    window, rank = rankfilt.check_window(window, rank)
+    sig = np.asarray(sig)
+    if sig.dtype not in (np.float32, np.float64):
+        sig = sig.astype(np.float64)
+    if sig.ndim != 1 or sig.size < 1:
+        raise ValueError(f"the track is 1-D with at least one frame, got shape {sig.shape}")
+    if sig.size > 2 ** 30:
+        raise ValueError(f"the track has {sig.size} frames, more than 2^30")
+    h = (window - 1) // 2
+    windows = np.lib.stride_tricks.sliding_window_view(np.pad(sig, h, mode="edge"), window)
+    out = np.empty_like(sig)
+    step = max(1, (1 << 22) // window)      # (the sorted copies of 4 M elements at a time, not of T * window)
+    for i0 in range(0, sig.size, step):
+        out[i0:i0 + step] = np.partition(windows[i0:i0 + step], rank, axis=1)[:, rank]
+    return out
+
+
+def median_filter(sig, window):
+    """The median of `window` frames (odd, 1..1023) around every frame, the track's ends replicated: rank_filter at rank
+    (window - 1) / 2, scipy.ndimage.median_filter(sig, window, mode='nearest').  It removes every flicker shorter than window / 2
+    frames, keeps every edge where it was and returns only values the track already holds."""
+    import rankfilt
+    return rank_filter(sig, *rankfilt.check_window(window))
+
+
+def rank_filter_device(probs, window, rank, lengths=None, out=None):
+    """`rank_filter` for a (T,) or (C, T) track in GPU memory (csrc/rankfilt.hip through rankfilt.py): a tensor of the same shape and
+    dtype that stays on the device, bit for bit what the host form returns.  No CPU fallback."""
+    import rankfilt
+    return rankfilt.rank_filter_device(probs, window, rank, lengths=lengths, out=out)
+
+
+def median_filter_device(probs, window, lengths=None, out=None):
+    """`median_filter` for a (T,) or (C, T) track in GPU memory, e.g. for get_laughter_instances_device.  No CPU fallback."""
+    import rankfilt
+    return rankfilt.median_filter_device(probs, window, lengths=lengths, out=out)
+
+
 def fix_over_underflow(prob):
     """p > 1 -> 1; p <= 0 -> 1e-7 (so that threshold 0 still accepts the frame); else p."""
     if prob > 1:

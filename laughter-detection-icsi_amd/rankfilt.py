@@ -1,0 +1,78 @@
+"""Median and rank filtering of probability tracks on the MI355X (csrc/rankfilt.hip).
+
+Not in the reference, whose only smoother is `lowpass` (laugh_segmenter.py:49-55); this one stands at the same place, in front of
+the thresholds.  The convention is written out above lad_rank_filter in include/lad_hip.h: a window of `window` frames (odd) around
+every frame with the track's ends replicated (scipy.ndimage's mode='nearest'), sorted, its element `rank` taken.  The median is
+rank = (window - 1) / 2, the minimum rank 0, the maximum rank window - 1.  The result is one of the track's own values, so the
+device form equals the host form (laugh_segmenter.rank_filter) bit for bit.  There is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+
+MAX_WINDOW = 1023      # lad_rank_filter_max_window()
+
+
+def check_window(window, rank=None):
+    """(window, rank) as ints; ValueError for what lad_rank_filter refuses: a window that is even or outside 1..1023, a rank outside
+    0..window - 1 (rank=None: the median's)."""
+    if isinstance(window, bool) or int(window) != window:
+        raise ValueError(f"window must be an odd integer from 1 to {MAX_WINDOW}, got {window!r}")
+    window = int(window)
+    if not 1 <= window <= MAX_WINDOW or window % 2 == 0:
+        raise ValueError(f"window must be an odd integer from 1 to {MAX_WINDOW}, got {window}")
+    if rank is None:
+        return window, (window - 1) // 2
+    if isinstance(rank, bool) or int(rank) != rank or not 0 <= int(rank) < window:
+        raise ValueError(f"rank must be an integer from 0 to window - 1 = {window - 1}, got {rank!r}")
+    return window, int(rank)
+
+
+def rank_filter_device(probs, window, rank, lengths=None, out=None):
+    """Element `rank` of the sorted window of `window` frames around every frame, the ends replicated, on the device.  probs: (T,) or
+    (C, T) float32 / float64 GPU tensor, contiguous -> a tensor of the same shape and dtype.  lengths: C ints, channel c is filtered
+    over its first lengths[c] frames (its end is replicated there) and the rest of its row comes back as NaN.  out: a contiguous GPU
+    tensor of the same shape and dtype to write into."""
+    import torch
+
+    import _hip
+    single = getattr(probs, "ndim", None) == 1
+    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
+    if getattr(p2, "ndim", None) != 2:
+        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device rank filter has no CPU fallback)")
+    if isinstance(p2, torch.Tensor) and p2.is_cuda and p2.dtype not in (torch.float32, torch.float64):
+        raise _hip.LadHipError(f"probs must be float32 or float64, got {p2.dtype}")
+    _hip.require_cuda(p2, "probs")
+    window, rank = check_window(window, rank)
+    C, T = p2.shape
+    if lengths is not None:
+        lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if lengths.shape != (C,):
+            raise ValueError(f"{lengths.size} lengths for {C} channels")
+        if C and T and (lengths.min() < 1 or lengths.max() > T):
+            raise ValueError(f"every length lies in 1..{T}, got {int(lengths.min())}..{int(lengths.max())}")
+    if out is None:
+        out2 = torch.empty((C, T), dtype=p2.dtype, device=p2.device)
+    else:
+        _hip.require_cuda(out, "out", p2.dtype)
+        if out.shape != probs.shape or out.device != p2.device:
+            raise ValueError("out must have the shape and device of probs")
+        out2 = out.unsqueeze(0) if single else out
+    if C == 0 or T == 0:
+        return out2[0] if single else out2
+    lib = _hip.lib()
+    ws_bytes = lib.lad_rank_filter_workspace_bytes(C, T, window)
+    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_rank_filter_workspace_bytes")
+    dtype = 0 if p2.dtype == torch.float32 else 1     # lad_runs_dtype
+    lptr = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if lengths is not None else None
+    with torch.cuda.device(p2.device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p2.device)
+        _hip.check(lib.lad_rank_filter(_hip.ptr(p2), dtype, C, T, lptr, window, rank, _hip.ptr(out2), _hip.ptr(ws),
+                                       _hip.stream_handle(p2.device)), "lad_rank_filter")
+    return out2[0] if single else out2
+
+
+def median_filter_device(probs, window, lengths=None, out=None):
+    """Device form of laugh_segmenter.median_filter for a track that is already in GPU memory: rank_filter_device at the median's
+    rank, (window - 1) / 2."""
+    return rank_filter_device(probs, window, check_window(window)[1], lengths=lengths, out=out)

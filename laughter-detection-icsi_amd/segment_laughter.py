@@ -25,6 +25,10 @@ cross to the host, and the track itself only when `--save_probs` asks for it.  S
 which segment_laughter.py:107-108 leaves commented out): scipy on the host under `--segmenter host`, csrc/lowpass.hip under
 `--segmenter device`, where the track still never leaves the GPU.  `--save_probs` keeps writing the raw track.
 
+`--median FRAMES` (default: off; not in the reference) passes the track through a median filter of FRAMES frames before the sweep
+(odd, 1..1023, the ends replicated): laugh_segmenter.median_filter under `--segmenter host`, csrc/rankfilt.hip under `--segmenter
+device` -- the same values bit for bit, so the same files.  Not together with `--lowpass`; `--save_probs` keeps writing the raw track.
+
 `--offset_drops` / `--min_gaps` (default: absent) add hysteresis and gap filling (laugh_segmenter.binarize_instances, or
 csrc/binarize.hip under `--segmenter device`): the instances of setting (thr, drop, gap, min_len) go to
 `t_<thr>/l_<min_len>/d_<drop>_g_<gap>/`.  Without the two flags paths and bytes are what they were.
@@ -48,7 +52,7 @@ import torch  # noqa: E402
 
 import audio_utils  # noqa: E402
 import config as config_mod  # noqa: E402
-from evaluate_sweep import cutoff_arg, float_list  # noqa: E402  (the argparse types of --lowpass and of the decoders' lists)
+from evaluate_sweep import cutoff_arg, float_list, window_arg  # noqa: E402  (the argparse types of --lowpass, --median and the decoders' lists)
 import laugh_segmenter  # noqa: E402
 import load_data  # noqa: E402
 import parallel  # noqa: E402
@@ -117,16 +121,19 @@ def save_audio_instances(instances, audio_path, output_dir, rate=None):
 
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
-                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None):
+                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None, median=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
     (None: the file's own).  lowpass: a cutoff (of Nyquist): the track is smoothed before the sweep (segment_laughter.py:107-108), on
-    the host or on the device like the sweep itself; save_probs still gets the raw track.
+    the host or on the device like the sweep itself; save_probs still gets the raw track.  median: a window in frames (odd,
+    1..1023): the track goes through the median filter instead (laugh_segmenter.median_filter / median_filter_device); not both.
     offset_drops / min_gaps (either given): hysteresis and gap filling; the dictionary's keys are (thr, drop, gap, min_len).
     penalties: the Viterbi decoder; the dictionary's keys are (thr, penalty, min_len).  Not together with the two above."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
+    if lowpass is not None and median is not None:
+        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
     if save_to_audio_files and output_dir is None:
         raise Exception("Need to specify an output directory to save audio files")   # segment_laughter.py:138-140
     start_time = time.time()
@@ -142,6 +149,9 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     if lowpass is not None and (segmenter == "host" or rank == 0):
         probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
             laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
+    elif median is not None and (segmenter == "host" or rank == 0):
+        probs = laugh_segmenter.median_filter(probs, median) if segmenter == "host" else \
+            laugh_segmenter.median_filter_device(probs, median)
     decoder, axis_values = laugh_segmenter.decoder_for(offset_drops, min_gaps, penalties)
     if segmenter == "host" or rank == 0:
         instance_dict = laugh_segmenter._instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device=segmenter == "device")
@@ -193,6 +203,10 @@ def build_parser():
                         help="smooth the probability track before the sweep: second-order Butterworth at CUTOFF of Nyquist, forwards "
                              "and backwards (the reference's lowpass, cutoff 0.01, which it leaves commented out); on the host or the "
                              "GPU as --segmenter says; default: off")
+    parser.add_argument('--median', type=window_arg, default=None, metavar='FRAMES',
+                        help="(not in the reference) pass the probability track through a median filter of FRAMES frames before the "
+                             "sweep (odd, 1..1023, the ends replicated); on the host or the GPU as --segmenter says; not with --lowpass; "
+                             "default: off")
     parser.add_argument('--offset_drops', type=float_list, default=None,
                         help="(not in the reference) comma-separated list: hysteresis, an instance that starts above a threshold lasts "
                              "until the track falls to or below threshold - drop; default: absent")
@@ -213,6 +227,8 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.median is not None and args.lowpass is not None:
+        raise SystemExit("--median cannot be combined with --lowpass: they are two smoothers for the same place")
     if args.gpus is not None and args.gpus > 1 and not parallel.under_launcher():
         raise SystemExit(parallel.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:] if argv is None else list(argv),
                                               timeout=None))
@@ -231,7 +247,8 @@ def main(argv=None):
                   save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
                   segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
-                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties)
+                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties,
+                  median=args.median)
 
 
 if __name__ == '__main__':

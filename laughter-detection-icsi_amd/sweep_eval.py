@@ -385,13 +385,15 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offs
 
 
 def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
-                       min_gaps=None, events=None, penalties=None):
+                       min_gaps=None, events=None, penalties=None, median=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
     (C, K, L, 7), equal to score_sweep_host of the same tracks.  channels: C (meeting_id, chan); fps: a float or C floats; index: a
     TranscriptIndex (or the DeviceIndex of these channels).  The decoder's count + fill (laugh_segmenter._device_tables) + lad_score_runs
     (include/lad_hip.h) per round of at most decoder.round_size settings: the run tables never leave the device.
     lowpass: a cutoff (of Nyquist): every track is smoothed on the device first (laugh_segmenter.lowpass_device: lad_lowpass before
     the count), channel c over its first lengths[c] frames (lengths=None: all T; the padding stays NaN).
+    median: a window in frames (odd, 1..1023): every track goes through the median filter on the device first instead
+    (laugh_segmenter.median_filter_device: lad_rank_filter), with `lengths` as for lowpass; ValueError for both smoothers together.
     offset_drops / min_gaps (either given) or penalties: HYSTERESIS or VITERBI instead of THRESHOLD -> (C, K, D, G, L, 7) or
     (C, K, P, L, 7), equal to score_sweep_host with the same lists; ValueError for both kinds together.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
@@ -401,6 +403,8 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
 
     import _hip
     probs, dtype, _ = ls.device_track(probs, "scorer")
+    if lowpass is not None and median is not None:
+        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
     channels, thresholds, min_lengths = list(channels), list(thresholds), list(min_lengths)
     C, T = probs.shape
     L = len(min_lengths)
@@ -420,6 +424,8 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         return np.zeros(out_shape, np.int64), ev
     if lowpass is not None:
         probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
+    elif median is not None:
+        probs, dtype, _ = ls.device_track(ls.median_filter_device(probs, median, lengths=lengths), "scorer")
     elif lengths is not None:
         raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
@@ -584,11 +590,11 @@ def score_surface_host(tracks, channels, levels, min_lengths, fps, index, events
     return out if ev is None else (out, ev)
 
 
-def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpass=None, lengths=None, events=None):
+def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpass=None, lengths=None, events=None, median=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN -> int64 numpy (C, K, L, 7), equal to
     score_surface_host (and so to score_sweep_host) of the same tracks, for up to lad_surface_max_levels() ascending levels in one
     call of lad_score_surface (include/lad_hip.h; csrc/surface.hip): no run table is built and only the scores cross to the host.
-    channels, fps, index, lowpass and lengths as for score_sweep_device.  No CPU fallback.
+    channels, fps, index, lowpass, median and lengths as for score_sweep_device.  No CPU fallback.
     events=(min_overlap_ms, min_overlap_pct): returns (scores, events), the second an int64 array of the same shape with the seven
     EVENT_FIELDS, equal to score_surface_host's: both from one call of lad_score_surface_events (csrc/surface_events.hip), one set
     of bins and one tree."""
@@ -596,6 +602,8 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
 
     import _hip
     probs, dtype, _ = ls.device_track(probs, "surface scorer")
+    if lowpass is not None and median is not None:
+        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
     channels, min_lengths = list(channels), list(min_lengths)
     lv = _surface_levels(levels)
     C, T = probs.shape
@@ -615,6 +623,8 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
         return np.zeros(out_shape, np.int64), ev
     if lowpass is not None:
         probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "surface scorer")
+    elif median is not None:
+        probs, dtype, _ = ls.device_track(ls.median_filter_device(probs, median, lengths=lengths), "surface scorer")
     elif lengths is not None:
         raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
