@@ -1048,6 +1048,52 @@ int lad_rank_filter(const void *probs, int32_t dtype, int64_t channels, int64_t 
                     int32_t window, int32_t rank, void *out, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Confidence of an instance (csrc/spanstats.hip): the sum and the earliest peak of the probability track over every row of the
+ * span tables, whichever decoder cut them (lad_runs_fill, lad_binarize_fill, lad_viterbi_fill, or the caller).  Not in the
+ * reference, which returns bare (start, end).
+ * Convention: for the track p of channel c and a row (first, last) of one of its tables, 0 <= first <= last < frames:
+ *   frame value   v(i) is lad_runs_count's: the element as float64, > 1 -> 1.0, <= 0 -> 0.0000001.  w(i) = v(i), or 0.0 where the
+ *                 element is NaN (hysteresis gap filling, Viterbi paths and caller-made tables can put NaN frames inside a span).
+ *   sum           Q(i) = rint(w(i) * 2^32) in float64, round-half-even, as an int64: the product is exact, so Q is a pure function
+ *                 of the element.  sum = Q(first) + ... + Q(last), int64: at most 2^62 with frames <= 2^30, it cannot overflow.
+ *   peak          the earliest frame of first..last at which w is largest, compared on w itself, not on Q.  peak_value = w(peak),
+ *                 one of the track's own fixed values bit for bit; 0.0 only if every frame of the span is NaN.
+ *   invalid rows  first < 0, last >= frames or first > last: nothing is read, the row yields (sum 0, peak -1, peak_value 0.0).
+ *   derived       on the host, from the integers (laugh_segmenter.confidences): n = last - first + 1,
+ *                 mean = float64(sum) / float64(n * 2^32), one IEEE division; peak_time = peak / fps, as `start` is computed.
+ *                 No floating-point sum runs on the device.
+ * lad_span_stats_prepare runs once per track, independent of any setting, and writes into the workspace the inclusive int64
+ * prefix sums of Q per channel and a binary tree of maxima of w (float64, level h: the maximum of 2^h frames; level 0 is the
+ * track): five launches whatever the sizes and the data (chunk sums and tree levels 1..11 per lad_span_stats_tile_frames()
+ * frames, the scan of the chunk sums, the chunks again, two more launches of 11 tree levels each); no atomics, no workgroup
+ * waits for another.  lad_span_stats is one copy of channels + 1 int64 and one launch, one lane per row: the sum is two reads
+ * of the prefix sums, the peak at most 3 ceil(log2 frames) + 2 reads of the tree (up the two edges of the span, two reads a
+ * level, then down into the leftmost child that holds the maximum, one read a level): 92 for the largest track, 59 for 360,000
+ * frames, whatever the length of the span and whatever the track holds.  Two calls write identical bytes.
+ * ---------------------------------------------------------------------------------------------- */
+/* frames per workgroup of the prepare passes, and the frames under a node of tree level 11 (the tests place their edges from it) */
+int32_t lad_span_stats_tile_frames(void);
+/* bytes of workspace for lad_span_stats_prepare / lad_span_stats; needs no GPU.  -1 and lad_last_error() for channels outside
+ * 1..65535 or frames outside 1..2^30. */
+int64_t lad_span_stats_workspace_bytes(int64_t channels, int64_t frames);
+/* probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype).  workspace: DEVICE,
+ * lad_span_stats_workspace_bytes.  LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for a null
+ * pointer, an unknown dtype, sizes out of range or probs overlapping the workspace.  The track is only read. */
+int lad_span_stats_prepare(const void *probs, int32_t dtype, int64_t channels, int64_t frames, void *workspace, void *stream);
+/* probs, dtype, channels, frames, workspace: as given to lad_span_stats_prepare, which has run on this stream or has finished.
+ * table: DEVICE int32 [total][2], the tables of the channels * n_settings (channel, setting) pairs back to back in
+ * c * n_settings + k order; counts_host: HOST int32[channels * n_settings], their row counts (as lad_score_runs takes them).
+ * sums: DEVICE int64[total]; peaks: DEVICE int32[total]; peak_values: DEVICE double[total]: one entry per row, nothing beyond
+ * row total - 1 is written.  The last channels + 1 int64 of the workspace take the first row of every channel for the launch:
+ * calls that share a workspace are ordered by their stream; everything else is only read.  A total of zero rows is LAD_OK with
+ * nothing launched.  LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for a null pointer (table
+ * may be NULL for zero rows), an unknown dtype, sizes out of range (n_settings < 1 included), a negative count, or an output
+ * overlapping probs, the table, the workspace or another output. */
+int lad_span_stats(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const void *workspace, const int32_t *table,
+                   const int32_t *counts_host, int32_t n_settings, int64_t *sums, int32_t *peaks, double *peak_values,
+                   void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Redrawing the segment table (csrc/sample.hip): which frames of which channel form each training example, drawn afresh for
  * every epoch from regions and pools of regions.  Replaces, on the device, the sampling of the reference's create_data_df.py
  * (get_subsample :84-95, get_random_segment_from_df :65-81, the rejection loops of get_random_non_laughter_segment :32-63) and

@@ -224,6 +224,12 @@ SIGNATURES = {
     "lad_rank_filter_max_window": (c_i32, []),
     "lad_rank_filter_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "lad_rank_filter": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64), c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    # confidence of an instance: sum and earliest peak of the track over every span (csrc/spanstats.hip)
+    "lad_span_stats_tile_frames": (c_i32, []),
+    "lad_span_stats_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "lad_span_stats_prepare": (c_int, [c_void_p, c_i32, c_i64, c_i64, c_void_p, c_void_p]),
+    "lad_span_stats": (c_int, [c_void_p, c_i32, c_i64, c_i64, c_void_p, c_void_p, ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     # redrawing the segment table, transcript coverage of windows (csrc/sample.hip)
     "lad_sample_segments": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i32,
                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),

@@ -22,6 +22,10 @@ fill; sweep_eval's scorers read the tables where they lie).  `decoder_for` picks
 functions -- get_laughter_* (THRESHOLD), binarize_* (HYSTERESIS), viterbi_* (VITERBI), each as `*_frame_spans` and `*_instances`,
 on the host and as `*_device` for a track in GPU memory -- are wrappers.  A device form returns what its host form returns, bit for
 bit; only the compact tables cross to the host; there is no CPU fallback.  torch and _hip are imported by the device forms only.
+
+Every `*_instances` form takes stats=True and then also says how sure each instance is: mean probability, time of the peak and probability
+at the peak (`span_stats`, `confidences`; csrc/spanstats.hip for a track in GPU memory; the convention is written out above
+lad_span_stats in include/lad_hip.h).  It reads spans only, so it is written once, in `_instances` / `_device_frame_spans`.
 """
 import math
 import ctypes
@@ -156,6 +160,51 @@ def format_outputs(instances, wav_paths=None):
     return outs
 
 
+# ---- confidence of an instance (include/lad_hip.h: lad_span_stats has the convention) --------------------------------------------
+def span_stats(probs, spans):
+    """(sums int64 (n,), peaks int64 (n,), peak_values float64 (n,)) of the int64 (n, 2) spans (first_frame, last_frame) of a 1-D
+    track: w = the decoders' frame value (fix_probs), 0.0 for a NaN frame; sum = the int64 sum of rint(w * 2^32) over the span;
+    peak = the earliest frame of the span at which w is largest, peak_value = w there.  A span with first < 0, last >= frames or
+    first > last reads nothing: (0, -1, 0.0).  Not in the reference.  Host parity form of csrc/spanstats.hip: a cumulative sum, and
+    one argmax per span of more than one frame."""
+    w = fix_probs(probs)
+    if w.ndim != 1:
+        raise ValueError(f"the track is 1-D, got shape {w.shape}")
+    w[np.isnan(w)] = 0.0
+    spans = np.asarray(spans, dtype=np.int64).reshape(-1, 2)
+    first, last = spans[:, 0], spans[:, 1]
+    ok = (first >= 0) & (last < len(w)) & (first <= last)
+    cum = np.concatenate([[0], np.cumsum(np.rint(w * 4294967296.0).astype(np.int64))])
+    sums, peaks, values = np.zeros(len(spans), np.int64), np.full(len(spans), -1, np.int64), np.zeros(len(spans), np.float64)
+    sums[ok] = cum[last[ok] + 1] - cum[first[ok]]
+    peaks[ok] = first[ok]                                   # (a span of one frame)
+    for i in np.flatnonzero(ok & (last > first)):
+        peaks[i] = first[i] + np.argmax(w[first[i]:last[i] + 1])        # (the first of equal maxima)
+    values[ok] = w[peaks[ok]]
+    return sums, peaks, values
+
+
+def span_stats_device(probs, table, counts):
+    """`span_stats` for a (T,) or (C, T) float32 / float64 track in GPU memory and span tables that lie there too (csrc/spanstats.hip
+    through spanstats.py): table int32 (total, 2), the tables back to back in c * K + k order, counts their row counts, as
+    _device_tables returns them.  The same three arrays, one entry per row, bit for bit.  No CPU fallback."""
+    import spanstats
+    return spanstats.span_stats_device(probs, table, counts)
+
+
+def confidences(sums, peaks, peak_values, spans, fps):
+    """float64 (n, 3): (mean, peak_time, peak_value) per span from the integers of span_stats: n = last - first + 1, mean =
+    float64(sum) / float64(n * 2^32), one IEEE division; peak_time = peak / fps, as a span's start is computed.  A row that
+    span_stats refused (peak -1) has mean 0.0."""
+    spans = np.asarray(spans, dtype=np.int64).reshape(-1, 2)
+    n = np.where(np.asarray(peaks) >= 0, spans[:, 1] - spans[:, 0] + 1, 1)
+    out = np.empty((len(spans), 3), np.float64)
+    out[:, 0] = np.asarray(sums, dtype=np.int64).astype(np.float64) / (n << 32).astype(np.float64)
+    out[:, 1] = np.asarray(peaks, dtype=np.int64) / fps
+    out[:, 2] = peak_values
+    return out
+
+
 # ---- what the decoders share -----------------------------------------------------------------------------------------------------
 class Decoder(NamedTuple):
     """One way from a probability track to spans.  `ctx` is the dictionary of what a call prepares once: "fps_host" (float64 numpy
@@ -228,17 +277,21 @@ def _table(total, device, n=None):
     return torch.empty((max(total, 1), 2) if n is None else (n, max(total, 1), 2), dtype=torch.int32, device=device)
 
 
-def _instances_from_spans(keys, spans_list, min_lengths, fps):
+def _instances_from_spans(keys, spans_list, min_lengths, fps, stats_list=None):
     """{(*key, min_length): [(start_s, end_s), ...]}, keys-major: first / fps, last / fps and end - start > min_length in float64
-    (the arithmetic of the reference's Python floats) on the integer spans of each key."""
-    instance_dict = {}
-    for key, spans in zip(keys, spans_list):
+    (the arithmetic of the reference's Python floats) on the integer spans of each key.  stats_list (the span_stats triple of
+    each key's spans): -> (that dictionary, {same key: float64 (n, 3) `confidences` of exactly its instances, in their order})."""
+    instance_dict, stats_dict = {}, {}
+    for i, (key, spans) in enumerate(zip(keys, spans_list)):
         starts, ends = spans[:, 0] / fps, spans[:, 1] / fps
         length = ends - starts
+        conf = confidences(*stats_list[i], spans, fps) if stats_list is not None else None
         for min_l in min_lengths:
             keep = length > min_l
             instance_dict[(*key, min_l)] = list(zip(starts[keep].tolist(), ends[keep].tolist()))
-    return instance_dict
+            if conf is not None:
+                stats_dict[(*key, min_l)] = conf[keep]
+    return instance_dict if stats_list is None else (instance_dict, stats_dict)
 
 
 # ---- THRESHOLD: the reference's frame-by-frame rule (include/lad_hip.h: lad_runs_count) ------------------------------------------
@@ -505,52 +558,71 @@ def _device_run_tables(probs, thresholds):
 def _device_frame_spans(decoder, probs, settings, ctx):
     """[int64 (n, 2) array per setting] for a (T,) tensor, one such list per channel for a (C, T) one: the tables of
     _device_tables on the host, in rounds of at most decoder.round_size settings.  ctx["fps"], if there: one value or one per
-    channel."""
+    channel.  ctx["want_stats"]: ctx["stats"] becomes the span_stats triple of every one of those arrays, in the same nesting:
+    lad_span_stats_prepare once per call, lad_span_stats on every round's table while it lies on the device (csrc/spanstats.hip)."""
     import _hip
     probs, dtype, single = device_track(probs, decoder.what)
     C, T = probs.shape
+    want_stats = bool(ctx.get("want_stats"))
     if "fps" in ctx:
         ctx["fps_host"] = fps_per_channel(ctx["fps"], C)
     if T == 0 or C == 0 or not settings:
         out = [[np.zeros((0, 2), np.int64) for _ in settings] for _ in range(C)]
+        stats = [[(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)) for _ in settings] for _ in range(C)]
     else:
-        out = [[] for _ in range(C)]
+        out, stats = [[] for _ in range(C)], [[] for _ in range(C)]
+        if want_stats:
+            import spanstats
+            stats_ws = spanstats.prepare_device(probs, dtype)
         step = decoder.round_size(_hip.lib(), len(settings))
         for k0 in range(0, len(settings), step):
             _, table, counts, _ = _device_tables(decoder, probs, dtype, settings[k0:k0 + step], ctx)
+            if want_stats:
+                triple = spanstats.to_host(*spanstats.stats_device(probs, dtype, stats_ws, table, counts))
             rows, edges = table.cpu().numpy(), np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
             for i in range(len(counts)):                # the tables lie back to back in c * K + k order
                 out[i // (len(counts) // C)].append(rows[edges[i]:edges[i + 1]].astype(np.int64))
+                if want_stats:
+                    stats[i // (len(counts) // C)].append(tuple(a[edges[i]:edges[i + 1]] for a in triple))
+    if want_stats:
+        ctx["stats"] = stats[0] if single else stats
     return out[0] if single else out
 
 
-def _instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device, table=None):
+def _instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device, table=None, stats=False):
     """{(threshold, *axis values, min_length): [(start_s, end_s), ...]}, thresholds-major, then the axes in their order, then
     min_length: the decoder's spans as (first / fps, last / fps), kept iff end - start > min_length.  device: probs is a (T,) track
-    in GPU memory and the spans come from there; the seconds and the filter are evaluated on the host either way."""
+    in GPU memory and the spans come from there; the seconds and the filter are evaluated on the host either way.  stats: ->
+    (that dictionary, {same key: float64 (n, 3) array (mean, peak_time, peak_value) of exactly its instances, in their order}), the
+    integers from span_stats on the host or from csrc/spanstats.hip on the device (`confidences` either way); without it nothing
+    of that runs."""
     if device and getattr(probs, "ndim", None) != 1:
         import _hip
         raise _hip.LadHipError(f"probs must be a (T,) GPU tensor (the device {decoder.what} has no CPU fallback)")
-    ctx = {"table": table}
+    ctx = {"table": table, "want_stats": bool(stats)}
     keys, settings = decoder.keys(list(thresholds), [list(values) for values in axis_values], ctx)
     min_lengths = list(min_lengths)
     if decoder is not THRESHOLD:            # (the reference's own sweep takes fps as it comes)
         fps = ctx["fps"] = np.float64(_check_fps(fps))
     spans = _device_frame_spans(decoder, probs, settings, ctx) if device else decoder.host_spans(probs, settings, fps, ctx)
-    return _instances_from_spans(keys, spans, min_lengths, fps)
+    if not stats:
+        return _instances_from_spans(keys, spans, min_lengths, fps)
+    return _instances_from_spans(keys, spans, min_lengths, fps, ctx["stats"] if device else [span_stats(probs, s) for s in spans])
 
 
 # ---- the public forms ------------------------------------------------------------------------------------------------------------
-def get_laughter_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+def get_laughter_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., stats=False):
     """{(threshold, min_length): [(start_s, end_s), ...]} exactly as laugh_segmenter.py:74-111: frame i is laughter iff
     p[i] > threshold; maximal runs -> (first/fps, last/fps); kept iff end - start > min_length.  Keys thresholds-major, as the
-    reference iterates."""
-    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=False)
+    reference iterates.  stats=True (not in the reference; here and in the five forms below): -> (that dictionary, {same key:
+    float64 (n, 3) array of (mean probability, time of the peak, probability at the peak) of exactly its instances, in their
+    order}) -- see span_stats and confidences."""
+    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=False, stats=stats)
 
 
-def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100.):
+def get_laughter_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., stats=False):
     """get_laughter_instances for a (T,) track in GPU memory: the same dictionary (keys, thresholds-major order, Python floats)."""
-    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=True)
+    return _instances(THRESHOLD, probs, thresholds, min_lengths, fps, (), device=True, stats=stats)
 
 
 def get_laughter_frame_spans(probs, threshold):
@@ -580,17 +652,17 @@ def binarize_frame_spans_device(probs, settings, fps=100.):
     return _device_frame_spans(HYSTERESIS, probs, [_check_setting(*s) for s in settings], {"fps": fps})
 
 
-def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+def binarize_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0], stats=False):
     """{(threshold, offset_drop, min_gap, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then drop, then gap, then
     min_length.  The onset is the threshold and the offset is threshold - offset_drop (drop >= 0); events are (first / fps,
     last / fps) and kept iff end - start > min_length, after gap filling.  drop = 0 and gap = 0 give the lists of
     get_laughter_instances."""
-    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=False)
+    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=False, stats=stats)
 
 
-def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0]):
+def binarize_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., offset_drops=[0.0], min_gaps=[0.0], stats=False):
     """binarize_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
-    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=True)
+    return _instances(HYSTERESIS, probs, thresholds, min_lengths, fps, (offset_drops, min_gaps), device=True, stats=stats)
 
 
 def viterbi_frame_spans(probs, threshold, penalty, table=None, unit=1024):
@@ -610,12 +682,12 @@ def viterbi_frame_spans_device(probs, settings, table=None):
     return _device_frame_spans(VITERBI, probs, _check_viterbi_settings(settings), ctx)
 
 
-def viterbi_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
+def viterbi_instances(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None, stats=False):
     """{(threshold, penalty, min_length): [(start_s, end_s), ...]}, keys thresholds-major, then penalty, then min_length: the runs of
     the decoded path as (first / fps, last / fps), kept iff end - start > min_length.  Host form (see viterbi_frame_spans)."""
-    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=False, table=table)
+    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=False, table=table, stats=stats)
 
 
-def viterbi_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None):
+def viterbi_instances_device(probs, thresholds=[0.5], min_lengths=[0.2], fps=100., penalties=[0.0], table=None, stats=False):
     """viterbi_instances for a (T,) track in GPU memory: the same dictionary (keys, order, Python floats)."""
-    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=True, table=table)
+    return _instances(VITERBI, probs, thresholds, min_lengths, fps, (penalties,), device=True, table=table, stats=stats)

@@ -36,6 +36,13 @@ csrc/binarize.hip under `--segmenter device`): the instances of setting (thr, dr
 `--penalties` (default: absent) cuts the track with the two-state Viterbi decoder instead (laugh_segmenter.viterbi_instances, or
 csrc/viterbi.hip under `--segmenter device`): log-odds relative to the threshold, a penalty in nats per instance.  The instances of
 setting (thr, penalty, min_len) go to `t_<thr>/l_<min_len>/p_<penalty>/`.  It cannot be combined with the two flags above.
+
+`--confidence True` (default: off; not in the reference) writes `<file>.confidence.csv` next to every TextGrid: one line per
+instance, `start,end,mean_prob,peak_time,peak_prob` (laugh_segmenter.span_stats / confidences, or csrc/spanstats.hip under
+`--segmenter device`: the same integers, so the same bytes).  `--min_confidence X` drops the instances whose mean probability is
+below X before anything is printed, cut or written.  Both work with either segmenter and every decoder; with `--lowpass` or
+`--median` the figures are those of the smoothed track, the one the instances were cut from.  Without the two flags paths and bytes
+are what they were; the TextGrid format never changes.
 """
 import argparse
 import os
@@ -119,9 +126,18 @@ def save_audio_instances(instances, audio_path, output_dir, rate=None):
     return paths
 
 
+def write_confidence_csv(path, instances, conf):
+    """start,end,mean_prob,peak_time,peak_prob: one line per instance, floats as repr (conf: the (n, 3) array of the instances)."""
+    with open(path, "w") as f:
+        f.write("start,end,mean_prob,peak_time,peak_prob\n")
+        for (start, end), row in zip(instances, conf.tolist()):
+            f.write(",".join(repr(float(v)) for v in (start, end, *row)) + "\n")
+
+
 def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
-                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None, median=None):
+                  save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None, median=None, confidence=False,
+                  min_confidence=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
@@ -129,7 +145,10 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     the host or on the device like the sweep itself; save_probs still gets the raw track.  median: a window in frames (odd,
     1..1023): the track goes through the median filter instead (laugh_segmenter.median_filter / median_filter_device); not both.
     offset_drops / min_gaps (either given): hysteresis and gap filling; the dictionary's keys are (thr, drop, gap, min_len).
-    penalties: the Viterbi decoder; the dictionary's keys are (thr, penalty, min_len).  Not together with the two above."""
+    penalties: the Viterbi decoder; the dictionary's keys are (thr, penalty, min_len).  Not together with the two above.
+    confidence: also write <file>.confidence.csv next to every TextGrid (start,end,mean_prob,peak_time,peak_prob per instance, of
+    the track the instances were cut from: the smoothed one under lowpass / median).  min_confidence: instances whose mean
+    probability lies below it are dropped from the dictionary and from everything printed, cut or written."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if lowpass is not None and median is not None:
@@ -153,8 +172,18 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
         probs = laugh_segmenter.median_filter(probs, median) if segmenter == "host" else \
             laugh_segmenter.median_filter_device(probs, median)
     decoder, axis_values = laugh_segmenter.decoder_for(offset_drops, min_gaps, penalties)
+    want_stats = bool(confidence) or min_confidence is not None
+    stats_dict = {}
     if segmenter == "host" or rank == 0:
-        instance_dict = laugh_segmenter._instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device=segmenter == "device")
+        instance_dict = laugh_segmenter._instances(decoder, probs, thresholds, min_lengths, fps, axis_values, device=segmenter == "device",
+                                                   stats=want_stats)
+        if want_stats:
+            instance_dict, stats_dict = instance_dict
+        if min_confidence is not None:
+            for setting, conf in stats_dict.items():
+                keep = ~(conf[:, 0] < min_confidence)
+                instance_dict[setting] = [inst for inst, k in zip(instance_dict[setting], keep) if k]
+                stats_dict[setting] = conf[keep]
     else:
         instance_dict = {}
     sweep_time = time.time() - start_time - predict_time
@@ -163,15 +192,17 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
             if verbose:
                 print(decoder.found_line(len(instances), setting))
             out_dir = os.path.join(output_dir or '.', f't_{setting[0]}', f'l_{setting[-1]}', *decoder.dir_suffix(setting))
-            if save_to_textgrid or (save_to_audio_files and len(instances) > 0):
+            if save_to_textgrid or confidence or (save_to_audio_files and len(instances) > 0):
                 os.makedirs(out_dir, exist_ok=True)
             if save_to_audio_files and len(instances) > 0:
                 wav_paths = save_audio_instances(instances, audio_path, out_dir, rate=save_audio_rate)
                 if verbose:
                     print(laugh_segmenter.format_outputs(instances, wav_paths))   # segment_laughter.py:148
+            fname = os.path.splitext(os.path.basename(audio_path))[0]
             if save_to_textgrid:
-                fname = os.path.splitext(os.path.basename(audio_path))[0]
                 textgrid.write_laughter_textgrid(os.path.join(out_dir, fname + '.TextGrid'), instances, xmax=file_length)
+            if confidence:
+                write_confidence_csv(os.path.join(out_dir, fname + '.confidence.csv'), instances, stats_dict[setting])
     time_taken = time.time() - start_time
     if rank == 0:
         print(f'Completed in: {time_taken:.2f}s  (real-time factor of the whole script {time_taken / file_length:.2e} at '
@@ -216,6 +247,13 @@ def build_parser():
     parser.add_argument('--penalties', type=float_list, default=None,
                         help="(not in the reference) comma-separated list of nats: two-state Viterbi decoding of the track, a frame "
                              "counting its log-odds relative to the threshold and every instance costing this much; default: absent")
+    parser.add_argument('--confidence', type=str, default='False',
+                        help="(not in the reference) 'True': write <file>.confidence.csv next to every TextGrid, one line per instance: "
+                             "start,end,mean_prob,peak_time,peak_prob; with --lowpass or --median the figures are those of the smoothed "
+                             "track, the one the instances were cut from; default: off")
+    parser.add_argument('--min_confidence', type=float, default=None, metavar='X',
+                        help="(not in the reference) drop the instances whose mean probability is below X before anything is printed, cut "
+                             "or written (of the smoothed track under --lowpass or --median); default: absent")
     parser.add_argument('--resample', type=str, default='False',
                         help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
                              "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
@@ -248,7 +286,7 @@ def main(argv=None):
                   precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
                   segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
                   lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties,
-                  median=args.median)
+                  median=args.median, confidence=args.confidence.lower() in truthy, min_confidence=args.min_confidence)
 
 
 if __name__ == '__main__':
