@@ -6,6 +6,7 @@ PyTorch is used only for device memory and streams (tensor.data_ptr(), current s
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -276,6 +277,49 @@ def require_cuda(t, name="tensor", dtype=None):
     if dtype is not None and t.dtype != dtype:
         raise LadHipError(f"{name} must have dtype {dtype}, got {t.dtype}")
     return t
+
+
+def device_track(probs, what="sweep"):
+    """What every device form asks of its probability tensor: (T,) or (C, T), in GPU memory, contiguous, float32 or float64.
+    Returns (the (C, T) tensor, its lad_runs_dtype, whether it was a (T,) one)."""
+    single = getattr(probs, "ndim", None) == 1
+    if single and hasattr(probs, "unsqueeze"):
+        probs = probs.unsqueeze(0)
+    if getattr(probs, "ndim", None) != 2:
+        raise LadHipError(f"probs must be a (T,) or (C, T) GPU tensor (the device {what} has no CPU fallback)")
+    require_cuda(probs, "probs")
+    if probs.dtype not in (torch.float32, torch.float64):
+        raise LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
+    return probs, 0 if probs.dtype == torch.float32 else 1, single
+
+
+def channel_lengths(lengths, C):
+    """lengths= of a filter: None, or the frame counts of the C channels as a contiguous int64 array."""
+    if lengths is None:
+        return None
+    lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    if lengths.shape != (C,):
+        raise ValueError(f"{lengths.size} lengths for {C} channels")
+    return lengths
+
+
+def out_track(out, probs, single, dtype):
+    """out= of a filter as the (C, T) tensor it writes into: a new one of `dtype`, or the caller's, which must be a contiguous GPU
+    tensor of that dtype with the shape ((T,) if `single`) and device of the track.  probs: the (C, T) tensor of device_track."""
+    if out is None:
+        return torch.empty(probs.shape, dtype=dtype, device=probs.device)
+    require_cuda(out, "out", dtype)
+    if out.shape != (probs.shape[1:] if single else probs.shape) or out.device != probs.device:
+        raise ValueError("out must have the shape and device of probs")
+    return out.unsqueeze(0) if single else out
+
+
+def workspace(query_name, *sizes, device):
+    """The workspace of an entry point: a uint8 GPU tensor of as many bytes as its size query asks for these sizes (LadHipError
+    with the library's message for sizes the query refuses)."""
+    n_bytes = getattr(lib(), query_name)(*sizes)
+    check(0 if n_bytes >= 0 else LAD_ERR_INVALID, query_name)
+    return torch.empty(n_bytes, dtype=torch.uint8, device=device)
 
 
 def ptr(t):

@@ -15,8 +15,9 @@
 //                          first_row[g] .. first_row[g + 1] of that table; cov, frag, first a and last b per min_length in
 //                          registers; the other six fields
 // Both sum with a butterfly over the lanes of the wave that share (c, k) and one vector global atomic add on int64 per
-// (min_length, field): integer sums, the same bytes whatever order the waves arrive in.  Every index read is clamped to the index,
-// every row read to the caller's row count.
+// (min_length, field) (lad_sweep_tile.h: add_group, as score.hip): integer sums, the same bytes whatever order the waves arrive in.
+// Every index read is clamped to the index, every row read to the caller's row count.  The checks of the entry point are
+// check_scorer's, shared with lad_score_runs.
 #pragma clang fp contract(off)
 #include "lad_sweep_tile.h"
 
@@ -29,24 +30,6 @@ __global__ __launch_bounds__(THREADS) void events_scan_kernel(const int32_t *__r
                                                               const int32_t *__restrict__ counts, int64_t CK,
                                                               int64_t *__restrict__ first_row) {
     scan_index_and_counts(bounds, offsets, n_intervals, cum, segments, counts, CK, first_row);
-}
-
-// v[l * FIELDS + f] of the lanes `in` of a wave that share table g -> events[g][l][f], one lane per sum
-template <typename Value>
-__device__ inline void add_group(bool in, long long g, int64_t CK, int L, int lane, Value value, unsigned long long *__restrict__ events) {
-    long long mine = 0;
-#pragma unroll
-    for (int l = 0; l < MAX_L; ++l) {
-        if (l < L) {
-#pragma unroll
-            for (int f = 0; f < FIELDS; ++f) {
-                if (!value.has(f)) continue;
-                const long long s = wave_sum64(in ? value(l, f) : 0ll);
-                if (lane == l * FIELDS + f) mine = s;
-            }
-        }
-    }
-    if (lane < L * FIELDS && mine != 0 && g >= 0 && g < CK) atomicAdd(events + (g * L * FIELDS + lane), (unsigned long long)mine);
 }
 
 struct PredHit {
@@ -88,7 +71,7 @@ __global__ __launch_bounds__(THREADS) void events_prepare_kernel(const int32_t *
         const int leader = __ffsll((long long)todo) - 1;
         const long long gl = __shfl(g, leader, WAVE);
         const bool in = valid && g == gl;
-        add_group(in, gl, CK, L, lane, p, events);
+        add_group<FIELDS>(in, gl, CK, L, lane, p, events);
         todo &= ~__ballot(in);
     }
 }
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(THREADS) void events_match_kernel(const int32_t *__
         const int leader = __ffsll((long long)todo) - 1;
         const long long gl = __shfl(g, leader, WAVE);
         const bool in = valid && g == gl;
-        add_group(in, gl, CK, L, lane, s, events);
+        add_group<FIELDS>(in, gl, CK, L, lane, s, events);
         todo &= ~__ballot(in);
     }
 }
@@ -203,29 +186,15 @@ extern "C" int lad_score_events(const void *runs_workspace, const int32_t *table
                                 const double *fps_host, const double *min_lengths, int32_t n_min_lengths, int32_t min_overlap_ms,
                                 int32_t min_overlap_pct, void *workspace, int64_t *events, void *stream) {
     using namespace lad;
-    LAD_REQUIRE(score_sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths) && frames >= 1 && frames <= MAX_T,
-                "lad_score_events: channels 1..%d, frames 1..2^30, intervals 0..2^30, thresholds 1..%d, min_lengths 1..%d "
-                "(got %lld, %lld, %lld, %d, %d)",
-                MAX_C, MAX_K, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_thresholds, n_min_lengths);
-    LAD_REQUIRE(min_overlap_ms >= 0 && min_overlap_pct >= 0 && min_overlap_pct <= 100,
-                "lad_score_events: min_overlap_ms >= 0, min_overlap_pct 0..100 (got %d, %d)", min_overlap_ms, min_overlap_pct);
-    LAD_REQUIRE(runs_workspace && counts_host && offsets && offsets_host && fps && fps_host && min_lengths && workspace && events,
-                "lad_score_events: null buffer");
-    LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "lad_score_events: null interval bounds");
     const int K = n_thresholds, L = n_min_lengths;
     const int64_t CK = channels * K;
+    const int32_t criteria[2] = {min_overlap_ms, min_overlap_pct};
     MinLengths ml;
-    if (int rc = load_min_lengths("lad_score_events", min_lengths, L, ml)) return rc;
-    if (int rc = check_index("lad_score_events", channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
-    const int64_t rows = total_runs("lad_score_events", counts_host, CK, frames);
-    if (rows < 0) return LAD_ERR_INVALID;
-    LAD_REQUIRE(rows <= MAX_ROWS, "lad_score_events: %lld run-table rows, at most 2^38 per call", (long long)rows);
-    LAD_REQUIRE(rows == 0 || table, "lad_score_events: null table");
-    int64_t most_events = 0;      // of one channel: grid.x of the match kernel
-    for (int64_t c = 0; c < channels; ++c) {
-        const int64_t n = offsets_host[c * CLASSES + LAD_SCORE_LAUGH + 1] - offsets_host[c * CLASSES + LAD_SCORE_LAUGH];
-        most_events = n > most_events ? n : most_events;
-    }
+    int64_t rows;
+    if (int rc = check_scorer("lad_score_events", criteria, runs_workspace, table, counts_host, channels, frames, K, bounds, offsets,
+                              bounds_host, offsets_host, n_intervals, fps, fps_host, min_lengths, L, workspace, events, ml, rows))
+        return rc;
+    const int64_t most_events = most_events_of(offsets_host, channels);      // grid.x of the match kernel
 
     int64_t *first_row = (int64_t *)workspace;
     int32_t *cum = (int32_t *)((char *)workspace + up256(CK * 8));

@@ -1,6 +1,10 @@
 // What the dense sweep's sources share (surface.hip, surface_events.hip): the bins of a track, the binary tree of minima over them,
-// the two nearest-smaller searches in it, the scan of the interval index, the size checks, and the host driver of the four launches
-// that build all of this.  Each source gets its own copy of the kernels below (anonymous namespace).
+// the two nearest-smaller searches in it, the scan of the interval index, the body of the nodes kernel (score_nodes: templated on
+// the fields of the difference array and on what fills those behind run_fields' seven), the prefix sum over the levels
+// (prefix_levels), the workspace (Workspace, layout, workspace_bytes), and the host half of an entry point up to and including the
+// nodes launch (sweep_nodes: the checks, the carving, the memset, build_trees' four launches, the decision between LDS and global
+// adds).  Each source gets its own copy of the kernels below (anonymous namespace) and keeps a __global__ of its own name around
+// each shared body.
 //
 // Frame value and comparison are lad_runs_count's: q = load_fixed(p) in float64, frame i is on at level j iff q > levels[j], i.e.
 // iff j < bin[i], bin[i] = the number of levels strictly below q (0 for NaN and beyond the track).
@@ -25,6 +29,7 @@ constexpr int CHUNK = 1 << CHUNK_BITS;           // frames per workgroup: lad_su
 constexpr int TREE_LEVELS = 1 + 3 * CHUNK_BITS;  // levels 0..33 are written; a search never leaves level ceil(log2 T) <= 30
 typedef unsigned short bin_t;                    // 0..4096
 constexpr bin_t ABSENT = 0xffff;                 // beyond a level's last node: never a minimum
+constexpr int MAX_PRIVATE_BYTES = 48 * 1024;     // the difference array of one channel in LDS, if it fits
 
 // nodes of level h, and the entries a level occupies in a channel's tree (at least its nodes, whatever T)
 __host__ __device__ inline int64_t nodes_at(int64_t T, int h) { return (T + ((int64_t)1 << h) - 1) >> h; }
@@ -161,13 +166,113 @@ __device__ inline int64_t nearest_right_lt(const bin_t *__restrict__ tree, int64
     return p;
 }
 
+// The body of a nodes kernel, one lane per frame: the two searches, run_fields for a representative, the fields behind its seven
+// from extra(first, last, fps, ml, L, v) (FIELDS in all), then +w at row base and -w at row top of the difference array per kept
+// min_length: into a copy of the channel's array in LDS when the host found that it fits (use_lds), flushed with one vector global
+// atomic per non-zero cell; straight to global memory otherwise.
+template <int FIELDS, typename Extra>
+__device__ inline void score_nodes(const bin_t *__restrict__ trees, int64_t tree_pitch, int64_t T, int K, const double *__restrict__ fps,
+                                   const MinLengths &ml, int L, const int32_t *__restrict__ bounds, const int32_t *__restrict__ cum,
+                                   const int32_t *__restrict__ offsets, int64_t n_intervals, int use_lds,
+                                   unsigned long long *__restrict__ diff, Extra extra) {
+    extern __shared__ unsigned long long priv[];
+    const int64_t c = blockIdx.y;
+    const bin_t *tree = trees + c * tree_pitch;
+    const int cells = (K + 1) * L * FIELDS;
+    unsigned long long *mine = diff + c * cells;
+    if (use_lds) {
+        for (int i = threadIdx.x; i < cells; i += THREADS) priv[i] = 0;
+        __syncthreads();
+    }
+    const double f = fps[c];
+    const int64_t chunk0 = (int64_t)blockIdx.x * CHUNK;
+    for (int j = threadIdx.x; j < CHUNK; j += THREADS) {
+        const int64_t i = chunk0 + j;
+        if (i >= T) break;
+        const int top = tree[i];
+        if (top == 0 || top > K) continue;
+        int lb, rb;
+        const int64_t left = nearest_left_le(tree, T, i, top, lb);
+        if (left >= 0 && lb == top) continue;        // an equal bin further left in the same interval: that frame speaks for it
+        const int64_t right = nearest_right_lt(tree, T, i, top, rb);
+        const int base = lb > rb ? lb : rb;
+        if (base >= top) continue;                   // (cannot happen: both neighbours are smaller)
+        int32_t v[FIELDS], time[SCORE_FIELDS];
+        const int32_t first = (int32_t)(left + 1), last = (int32_t)(right - 1);
+        const unsigned keep = run_fields(c, first, last, f, ml, L, bounds, cum, offsets, n_intervals, time);
+#pragma unroll
+        for (int fd = 0; fd < SCORE_FIELDS; ++fd) v[fd] = time[fd];
+        extra(first, last, f, ml, L, v);
+#pragma unroll
+        for (int l = 0; l < MAX_L; ++l) {
+            if (l < L && ((keep >> l) & 1u)) {
+#pragma unroll
+                for (int fd = 0; fd < FIELDS; ++fd) {
+                    if (v[fd] != 0) {
+                        const unsigned long long w = (unsigned long long)(long long)v[fd];
+                        const int up = (base * L + l) * FIELDS + fd, down = (top * L + l) * FIELDS + fd;
+                        if (use_lds) {
+                            atomicAdd(priv + up, w);
+                            atomicAdd(priv + down, 0ull - w);
+                        } else {
+                            atomicAdd(mine + up, w);
+                            atomicAdd(mine + down, 0ull - w);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < cells; i += THREADS) {
+            const unsigned long long w = priv[i];
+            if (w != 0) atomicAdd(mine + i, w);
+        }
+    }
+}
+
+// one workgroup, one (channel, min_length, field): out[j * out_step] = the sum of in[0 .. j] (in_step apart), j < K: block_scan
+// over the levels.  Row K of a difference array is never read.
+__device__ inline void prefix_levels(const long long *__restrict__ in, int64_t in_step, long long *__restrict__ out, int64_t out_step,
+                                     int K) {
+    block_scan<long long>(0, K, [&](int64_t j) { return in[j * in_step]; },
+                          [&](int64_t j, long long v) { out[j * out_step] = v + in[j * in_step]; });
+}
+
 inline bool surface_sizes_ok(int64_t C, int64_t T, int64_t n_intervals, int64_t K, int64_t L) {
     return C >= 1 && C <= MAX_C && T >= 1 && T <= MAX_T && n_intervals >= 0 && n_intervals <= MAX_INTERVALS && K >= 1 &&
            K <= MAX_LEVELS && L >= 1 && L <= MAX_L;
 }
-#define SURFACE_SIZES_MESSAGE(who)                                                                                                 \
-    who ": channels 1..%d, frames 1..2^30, intervals 0..2^30, levels 1..%d, min_lengths 1..%d (got %lld, %lld, %lld, %d, %d)", MAX_C, \
-        MAX_LEVELS, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_levels, n_min_lengths
+inline int fail_sizes(const char *who, int64_t channels, int64_t frames, int64_t n_intervals, int32_t n_levels, int32_t n_min_lengths) {
+    return fail(LAD_ERR_INVALID,
+                "%s: channels 1..%d, frames 1..2^30, intervals 0..2^30, levels 1..%d, min_lengths 1..%d (got %lld, %lld, %lld, %d, %d)", who,
+                MAX_C, MAX_LEVELS, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_levels, n_min_lengths);
+}
+
+// the workspace of a call whose difference array has `fields` fields per (level, min_length): byte offsets of its parts
+struct Workspace {
+    int64_t levels, cum, diff, trees, tree_pitch, bytes;
+};
+inline Workspace layout(int64_t C, int64_t T, int64_t n_intervals, int64_t K, int64_t L, int fields) {   // sizes surface_sizes_ok has passed
+    Workspace w;
+    w.levels = 0;
+    w.cum = up256(K * 8);
+    w.diff = w.cum + up256(n_intervals * 4);
+    w.trees = w.diff + up256(C * (K + 1) * L * fields * 8);
+    w.tree_pitch = tree_pitch_of(T);
+    w.bytes = w.trees + C * w.tree_pitch * (int64_t)sizeof(bin_t) + 256;
+    return w;
+}
+// the two *_workspace_bytes queries: -1 (reported) for sizes out of range
+inline int64_t workspace_bytes(const char *who, int64_t channels, int64_t frames, int64_t n_intervals, int32_t n_levels,
+                               int32_t n_min_lengths, int fields) {
+    if (!surface_sizes_ok(channels, frames, n_intervals, n_levels, n_min_lengths)) {
+        fail_sizes(who, channels, frames, n_intervals, n_levels, n_min_lengths);
+        return -1;
+    }
+    return layout(channels, frames, n_intervals, n_levels, n_min_lengths, fields).bytes;
+}
 
 // what both entry points ask of their levels before anything is launched
 inline int check_levels(const char *who, const double *levels, int K) {
@@ -200,6 +305,59 @@ inline int build_trees(const void *probs, int32_t dtype, int64_t channels, int64
     const int64_t segments = channels * CLASSES;
     hipLaunchKernelGGL(surface_cum_kernel, dim3((unsigned)segments), dim3(THREADS), 0, st, bounds, offsets, n_intervals, cum, segments);
     return check_launch("surface_cum_kernel");
+}
+
+// what the launches behind the nodes kernel need of a call
+struct Sweep {
+    MinLengths ml;
+    const bin_t *trees;
+    int64_t tree_pitch;
+    const long long *diff;
+    hipStream_t st;
+};
+
+// Everything lad_score_surface and lad_score_surface_events (criteria: its two values, null for the other) do alike, up to and
+// including the nodes launch.  The checks, in this order: sizes, criteria, null buffers (results: the entry point's own test of its
+// result arrays), interval bounds, dtype, levels, min_lengths, the index.  Then the workspace is carved, the difference array of
+// FIELDS fields zeroed, the trees built, and launch_nodes(grid, lds_bytes, st, trees, tree_pitch, ml, cum, use_lds, diff) called:
+// the difference array of one channel is kept in LDS iff it fits into MAX_PRIVATE_BYTES.
+template <int FIELDS, typename Launch>
+inline int sweep_nodes(const char *who, const char *nodes_name, const int32_t *criteria, const void *probs, int32_t dtype, int64_t channels,
+                       int64_t frames, const double *levels, int32_t n_levels, const int32_t *bounds, const int32_t *offsets,
+                       const int32_t *bounds_host, const int32_t *offsets_host, int64_t n_intervals, const double *fps,
+                       const double *fps_host, const double *min_lengths, int32_t n_min_lengths, void *workspace, bool results,
+                       void *stream, Sweep &s, Launch launch_nodes) {
+    if (!surface_sizes_ok(channels, frames, n_intervals, n_levels, n_min_lengths))
+        return fail_sizes(who, channels, frames, n_intervals, n_levels, n_min_lengths);
+    if (int rc = criteria ? check_criteria(who, criteria[0], criteria[1]) : LAD_OK) return rc;
+    LAD_REQUIRE(probs && levels && offsets && offsets_host && fps && fps_host && min_lengths && workspace && results, "%s: null buffer",
+                who);
+    LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "%s: null interval bounds", who);
+    if (int rc = check_dtype(who, dtype)) return rc;
+    const int K = n_levels, L = n_min_lengths;
+    if (int rc = check_levels(who, levels, K)) return rc;
+    if (int rc = load_min_lengths(who, min_lengths, L, s.ml)) return rc;
+    if (int rc = check_index(who, channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
+
+    const Workspace w = layout(channels, frames, n_intervals, K, L, FIELDS);
+    char *ws = (char *)workspace;
+    double *levels_dev = (double *)(ws + w.levels);
+    int32_t *cum = (int32_t *)(ws + w.cum);
+    unsigned long long *diff = (unsigned long long *)(ws + w.diff);
+    bin_t *trees = (bin_t *)(ws + w.trees);
+    s.trees = trees;
+    s.tree_pitch = w.tree_pitch;
+    s.diff = (const long long *)diff;
+    s.st = (hipStream_t)stream;
+    const int64_t private_bytes = (int64_t)(K + 1) * L * FIELDS * (int64_t)sizeof(long long);
+    LAD_HIP_CHECK(hipMemsetAsync(diff, 0, (size_t)(channels * private_bytes), s.st));
+    if (int rc = build_trees(probs, dtype, channels, frames, levels, K, levels_dev, trees, w.tree_pitch, bounds, offsets, n_intervals, cum,
+                             s.st))
+        return rc;
+    const int use_lds = private_bytes <= MAX_PRIVATE_BYTES;
+    launch_nodes(dim3((unsigned)ceil_div(frames, CHUNK), (unsigned)channels), use_lds ? (size_t)private_bytes : (size_t)0, s.st,
+                 (const bin_t *)trees, w.tree_pitch, s.ml, (const int32_t *)cum, use_lds, diff);
+    return check_launch(nodes_name);
 }
 }  // namespace
 }  // namespace surface

@@ -1,9 +1,11 @@
 // What the threshold sweep's sources share (runs.hip, binarize.hip, score.hip, events.hip): the tile geometry and the limits of a
 // call, the fixed load of a probability, run starts / ends of a tile's ballot words and their placement by rank, the workgroup scan,
-// what the two scorers do alike with a run-table row and the interval index (the scans in front, the table a row belongs to, the
-// coverage look-up, the wave sum), and the host checks whose messages differ only in the entry point's name and in what it calls
-// its K axis ("thresholds" / "settings").  lad_score_runs and lad_score_events read the workspace the other two wrote, so there is
-// one definition of each.
+// what the scorers do alike with a run-table row and the interval index (the scans in front, the table a row belongs to, the
+// coverage look-up, the seven integers of a run (run_fields: score.hip and the dense pair), the wave sum and the sum over the lanes
+// of a wave that share a table (add_group: score.hip, events.hip)), and the host checks whose messages differ only in the entry
+// point's name and in what it calls its K axis ("thresholds" / "settings"): among them everything lad_score_runs and
+// lad_score_events ask before they launch (check_scorer) and the largest number of events of one channel (most_events_of).
+// lad_score_runs and lad_score_events read the workspace the other two wrote, so there is one definition of each.
 #pragma once
 #include <cmath>
 
@@ -224,6 +226,25 @@ __device__ inline unsigned run_fields(int64_t c, int32_t first, int32_t last, do
     return keep;
 }
 
+// value(l, f) of the lanes `in` of a wave that share table g -> out[g][l][f] (FIELDS values per min_length), one lane per sum;
+// Value::has(f): whether the caller sums field f at all
+template <int FIELDS, typename Value>
+__device__ inline void add_group(bool in, long long g, int64_t CK, int L, int lane, Value value, unsigned long long *__restrict__ out) {
+    long long mine = 0;
+#pragma unroll
+    for (int l = 0; l < MAX_L; ++l) {
+        if (l < L) {
+#pragma unroll
+            for (int f = 0; f < FIELDS; ++f) {
+                if (!value.has(f)) continue;
+                const long long s = wave_sum64(in ? value(l, f) : 0ll);
+                if (lane == l * FIELDS + f) mine = s;
+            }
+        }
+    }
+    if (lane < L * FIELDS && mine != 0 && g >= 0 && g < CK) atomicAdd(out + (g * L * FIELDS + lane), (unsigned long long)mine);
+}
+
 // ---- host side: `who` is the entry point, `what` its name for the K axis -------------------------------------------------------
 inline int check_sizes(const char *who, const char *what, int64_t channels, int64_t frames, int32_t K) {
     LAD_REQUIRE(channels >= 1 && channels <= MAX_C && frames >= 1 && frames <= MAX_T && K >= 1 && K <= MAX_K,
@@ -307,6 +328,48 @@ template <typename F>
 inline void with_track_type(int32_t dtype, F f) {
     if (dtype == LAD_RUNS_F32) f(float{});
     else f(double{});
+}
+
+// the event criteria of lad_score_events and lad_score_surface_events
+inline int check_criteria(const char *who, int32_t min_overlap_ms, int32_t min_overlap_pct) {
+    LAD_REQUIRE(min_overlap_ms >= 0 && min_overlap_pct >= 0 && min_overlap_pct <= 100,
+                "%s: min_overlap_ms >= 0, min_overlap_pct 0..100 (got %d, %d)", who, min_overlap_ms, min_overlap_pct);
+    return LAD_OK;
+}
+
+// the LAUGH intervals of the channel that has most, from an index that check_index has passed
+inline int64_t most_events_of(const int32_t *offsets_host, int64_t channels) {
+    int64_t most = 0;
+    for (int64_t c = 0; c < channels; ++c) {
+        const int64_t n = offsets_host[c * CLASSES + LAD_SCORE_LAUGH + 1] - offsets_host[c * CLASSES + LAD_SCORE_LAUGH];
+        most = n > most ? n : most;
+    }
+    return most;
+}
+
+// what lad_score_runs and lad_score_events (criteria: its two values, null for the other) ask before they launch anything, in
+// this order: sizes, criteria, null buffers, min_lengths, the index, the run counts.  out: the entry point's result array.
+// Gives the min_lengths as a kernel argument and the rows of all run tables together.
+inline int check_scorer(const char *who, const int32_t *criteria, const void *runs_workspace, const int32_t *table,
+                        const int32_t *counts_host, int64_t channels, int64_t frames, int32_t K, const int32_t *bounds,
+                        const int32_t *offsets, const int32_t *bounds_host, const int32_t *offsets_host, int64_t n_intervals,
+                        const double *fps, const double *fps_host, const double *min_lengths, int32_t L, const void *workspace,
+                        const void *out, MinLengths &ml, int64_t &rows) {
+    LAD_REQUIRE(score_sizes_ok(channels, n_intervals, K, L) && frames >= 1 && frames <= MAX_T,
+                "%s: channels 1..%d, frames 1..2^30, intervals 0..2^30, thresholds 1..%d, min_lengths 1..%d "
+                "(got %lld, %lld, %lld, %d, %d)",
+                who, MAX_C, MAX_K, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, K, L);
+    if (int rc = criteria ? check_criteria(who, criteria[0], criteria[1]) : LAD_OK) return rc;
+    LAD_REQUIRE(runs_workspace && counts_host && offsets && offsets_host && fps && fps_host && min_lengths && workspace && out,
+                "%s: null buffer", who);
+    LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "%s: null interval bounds", who);
+    if (int rc = load_min_lengths(who, min_lengths, L, ml)) return rc;
+    if (int rc = check_index(who, channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
+    rows = total_runs(who, counts_host, channels * K, frames);
+    if (rows < 0) return LAD_ERR_INVALID;
+    LAD_REQUIRE(rows <= MAX_ROWS, "%s: %lld run-table rows, at most 2^38 per call", who, (long long)rows);
+    LAD_REQUIRE(rows == 0 || table, "%s: null table", who);
+    return LAD_OK;
 }
 }  // namespace sweep
 }  // namespace lad

@@ -19,18 +19,20 @@
 // Shape: two launches after one memset of the output.
 //   score_scan_kernel  one workgroup per (channel, class): cum; one more: each run table's first row from the counts that
 //                      lad_runs_count left at the start of its workspace
-//   score_rows_kernel  one lane per run-table row: (c, k) by binary search in the first-row table, a, b and the
-//                      keep bits in float64, ten coverage look-ups advanced together (ten independent loads per step), then a
-//                      butterfly sum over the lanes of the wave that share (c, k) and one vector global atomic add on int64 per
-//                      (min_length, field) -- integer sums: whatever order the waves arrive in, the bytes are the same.
+//   score_rows_kernel  one lane per run-table row: (c, k) by binary search in the first-row table, then run_fields (the arithmetic
+//                      the dense sweep runs per node): a, b and the keep bits in float64, ten coverage look-ups advanced together
+//                      (ten independent loads per step), then add_group: a butterfly sum over the lanes of the wave that share
+//                      (c, k) and one vector global atomic add on int64 per (min_length, field) -- integer sums: whatever order
+//                      the waves arrive in, the bytes are the same.
 // Every index read is clamped to the index, every row read to the caller's row count.  No LDS in the row kernel, no scratch.
 #pragma clang fp contract(off)
-// The limits of the sweep whose workspace this reads, and the scan, are lad_sweep_tile.h's.
+// The limits of the sweep whose workspace this reads, the scan, run_fields, add_group and the checks of the entry point
+// (check_scorer, shared with lad_score_events) are lad_sweep_tile.h's.
 #include "lad_sweep_tile.h"
 
 namespace {
 using namespace lad::sweep;
-constexpr int FIELDS = 7;                          // n_pred, n_valid, pred_ms, corr_ms, fp_speech_ms, fp_noise_ms, fp_silence_ms
+constexpr int FIELDS = SCORE_FIELDS;               // n_pred, n_valid, pred_ms, corr_ms, fp_speech_ms, fp_noise_ms, fp_silence_ms
 
 // the scans of lad_sweep_tile.h: cum per (channel, class), and each run table's first row
 __global__ __launch_bounds__(THREADS) void score_scan_kernel(const int32_t *__restrict__ bounds, const int32_t *__restrict__ offsets,
@@ -39,6 +41,14 @@ __global__ __launch_bounds__(THREADS) void score_scan_kernel(const int32_t *__re
                                                              int64_t *__restrict__ first_row) {
     scan_index_and_counts(bounds, offsets, n_intervals, cum, segments, counts, CK, first_row);
 }
+
+// the seven integers of a row and its keep bits, as add_group sums them: field f counts for min_length l iff the run is kept there
+struct RunScores {
+    int32_t v[FIELDS];
+    unsigned keep;                // bit l: the run passes min_length l
+    __device__ static constexpr bool has(int) { return true; }
+    __device__ long long operator()(int l, int f) const { return ((keep >> l) & 1u) ? (long long)v[f] : 0ll; }
+};
 
 __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__restrict__ table, int64_t rows,
                                                              const int64_t *__restrict__ first_row, int64_t CK, int K,
@@ -50,23 +60,18 @@ __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__re
     const int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     const bool valid = row < rows;
     long long g = 0;              // c * K + k of this row
-    int32_t v[FIELDS];
+    RunScores r;
 #pragma unroll
-    for (int f = 0; f < FIELDS; ++f) v[f] = 0;
-    unsigned keep = 0;            // bit l: the run passes min_length l
+    for (int f = 0; f < FIELDS; ++f) r.v[f] = 0;
+    r.keep = 0;
     if (valid) {
         g = table_of_row(first_row, CK, row);
         const int c = (int)(g / K);
-        int32_t x[2];
-        keep = run_ms(table[2 * row], table[2 * row + 1], fps[c], ml, L, x);
-        int32_t F[2 * CLASSES], size[CLASSES];
-        coverage_pairs<CLASSES>(c, x, bounds, cum, offsets, n_intervals, F, size);
-        const int32_t pred = (x[1] - x[0]) - (F[1] - F[0]);      // |(a, b] \ INVALID|
-        v[0] = 1;
-        v[1] = size[0] > 0 ? (pred > 0 ? 1 : 0) : 1;              // analyse.py:185-187
-        v[2] = pred;
-#pragma unroll
-        for (int j = 1; j < CLASSES; ++j) v[2 + j] = F[2 * j + 1] - F[2 * j];
+        // run_fields is the arithmetic of the dense sweep's nodes.  A row of one frame (first == last) is the empty interval (a, a]:
+        // pred_ms = 0 and every overlap is 0 whatever the look-ups say, and n_valid is 1 iff the channel has no INVALID interval, so
+        // run_fields skips the look-ups there and reads that from the offsets themselves; lad_score_runs has checked them on the
+        // host (check_index), so they equal the clamped ones coverage_pairs would use.  Any other row goes through the same expressions.
+        r.keep = run_fields(c, table[2 * row], table[2 * row + 1], fps[c], ml, L, bounds, cum, offsets, n_intervals, r.v);
     }
     // sums over the lanes that share (c, k), one (c, k) at a time (rows ascend with c * K + k: mostly one or two per wave)
     unsigned long long todo = __ballot(valid);
@@ -74,20 +79,7 @@ __global__ __launch_bounds__(THREADS) void score_rows_kernel(const int32_t *__re
         const int leader = __ffsll((long long)todo) - 1;
         const long long gl = __shfl(g, leader, WAVE);
         const bool in = valid && g == gl;
-        long long mine = 0;
-#pragma unroll
-        for (int l = 0; l < MAX_L; ++l) {
-            if (l < L) {
-                const bool on = in && ((keep >> l) & 1u);
-#pragma unroll
-                for (int f = 0; f < FIELDS; ++f) {
-                    const long long s = wave_sum64(on ? (long long)v[f] : 0ll);
-                    if (lane == l * FIELDS + f) mine = s;
-                }
-            }
-        }
-        if (lane < L * FIELDS && mine != 0 && gl >= 0 && gl < CK)
-            atomicAdd(scores + (gl * L * FIELDS + lane), (unsigned long long)mine);
+        add_group<FIELDS>(in, gl, CK, L, lane, r, scores);
         todo &= ~__ballot(in);
     }
 }
@@ -114,22 +106,13 @@ extern "C" int lad_score_runs(const void *runs_workspace, const int32_t *table, 
                               const double *fps_host, const double *min_lengths, int32_t n_min_lengths, void *workspace,
                               int64_t *scores, void *stream) {
     using namespace lad;
-    LAD_REQUIRE(score_sizes_ok(channels, n_intervals, n_thresholds, n_min_lengths) && frames >= 1 && frames <= MAX_T,
-                "lad_score_runs: channels 1..%d, frames 1..2^30, intervals 0..2^30, thresholds 1..%d, min_lengths 1..%d "
-                "(got %lld, %lld, %lld, %d, %d)",
-                MAX_C, MAX_K, MAX_L, (long long)channels, (long long)frames, (long long)n_intervals, n_thresholds, n_min_lengths);
-    LAD_REQUIRE(runs_workspace && counts_host && offsets && offsets_host && fps && fps_host && min_lengths && workspace && scores,
-                "lad_score_runs: null buffer");
-    LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "lad_score_runs: null interval bounds");
     const int K = n_thresholds, L = n_min_lengths;
     const int64_t CK = channels * K;
     MinLengths ml;
-    if (int rc = load_min_lengths("lad_score_runs", min_lengths, L, ml)) return rc;
-    if (int rc = check_index("lad_score_runs", channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
-    const int64_t rows = total_runs("lad_score_runs", counts_host, CK, frames);
-    if (rows < 0) return LAD_ERR_INVALID;
-    LAD_REQUIRE(rows <= MAX_ROWS, "lad_score_runs: %lld run-table rows, at most 2^38 per call", (long long)rows);
-    LAD_REQUIRE(rows == 0 || table, "lad_score_runs: null table");
+    int64_t rows;
+    if (int rc = check_scorer("lad_score_runs", nullptr, runs_workspace, table, counts_host, channels, frames, K, bounds, offsets, bounds_host,
+                              offsets_host, n_intervals, fps, fps_host, min_lengths, L, workspace, scores, ml, rows))
+        return rc;
 
     int64_t *first_row = (int64_t *)workspace;
     int32_t *cum = (int32_t *)((char *)workspace + up256(CK * 8));

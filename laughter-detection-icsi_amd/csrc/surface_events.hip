@@ -3,9 +3,11 @@
 // (lad_surface_tree.h).  The convention is include/lad_hip.h's (above lad_score_surface_events): the predictions of level j are the
 // nodes of the component tree with base <= j < top, i.e. exactly the rows of level j's run table.
 //
-// Per node (surface_events_nodes_kernel, one lane per frame as surface.hip's): run_fields gives the seven time integers and with
-// them lov = corr_ms and pred_ms, so the node's own hit bit; its links are the LAUGH intervals with lo < b minus those with hi <= a
-// (two binary searches; 0 for a == b).  Nine integers go to the difference array over the levels, +w at row base and -w at row top.
+// Per node (surface_events_nodes_kernel, one lane per frame: lad_surface_tree.h's score_nodes, the body surface.hip runs, with nine
+// fields): run_fields gives the seven time integers and with them lov = corr_ms and pred_ms, so the node's own hit bit; its links
+// are the LAUGH intervals with lo < b minus those with hi <= a (two binary searches; 0 for a == b): HitAndLinks, which holds the
+// criteria and the channel's LAUGH segment, found once per workgroup.  Nine integers go to the difference array over the levels,
+// +w at row base and -w at row top.
 //
 // Per (event, level) (surface_events_match_kernel): ms(f) = rint(f / fps * 1000) does not decrease with f, so with F0 the first
 // frame whose ms is > lo and F1 the last whose ms is < hi, the run [s, e] of level j is linked to the event (lo, hi] iff s <= F1,
@@ -18,7 +20,8 @@
 // atomic add on int64 per non-zero (level, min_length, field).
 //
 // Shape: one copy (the levels), two memsets (the difference array, the event array) and SEVEN launches whatever C, K, L and the
-// number of events are: bins, tree twice, cum (lad_surface_tree.h: build_trees), nodes, match, prefix.  No loop over levels or
+// number of events are: bins, tree twice, cum, nodes (lad_surface_tree.h: sweep_nodes, the host half shared with
+// lad_score_surface), match, prefix (prefix_levels per field, and N_REF).  No loop over levels or
 // events on the host.  Integer sums on int64 only: identical bytes on every call.  Every read of the tree is below its level's node
 // count (the two searches; the walk reads frames 0 .. T - 1 only), every index read is clamped to the index.  No scratch.
 #pragma clang fp contract(off)
@@ -28,11 +31,9 @@ namespace {
 using namespace lad::sweep;
 using namespace lad::surface;
 using lad::ceil_div;
-using lad::up256;
 
 constexpr int EV_FIELDS = LAD_EVENT_FIELDS;
 constexpr int DIFF_FIELDS = SCORE_FIELDS + 2;    // the seven time fields, PRED_HIT, LINKS
-constexpr int MAX_PRIVATE_BYTES = 48 * 1024;     // the difference array of one channel in LDS, if it fits
 constexpr int WALK_TILE = 1024;                  // frames of a window in LDS at a time: 2 + 8 bytes each, 10 KB per workgroup of one wave
 constexpr int MAX_GROUP = 64;                    // events per workgroup of the match kernel, at most
 
@@ -59,6 +60,23 @@ __device__ inline int64_t count_below(const int32_t *__restrict__ bounds, int64_
     return at - o0;
 }
 
+// the two fields behind run_fields' seven, for the nodes of one channel: PRED_HIT from lov = corr_ms and pred_ms, LINKS from the
+// channel's LAUGH segment [o0, o1) of the index
+struct HitAndLinks {
+    int32_t min_ms, min_pct;
+    const int32_t *__restrict__ bounds;
+    int64_t o0, o1;
+    __device__ void operator()(int32_t first, int32_t last, double f, const MinLengths &ml, int L, int32_t (&v)[DIFF_FIELDS]) const {
+        const long long lov = v[3], pred = v[2];                             // |(a, b] n LAUGH|, |(a, b] \ INVALID|
+        v[SCORE_FIELDS] = (lov >= (min_ms > 1 ? min_ms : 1) && 100ll * lov >= (long long)min_pct * pred) ? 1 : 0;
+        int32_t x[2];
+        run_ms(first, last, f, ml, L, x);
+        v[SCORE_FIELDS + 1] = 0;
+        if (x[1] > x[0])                                                     // events with lo < b, minus those with hi <= a
+            v[SCORE_FIELDS + 1] = (int32_t)(count_below(bounds, o0, o1, 0, x[1]) - count_below(bounds, o0, o1, 1, x[0] + 1));
+    }
+};
+
 __global__ __launch_bounds__(THREADS) void surface_events_nodes_kernel(const bin_t *__restrict__ trees, int64_t tree_pitch, int64_t T, int K,
                                                                        const double *__restrict__ fps, MinLengths ml, int L,
                                                                        const int32_t *__restrict__ bounds,
@@ -66,70 +84,9 @@ __global__ __launch_bounds__(THREADS) void surface_events_nodes_kernel(const bin
                                                                        const int32_t *__restrict__ offsets, int64_t n_intervals,
                                                                        int32_t min_ms, int32_t min_pct, int use_lds,
                                                                        unsigned long long *__restrict__ diff) {
-    extern __shared__ unsigned long long priv[];
-    const int64_t c = blockIdx.y;
-    const bin_t *tree = trees + c * tree_pitch;
-    const int cells = (K + 1) * L * DIFF_FIELDS;
-    unsigned long long *mine = diff + c * cells;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < cells; i += THREADS) priv[i] = 0;
-        __syncthreads();
-    }
-    const double f = fps[c];
-    int64_t o0, o1;
-    laugh_segment(c, offsets, n_intervals, o0, o1);
-    const int64_t chunk0 = (int64_t)blockIdx.x * CHUNK;
-    for (int j = threadIdx.x; j < CHUNK; j += THREADS) {
-        const int64_t i = chunk0 + j;
-        if (i >= T) break;
-        const int top = tree[i];
-        if (top == 0 || top > K) continue;
-        int lb, rb;
-        const int64_t left = nearest_left_le(tree, T, i, top, lb);
-        if (left >= 0 && lb == top) continue;        // an equal bin further left in the same interval: that frame speaks for it
-        const int64_t right = nearest_right_lt(tree, T, i, top, rb);
-        const int base = lb > rb ? lb : rb;
-        if (base >= top) continue;                   // (cannot happen: both neighbours are smaller)
-        int32_t v[DIFF_FIELDS];
-        int32_t time[SCORE_FIELDS];
-        const int32_t first = (int32_t)(left + 1), last = (int32_t)(right - 1);
-        const unsigned keep = run_fields(c, first, last, f, ml, L, bounds, cum, offsets, n_intervals, time);
-#pragma unroll
-        for (int fd = 0; fd < SCORE_FIELDS; ++fd) v[fd] = time[fd];
-        const long long lov = time[3], pred = time[2];                       // |(a, b] n LAUGH|, |(a, b] \ INVALID|
-        v[SCORE_FIELDS] = (lov >= (min_ms > 1 ? min_ms : 1) && 100ll * lov >= (long long)min_pct * pred) ? 1 : 0;
-        int32_t x[2];
-        run_ms(first, last, f, ml, L, x);
-        v[SCORE_FIELDS + 1] = 0;
-        if (x[1] > x[0])                                                     // events with lo < b, minus those with hi <= a
-            v[SCORE_FIELDS + 1] = (int32_t)(count_below(bounds, o0, o1, 0, x[1]) - count_below(bounds, o0, o1, 1, x[0] + 1));
-#pragma unroll
-        for (int l = 0; l < MAX_L; ++l) {
-            if (l < L && ((keep >> l) & 1u)) {
-#pragma unroll
-                for (int fd = 0; fd < DIFF_FIELDS; ++fd) {
-                    if (v[fd] != 0) {
-                        const unsigned long long w = (unsigned long long)(long long)v[fd];
-                        const int up = (base * L + l) * DIFF_FIELDS + fd, down = (top * L + l) * DIFF_FIELDS + fd;
-                        if (use_lds) {
-                            atomicAdd(priv + up, w);
-                            atomicAdd(priv + down, 0ull - w);
-                        } else {
-                            atomicAdd(mine + up, w);
-                            atomicAdd(mine + down, 0ull - w);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < cells; i += THREADS) {
-            const unsigned long long w = priv[i];
-            if (w != 0) atomicAdd(mine + i, w);
-        }
-    }
+    HitAndLinks extra{min_ms, min_pct, bounds, 0, 0};
+    laugh_segment(blockIdx.y, offsets, n_intervals, extra.o0, extra.o1);     // once per workgroup
+    score_nodes<DIFF_FIELDS>(trees, tree_pitch, T, K, fps, ml, L, bounds, cum, offsets, n_intervals, use_lds, diff, extra);
 }
 
 // the first frame f of [0, T) with rint(f / fps * 1000) >= x, or T
@@ -269,8 +226,7 @@ __global__ __launch_bounds__(WAVE) void surface_events_match_kernel(const bin_t 
 }
 
 // one workgroup per (channel, min_length, field of the difference array): the sum of diff[c][0..j][l][f] to scores[c][j][l][f] for
-// a time field, to events[c][j][l][PRED_HIT / LINKS] for the other two; the workgroup of PRED_HIT also writes N_REF.  Row K of diff
-// is never read.
+// a time field, to events[c][j][l][PRED_HIT / LINKS] for the other two (prefix_levels); the workgroup of PRED_HIT also writes N_REF.
 __global__ __launch_bounds__(THREADS) void surface_events_prefix_kernel(const long long *__restrict__ diff, int K, int L,
                                                                         const int32_t *__restrict__ offsets, int64_t n_intervals,
                                                                         long long *__restrict__ scores, long long *__restrict__ events) {
@@ -279,45 +235,24 @@ __global__ __launch_bounds__(THREADS) void surface_events_prefix_kernel(const lo
     const int l = (int)(blockIdx.x % LF) / DIFF_FIELDS, fd = (int)(blockIdx.x % LF) % DIFF_FIELDS;
     const long long *in = diff + c * (K + 1) * LF + l * DIFF_FIELDS + fd;
     if (fd < SCORE_FIELDS) {
-        long long *out = scores + (c * K * L + l) * SCORE_FIELDS + fd;
-        const int step = L * SCORE_FIELDS;
-        block_scan<long long>(0, K, [&](int64_t j) { return in[j * LF]; }, [&](int64_t j, long long v) { out[j * step] = v + in[j * LF]; });
+        prefix_levels(in, LF, scores + (c * K * L + l) * SCORE_FIELDS + fd, L * SCORE_FIELDS, K);
         return;
     }
-    int64_t o0, o1;
-    laugh_segment(c, offsets, n_intervals, o0, o1);
     const bool hit = fd == SCORE_FIELDS;
     long long *out = events + (c * K * L + l) * EV_FIELDS;
     const int step = L * EV_FIELDS;
-    block_scan<long long>(0, K, [&](int64_t j) { return in[j * LF]; },
-                          [&](int64_t j, long long v) {
-                              out[j * step + (hit ? LAD_EVENT_PRED_HIT : LAD_EVENT_LINKS)] = v + in[j * LF];
-                              if (hit) out[j * step + LAD_EVENT_N_REF] = o1 - o0;
-                          });
-}
-
-struct Workspace {
-    int64_t levels, cum, diff, trees, tree_pitch, bytes;
-};
-Workspace layout(int64_t C, int64_t T, int64_t n_intervals, int64_t K, int64_t L) {   // of sizes that surface_sizes_ok has passed
-    Workspace w;
-    w.levels = 0;
-    w.cum = up256(K * 8);
-    w.diff = w.cum + up256(n_intervals * 4);
-    w.trees = w.diff + up256(C * (K + 1) * L * DIFF_FIELDS * 8);
-    w.tree_pitch = tree_pitch_of(T);
-    w.bytes = w.trees + C * w.tree_pitch * (int64_t)sizeof(bin_t) + 256;
-    return w;
+    prefix_levels(in, LF, out + (hit ? LAD_EVENT_PRED_HIT : LAD_EVENT_LINKS), step, K);
+    if (hit) {
+        int64_t o0, o1;
+        laugh_segment(c, offsets, n_intervals, o0, o1);
+        for (int j = threadIdx.x; j < K; j += THREADS) out[(int64_t)j * step + LAD_EVENT_N_REF] = o1 - o0;
+    }
 }
 }  // namespace
 
 extern "C" int64_t lad_surface_events_workspace_bytes(int64_t channels, int64_t frames, int64_t n_intervals, int32_t n_levels,
                                                       int32_t n_min_lengths) {
-    if (!surface_sizes_ok(channels, frames, n_intervals, n_levels, n_min_lengths)) {
-        lad::fail(LAD_ERR_INVALID, SURFACE_SIZES_MESSAGE("lad_surface_events_workspace_bytes"));
-        return -1;
-    }
-    return layout(channels, frames, n_intervals, n_levels, n_min_lengths).bytes;
+    return workspace_bytes("lad_surface_events_workspace_bytes", channels, frames, n_intervals, n_levels, n_min_lengths, DIFF_FIELDS);
 }
 
 extern "C" int lad_score_surface_events(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *levels,
@@ -326,53 +261,30 @@ extern "C" int lad_score_surface_events(const void *probs, int32_t dtype, int64_
                                         const double *min_lengths, int32_t n_min_lengths, int32_t min_overlap_ms,
                                         int32_t min_overlap_pct, void *workspace, int64_t *scores, int64_t *events, void *stream) {
     using namespace lad;
-    const char *who = "lad_score_surface_events";
-    LAD_REQUIRE(surface_sizes_ok(channels, frames, n_intervals, n_levels, n_min_lengths), SURFACE_SIZES_MESSAGE("lad_score_surface_events"));
-    LAD_REQUIRE(min_overlap_ms >= 0 && min_overlap_pct >= 0 && min_overlap_pct <= 100,
-                "lad_score_surface_events: min_overlap_ms >= 0, min_overlap_pct 0..100 (got %d, %d)", min_overlap_ms, min_overlap_pct);
-    LAD_REQUIRE(probs && levels && offsets && offsets_host && fps && fps_host && min_lengths && workspace && scores && events,
-                "lad_score_surface_events: null buffer");
-    LAD_REQUIRE(n_intervals == 0 || (bounds && bounds_host), "lad_score_surface_events: null interval bounds");
-    if (int rc = check_dtype(who, dtype)) return rc;
     const int K = n_levels, L = n_min_lengths;
-    if (int rc = check_levels(who, levels, K)) return rc;
-    MinLengths ml;
-    if (int rc = load_min_lengths(who, min_lengths, L, ml)) return rc;
-    if (int rc = check_index(who, channels, frames, fps_host, offsets_host, bounds_host, n_intervals)) return rc;
-    int64_t most_events = 0;      // of one channel
-    for (int64_t c = 0; c < channels; ++c) {
-        const int64_t n = offsets_host[c * CLASSES + LAD_SCORE_LAUGH + 1] - offsets_host[c * CLASSES + LAD_SCORE_LAUGH];
-        most_events = n > most_events ? n : most_events;
-    }
-
-    const Workspace w = layout(channels, frames, n_intervals, K, L);
-    char *ws = (char *)workspace;
-    double *levels_dev = (double *)(ws + w.levels);
-    int32_t *cum = (int32_t *)(ws + w.cum);
-    unsigned long long *diff = (unsigned long long *)(ws + w.diff);
-    bin_t *trees = (bin_t *)(ws + w.trees);
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t cells = (int64_t)(K + 1) * L * DIFF_FIELDS;
-    LAD_HIP_CHECK(hipMemsetAsync(diff, 0, (size_t)(channels * cells) * sizeof(long long), st));
-    LAD_HIP_CHECK(hipMemsetAsync(events, 0, (size_t)(channels * K * L * EV_FIELDS) * sizeof(long long), st));
-    if (int rc = build_trees(probs, dtype, channels, frames, levels, K, levels_dev, trees, w.tree_pitch, bounds, offsets, n_intervals, cum, st))
+    const int32_t criteria[2] = {min_overlap_ms, min_overlap_pct};
+    Sweep s;
+    const auto nodes = [&](dim3 grid, size_t lds_bytes, hipStream_t st, const bin_t *trees, int64_t tree_pitch, const MinLengths &ml,
+                           const int32_t *cum, int use_lds, unsigned long long *diff) {
+        hipLaunchKernelGGL(surface_events_nodes_kernel, grid, dim3(THREADS), lds_bytes, st, trees, tree_pitch, frames, K, fps, ml, L, bounds,
+                           cum, offsets, n_intervals, min_overlap_ms, min_overlap_pct, use_lds, diff);
+    };
+    if (int rc = sweep_nodes<DIFF_FIELDS>("lad_score_surface_events", "surface_events_nodes_kernel", criteria, probs, dtype, channels, frames,
+                                          levels, K, bounds, offsets, bounds_host, offsets_host, n_intervals, fps, fps_host, min_lengths, L,
+                                          workspace, scores && events, stream, s, nodes))
         return rc;
-    const int64_t private_bytes = cells * (int64_t)sizeof(long long);
-    const int use_lds = private_bytes <= MAX_PRIVATE_BYTES;
-    hipLaunchKernelGGL(surface_events_nodes_kernel, dim3((unsigned)ceil_div(frames, CHUNK), (unsigned)channels), dim3(THREADS),
-                       use_lds ? (size_t)private_bytes : 0, st, (const bin_t *)trees, w.tree_pitch, frames, K, fps, ml, L, bounds,
-                       (const int32_t *)cum, offsets, n_intervals, min_overlap_ms, min_overlap_pct, use_lds, diff);
-    if (int rc = check_launch("surface_events_nodes_kernel")) return rc;
+    const int64_t most_events = most_events_of(offsets_host, channels);
+    LAD_HIP_CHECK(hipMemsetAsync(events, 0, (size_t)(channels * K * L * EV_FIELDS) * sizeof(long long), s.st));
     // events per workgroup: as many as leave some 16384 workgroups to the device (fewer atomics, the same sums)
     const int64_t level_blocks = ceil_div(K, WAVE);
     int64_t group = most_events * level_blocks * channels / 16384;
     group = group < 1 ? 1 : (group > MAX_GROUP ? MAX_GROUP : group);
     const int64_t groups = most_events > 0 ? ceil_div(most_events, group) : 1;      // (no event: every workgroup returns at once)
-    hipLaunchKernelGGL(surface_events_match_kernel, dim3((unsigned)groups, (unsigned)level_blocks, (unsigned)channels), dim3(WAVE), 0, st,
-                       (const bin_t *)trees, w.tree_pitch, frames, K, fps, ml, L, bounds, offsets, n_intervals, (int)group, min_overlap_ms,
+    hipLaunchKernelGGL(surface_events_match_kernel, dim3((unsigned)groups, (unsigned)level_blocks, (unsigned)channels), dim3(WAVE), 0, s.st,
+                       s.trees, s.tree_pitch, frames, K, fps, s.ml, L, bounds, offsets, n_intervals, (int)group, min_overlap_ms,
                        min_overlap_pct, (unsigned long long *)events);
     if (int rc = check_launch("surface_events_match_kernel")) return rc;
-    hipLaunchKernelGGL(surface_events_prefix_kernel, dim3((unsigned)(channels * L * DIFF_FIELDS)), dim3(THREADS), 0, st,
-                       (const long long *)diff, K, L, offsets, n_intervals, (long long *)scores, (long long *)events);
+    hipLaunchKernelGGL(surface_events_prefix_kernel, dim3((unsigned)(channels * L * DIFF_FIELDS)), dim3(THREADS), 0, s.st, s.diff, K, L,
+                       offsets, n_intervals, (long long *)scores, (long long *)events);
     return check_launch("surface_events_prefix_kernel");
 }

@@ -238,20 +238,9 @@ def fps_per_channel(fps, C, each=_check_fps):
 
 
 def device_track(probs, what="sweep"):
-    """What every device form asks of its probability tensor: (T,) or (C, T), in GPU memory, contiguous, float32 or float64.
-    Returns (the (C, T) tensor, its lad_runs_dtype, whether it was a (T,) one)."""
-    import torch
-
+    """_hip.device_track: what every device form asks of its probability tensor."""
     import _hip
-    single = getattr(probs, "ndim", None) == 1
-    if single and hasattr(probs, "unsqueeze"):
-        probs = probs.unsqueeze(0)
-    if getattr(probs, "ndim", None) != 2:
-        raise _hip.LadHipError(f"probs must be a (T,) or (C, T) GPU tensor (the device {what} has no CPU fallback)")
-    _hip.require_cuda(probs, "probs")
-    if probs.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {probs.dtype}")
-    return probs, 0 if probs.dtype == torch.float32 else 1, single
+    return _hip.device_track(probs, what)
 
 
 def on_device(ctx, name, device):
@@ -522,24 +511,22 @@ def decoder_for(offset_drops=None, min_gaps=None, penalties=None):
     return HYSTERESIS, (list(offset_drops) if offset_drops is not None else [0.0], list(min_gaps) if min_gaps is not None else [0.0])
 
 
-def _device_tables(decoder, probs, dtype, chunk, ctx, extra_bytes=0, want_best=False):
+def _device_tables(decoder, probs, dtype, chunk, ctx, want_best=False):
     """Count + fill of one round (include/lad_hip.h) on a (C, T) tensor that device_track has passed, T >= 1, for the settings
     `chunk`, at most decoder.round_size of them.  Everything stays on the device: returns (workspace, table, counts, best) with
-    `workspace` a uint8 tensor whose first lad_*_workspace_bytes bytes are the family's workspace (the tables' counts at its start,
-    where the scorers read them) followed by extra_bytes for the caller, `table` the (total, 2) int32 tables back to back in
-    c * K + k order, counts their row counts, int32 numpy (C * K,), and best the int64 (C * K,) path scores of the Viterbi decoder
-    on the device (None unless asked for).  The counts cross to the host once, after the count (HYSTERESIS: and after its fill)."""
+    `workspace` the family's workspace, a uint8 tensor (the tables' counts at its start, where the scorers read them), `table` the
+    (total, 2) int32 tables back to back in c * K + k order, counts their row counts, int32 numpy (C * K,), and best the int64
+    (C * K,) path scores of the Viterbi decoder on the device (None unless asked for).  The counts cross to the host once, after
+    the count (HYSTERESIS: and after its fill)."""
     import torch
 
     import _hip
     lib = _hip.lib()
     C, T = probs.shape
     K = len(chunk)
-    ws_bytes = getattr(lib, decoder.lib + "_workspace_bytes")(C, T, K)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, decoder.lib + "_workspace_bytes")
+    ws = _hip.workspace(decoder.lib + "_workspace_bytes", C, T, K, device=probs.device)
     with torch.cuda.device(probs.device):
         stream = _hip.stream_handle(probs.device)
-        ws = torch.empty(ws_bytes + extra_bytes, dtype=torch.uint8, device=probs.device)
         ctx["best"] = best = torch.empty(C * K, dtype=torch.int64, device=probs.device) if want_best else None
         track = (_hip.ptr(probs), dtype, C, T)
         decoder.count(lib, track, chunk, ws, stream, ctx)

@@ -57,28 +57,13 @@ def filtfilt_device(probs, b, a, lengths=None, out=None):
     import torch
 
     import _hip
-    single = getattr(probs, "ndim", None) == 1
-    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
-    if getattr(p2, "ndim", None) != 2:
-        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device low-pass has no CPU fallback)")
-    if isinstance(p2, torch.Tensor) and p2.is_cuda and p2.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {p2.dtype}")
-    _hip.require_cuda(p2, "probs")
+    p2, dtype, single = _hip.device_track(probs, "low-pass")
     C, T = p2.shape
-    if lengths is not None:
-        lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
-        if lengths.shape != (C,):
-            raise ValueError(f"{lengths.size} lengths for {C} channels")
+    lengths = _hip.channel_lengths(lengths, C)
     shortest = T if lengths is None or C == 0 else int(lengths.min())
     if shortest <= PADLEN:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {PADLEN}.")
-    if out is None:
-        out2 = torch.empty((C, T), dtype=torch.float64, device=p2.device)
-    else:
-        _hip.require_cuda(out, "out", torch.float64)
-        if out.shape != probs.shape or out.device != p2.device:
-            raise ValueError("out must have the shape and device of probs")
-        out2 = out.unsqueeze(0) if single else out
+    out2 = _hip.out_track(out, p2, single, torch.float64)
     if C == 0:
         return out2[0] if single else out2
     lib = _hip.lib()
@@ -86,12 +71,9 @@ def filtfilt_device(probs, b, a, lengths=None, out=None):
     bb = np.ascontiguousarray(b, dtype=np.float64)
     aa = np.ascontiguousarray(a, dtype=np.float64)
     zi = zi2(bb, aa)
-    ws_bytes = lib.lad_lowpass_workspace_bytes(C, T)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_lowpass_workspace_bytes")
-    dtype = 0 if p2.dtype == torch.float32 else 1     # lad_runs_dtype
     lptr = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if lengths is not None else None
     with torch.cuda.device(p2.device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p2.device)
+        ws = _hip.workspace("lad_lowpass_workspace_bytes", C, T, device=p2.device)
         _hip.check(lib.lad_lowpass(_hip.ptr(p2), dtype, C, T, lptr, bb.ctypes.data_as(f64p), aa.ctypes.data_as(f64p),
                                    zi.ctypes.data_as(f64p), _hip.ptr(out2), _hip.ptr(ws), _hip.stream_handle(p2.device)),
                    "lad_lowpass")

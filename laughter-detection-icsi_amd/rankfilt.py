@@ -8,8 +8,6 @@ device form equals the host form (laugh_segmenter.rank_filter) bit for bit.  The
 """
 import ctypes
 
-import numpy as np
-
 MAX_WINDOW = 1023      # lad_rank_filter_max_window()
 
 
@@ -36,39 +34,20 @@ def rank_filter_device(probs, window, rank, lengths=None, out=None):
     import torch
 
     import _hip
-    single = getattr(probs, "ndim", None) == 1
-    p2 = probs.unsqueeze(0) if single and hasattr(probs, "unsqueeze") else probs
-    if getattr(p2, "ndim", None) != 2:
-        raise _hip.LadHipError("probs must be a (T,) or (C, T) GPU tensor (the device rank filter has no CPU fallback)")
-    if isinstance(p2, torch.Tensor) and p2.is_cuda and p2.dtype not in (torch.float32, torch.float64):
-        raise _hip.LadHipError(f"probs must be float32 or float64, got {p2.dtype}")
-    _hip.require_cuda(p2, "probs")
+    p2, dtype, single = _hip.device_track(probs, "rank filter")
     window, rank = check_window(window, rank)
     C, T = p2.shape
-    if lengths is not None:
-        lengths = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
-        if lengths.shape != (C,):
-            raise ValueError(f"{lengths.size} lengths for {C} channels")
-        if C and T and (lengths.min() < 1 or lengths.max() > T):
-            raise ValueError(f"every length lies in 1..{T}, got {int(lengths.min())}..{int(lengths.max())}")
-    if out is None:
-        out2 = torch.empty((C, T), dtype=p2.dtype, device=p2.device)
-    else:
-        _hip.require_cuda(out, "out", p2.dtype)
-        if out.shape != probs.shape or out.device != p2.device:
-            raise ValueError("out must have the shape and device of probs")
-        out2 = out.unsqueeze(0) if single else out
+    lengths = _hip.channel_lengths(lengths, C)
+    if lengths is not None and C and T and (lengths.min() < 1 or lengths.max() > T):
+        raise ValueError(f"every length lies in 1..{T}, got {int(lengths.min())}..{int(lengths.max())}")
+    out2 = _hip.out_track(out, p2, single, p2.dtype)
     if C == 0 or T == 0:
         return out2[0] if single else out2
-    lib = _hip.lib()
-    ws_bytes = lib.lad_rank_filter_workspace_bytes(C, T, window)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_rank_filter_workspace_bytes")
-    dtype = 0 if p2.dtype == torch.float32 else 1     # lad_runs_dtype
     lptr = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if lengths is not None else None
     with torch.cuda.device(p2.device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p2.device)
-        _hip.check(lib.lad_rank_filter(_hip.ptr(p2), dtype, C, T, lptr, window, rank, _hip.ptr(out2), _hip.ptr(ws),
-                                       _hip.stream_handle(p2.device)), "lad_rank_filter")
+        ws = _hip.workspace("lad_rank_filter_workspace_bytes", C, T, window, device=p2.device)
+        _hip.check(_hip.lib().lad_rank_filter(_hip.ptr(p2), dtype, C, T, lptr, window, rank, _hip.ptr(out2), _hip.ptr(ws),
+                                              _hip.stream_handle(p2.device)), "lad_rank_filter")
     return out2[0] if single else out2
 
 

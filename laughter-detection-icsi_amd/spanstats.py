@@ -20,10 +20,8 @@ def prepare_device(probs, dtype):
     import _hip
     lib = _hip.lib()
     C, T = probs.shape
-    ws_bytes = lib.lad_span_stats_workspace_bytes(C, T)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_span_stats_workspace_bytes")
+    ws = _hip.workspace("lad_span_stats_workspace_bytes", C, T, device=probs.device)
     with torch.cuda.device(probs.device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
         _hip.check(lib.lad_span_stats_prepare(_hip.ptr(probs), dtype, C, T, _hip.ptr(ws), _hip.stream_handle(probs.device)),
                    "lad_span_stats_prepare")
     return ws

@@ -384,6 +384,50 @@ def score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, offs
     return out if events is None else (out, ev)
 
 
+def _device_head(probs, what, channels, behind, fps, index, lowpass, median, lengths, events):
+    """What the two device scorers do alike before they reach the library, in the order of their checks: the track
+    (laugh_segmenter.device_track), the one-smoother rule, the channel count, fps, the result of a call with nothing to launch on
+    (the result has the shape (C, *behind)), the smoother, the rule for `lengths`, the DeviceIndex.  Returns (None, that result)
+    or ((probs, dtype, DeviceIndex, fps as a float64 host array, the event criteria or None), None)."""
+    probs, dtype, _ = ls.device_track(probs, what)
+    if lowpass is not None and median is not None:
+        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
+    C, T = probs.shape
+    if C != len(channels):
+        raise ValueError(f"{C} tracks for {len(channels)} channels")
+    fps_host = ls.fps_per_channel(fps, C, each=float)
+    out_shape = (C, *behind)
+    criteria = None if events is None else _event_criteria(events)
+    if T == 0 or 0 in out_shape:
+        if criteria is None:
+            return None, np.zeros(out_shape, np.int64)
+        ev = np.zeros(out_shape, np.int64)          # (nothing to launch on: no prediction, the events of each channel counted)
+        if 0 not in out_shape:
+            offsets = (index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)).offsets_host
+            ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape((C,) + (1,) * (len(out_shape) - 2))
+        return None, (np.zeros(out_shape, np.int64), ev)
+    if lowpass is not None:
+        probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), what)
+    elif median is not None:
+        probs, dtype, _ = ls.device_track(ls.median_filter_device(probs, median, lengths=lengths), what)
+    elif lengths is not None:
+        raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
+    dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
+    if dix.channels != channels or dix.device != probs.device:
+        raise ValueError("the DeviceIndex was built for other channels or another device")
+    return (probs, dtype, dix, fps_host, criteria), None
+
+
+def _index_and_lengths(dix, ctx, min_lengths):
+    """The ten arguments every scoring entry point ends its inputs with: the index on the device and on the host, fps
+    (ctx["fps_host"]) on the device and on the host, the min_lengths and their number."""
+    import _hip
+    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    return (_hip.ptr(dix.bounds), _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p),
+            dix.n_intervals, _hip.ptr(ls.on_device(ctx, "fps_host", dix.device)), ctx["fps_host"].ctypes.data_as(f64p),
+            (ctypes.c_double * len(min_lengths))(*[float(m) for m in min_lengths]), len(min_lengths))
+
+
 def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
                        min_gaps=None, events=None, penalties=None, median=None):
     """probs: (C, T) or (T,) float32 / float64 GPU tensor, a shorter channel padded with NaN (off for every threshold) -> int64 numpy
@@ -402,59 +446,34 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
     import torch
 
     import _hip
-    probs, dtype, _ = ls.device_track(probs, "scorer")
-    if lowpass is not None and median is not None:
-        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
     channels, thresholds, min_lengths = list(channels), list(thresholds), list(min_lengths)
+    decoder, axes = ls.decoder_for(offset_drops, min_gaps, penalties)
+    out_shape = _score_shape(len(channels), thresholds, min_lengths, axes)
+    head, empty = _device_head(probs, "scorer", channels, out_shape[1:], fps, index, lowpass, median, lengths, events)
+    if head is None:
+        return empty
+    probs, dtype, dix, fps_host, criteria = head
     C, T = probs.shape
     L = len(min_lengths)
-    if C != len(channels):
-        raise ValueError(f"{C} tracks for {len(channels)} channels")
-    ctx = {"fps_host": ls.fps_per_channel(fps, C, each=float)}
-    decoder, axes = ls.decoder_for(offset_drops, min_gaps, penalties)
-    out_shape = _score_shape(C, thresholds, min_lengths, axes)
-    criteria = None if events is None else _event_criteria(events)
-    if T == 0 or 0 in out_shape:
-        if criteria is None:
-            return np.zeros(out_shape, np.int64)
-        ev = np.zeros(out_shape, np.int64)          # (nothing to launch on: no prediction, the events of each channel counted)
-        if 0 not in out_shape:
-            offsets = (index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)).offsets_host
-            ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape((C,) + (1,) * (len(out_shape) - 2))
-        return np.zeros(out_shape, np.int64), ev
-    if lowpass is not None:
-        probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "scorer")
-    elif median is not None:
-        probs, dtype, _ = ls.device_track(ls.median_filter_device(probs, median, lengths=lengths), "scorer")
-    elif lengths is not None:
-        raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
     lib = _hip.lib()
-    dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
-    if dix.channels != channels or dix.device != probs.device:
-        raise ValueError("the DeviceIndex was built for other channels or another device")
-    mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
-    i32p = ctypes.POINTER(ctypes.c_int32)
+    ctx = {"fps_host": fps_host}
+    index_and_lengths = _index_and_lengths(dix, ctx, min_lengths)
     settings = decoder.keys(thresholds, axes, ctx)[1]
     step = decoder.round_size(lib, len(settings))
     parts, ev_parts = [], []
     for k0 in range(0, len(settings), step):
         chunk = settings[k0:k0 + step]
         n = len(chunk)
-        sws_bytes = lib.lad_score_workspace_bytes(C, dix.n_intervals, n, L)
-        _hip.check(0 if sws_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_workspace_bytes")
-        ws, table, counts, _ = ls._device_tables(decoder, probs, dtype, chunk, ctx, extra_bytes=sws_bytes)
+        sws = _hip.workspace("lad_score_workspace_bytes", C, dix.n_intervals, n, L, device=probs.device)
+        ws, table, counts, _ = ls._device_tables(decoder, probs, dtype, chunk, ctx)
         with torch.cuda.device(probs.device):
             stream = _hip.stream_handle(probs.device)
-            scored = (_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(i32p), C, T, n, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
-                      dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
-                      _hip.ptr(ls.on_device(ctx, "fps_host", probs.device)), ctx["fps_host"].ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                      mls, L)                       # what the two scorers are given alike: the tables, the index, fps and min_lengths
+            # what the two scorers are given alike: the tables, the index, fps and min_lengths
+            scored = (_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), C, T, n, *index_and_lengths)
             scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
-            _hip.check(lib.lad_score_runs(*scored, _hip.ptr(ws[ws.numel() - sws_bytes:]), _hip.ptr(scores), stream), "lad_score_runs")
+            _hip.check(lib.lad_score_runs(*scored, _hip.ptr(sws), _hip.ptr(scores), stream), "lad_score_runs")
             if criteria is not None:
-                ews_bytes = lib.lad_score_events_workspace_bytes(C, dix.n_intervals, n, L, len(table))
-                _hip.check(0 if ews_bytes >= 0 else _hip.LAD_ERR_INVALID, "lad_score_events_workspace_bytes")
-                ews = torch.empty(ews_bytes, dtype=torch.uint8, device=probs.device)
+                ews = _hip.workspace("lad_score_events_workspace_bytes", C, dix.n_intervals, n, L, len(table), device=probs.device)
                 ev = torch.empty((C, n, L, len(EVENT_FIELDS)), dtype=torch.int64, device=probs.device)
                 _hip.check(lib.lad_score_events(*scored, *criteria, _hip.ptr(ews), _hip.ptr(ev), stream), "lad_score_events")
                 ev_parts.append(ev.cpu().numpy())
@@ -601,48 +620,23 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
     import torch
 
     import _hip
-    probs, dtype, _ = ls.device_track(probs, "surface scorer")
-    if lowpass is not None and median is not None:
-        raise ValueError("lowpass and median are two smoothers for the same place: give one of them")
     channels, min_lengths = list(channels), list(min_lengths)
     lv = _surface_levels(levels)
-    C, T = probs.shape
     K, L = len(lv), len(min_lengths)
-    if C != len(channels):
-        raise ValueError(f"{C} tracks for {len(channels)} channels")
-    fps_host = ls.fps_per_channel(fps, C, each=float)
-    out_shape = (C, K, L, len(FIELDS))
-    criteria = None if events is None else _event_criteria(events)
-    if T == 0 or 0 in out_shape:
-        if criteria is None:
-            return np.zeros(out_shape, np.int64)
-        ev = np.zeros(out_shape, np.int64)          # (nothing to launch on: no prediction, the events of each channel counted)
-        if 0 not in out_shape:
-            offsets = (index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)).offsets_host
-            ev[..., 0] = np.diff(offsets)[1::len(CLASSES)].reshape(C, 1, 1)
-        return np.zeros(out_shape, np.int64), ev
-    if lowpass is not None:
-        probs, dtype, _ = ls.device_track(ls.lowpass_device(probs, cutoff=lowpass, lengths=lengths), "surface scorer")
-    elif median is not None:
-        probs, dtype, _ = ls.device_track(ls.median_filter_device(probs, median, lengths=lengths), "surface scorer")
-    elif lengths is not None:
-        raise ValueError("lengths are the true frame counts for the low-pass: give a cutoff as well")
+    out_shape = (len(channels), K, L, len(FIELDS))
+    head, empty = _device_head(probs, "surface scorer", channels, out_shape[1:], fps, index, lowpass, median, lengths, events)
+    if head is None:
+        return empty
+    probs, dtype, dix, fps_host, criteria = head
+    C, T = probs.shape
     lib = _hip.lib()
-    dix = index if isinstance(index, DeviceIndex) else index.to_device(channels, probs.device)
-    if dix.channels != channels or dix.device != probs.device:
-        raise ValueError("the DeviceIndex was built for other channels or another device")
     size_query = "lad_surface_workspace_bytes" if criteria is None else "lad_surface_events_workspace_bytes"
-    ws_bytes = getattr(lib, size_query)(C, T, dix.n_intervals, K, L)
-    _hip.check(0 if ws_bytes >= 0 else _hip.LAD_ERR_INVALID, size_query)
-    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    mls = (ctypes.c_double * L)(*[float(m) for m in min_lengths])
     with torch.cuda.device(probs.device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=probs.device)
+        ws = _hip.workspace(size_query, C, T, dix.n_intervals, K, L, device=probs.device)
         scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
-        fps_dev = torch.from_numpy(fps_host).to(probs.device)
-        track_and_index = (_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(f64p), K, _hip.ptr(dix.bounds), _hip.ptr(dix.offsets),
-                           dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p), dix.n_intervals,
-                           _hip.ptr(fps_dev), fps_host.ctypes.data_as(f64p), mls, L)
+        ctx = {"fps_host": fps_host}
+        track_and_index = (_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K,
+                           *_index_and_lengths(dix, ctx, min_lengths))
         stream = _hip.stream_handle(probs.device)
         if criteria is None:
             _hip.check(lib.lad_score_surface(*track_and_index, _hip.ptr(ws), _hip.ptr(scores), stream), "lad_score_surface")

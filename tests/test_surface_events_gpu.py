@@ -12,7 +12,7 @@ import torch
 
 import _score_model as sm
 from oracle import recipe
-from test_surface_gpu import AWKWARD_FPS, CHANNELS, M, MIN_LENGTHS, NAMES, _index, _levels, _tile, _tracks
+from test_surface_gpu import AWKWARD_FPS, CHANNELS, M, MIN_LENGTHS, NAMES, _index, _lds_edge, _levels, _tile, _tracks
 
 pytestmark = pytest.mark.gpu
 
@@ -63,11 +63,12 @@ def test_device_equals_host_on_every_track_shape(size):
         assert host[1][:, :, :, 1].sum(axis=(1, 2)).min() > 0 and host[1][0, :, :, 2:].any()
 
 
-@pytest.mark.parametrize("K", [1, 2, 131])
+@pytest.mark.parametrize("K", [1, 2, 131, "lds_fits", "lds_over"])
 @pytest.mark.parametrize("L", [1, 3, 8])
 def test_level_and_min_length_counts(K, L):
     import sweep_eval as se
     t = _tile()
+    K = _lds_edge(9, L).get(K, K)                  # nine fields in this difference array (L = 1: 681 and 682 levels)
     T = 4 * t + 3
     tracks = [x.astype(np.float32) for x in _tracks(T, t)][:3] + [_tracks(T, t)[6].astype(np.float32)]
     channels = CHANNELS[:3] + [CHANNELS[6]]

@@ -5,6 +5,7 @@ sweep_eval.score_surface_host (which tests/test_surface_cpu.py holds to score_sw
 score_sweep_device, the kernels that were there before."""
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -92,13 +93,24 @@ def test_device_equals_host_on_every_track_shape(size):
         assert host[:, :, :, 0].sum(axis=(1, 2)).min() > 0 and host[0, :, :, 2:].any()
 
 
-@pytest.mark.parametrize("K", [1, 2, 131, "max"])
+def _lds_edge(fields, L):
+    """{"lds_fits": the largest K at which the nodes kernel still keeps the difference array of one channel in LDS, "lds_over": the
+    smallest at which it adds to global memory}: the array has K + 1 rows of L min_lengths x `fields` int64, and the entry point
+    takes LDS iff those bytes are at most MAX_PRIVATE_BYTES (csrc/lad_surface_tree.h; read from there, so the cases move with it)."""
+    import _hip
+    header = os.path.join(os.path.dirname(os.path.abspath(_hip.__file__)), "csrc", "lad_surface_tree.h")
+    kib = int(re.search(r"constexpr int MAX_PRIVATE_BYTES = (\d+) \* 1024;", open(header).read()).group(1))
+    rows = kib * 1024 // (L * fields * 8)
+    return {"lds_fits": rows - 1, "lds_over": rows}
+
+
+@pytest.mark.parametrize("K", [1, 2, 131, "max", "lds_fits", "lds_over"])
 @pytest.mark.parametrize("L", [1, 3, 8])
 def test_level_and_min_length_counts(K, L):
     import _hip
     import sweep_eval as se
     t = _tile()
-    K = int(_hip.lib().lad_surface_max_levels()) if K == "max" else K
+    K = {"max": int(_hip.lib().lad_surface_max_levels()), **_lds_edge(7, L)}.get(K, K)     # (L = 1: 876 and 877 levels)
     T = 4 * t + 3
     tracks = [x.astype(np.float32) for x in _tracks(T, t)][:3] + [_tracks(T, t)[6].astype(np.float32)]
     channels = CHANNELS[:3] + [CHANNELS[6]]
