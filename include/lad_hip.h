@@ -1151,6 +1151,57 @@ int lad_window_coverage(const int32_t *set_chan, const int64_t *first, const int
                         const int32_t *bounds, const int32_t *offsets, const int32_t *bounds_host, const int32_t *offsets_host,
                         int64_t n_intervals, int32_t n_channels, int32_t n_sets, int32_t *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bootstrap intervals of the sweep's figures (csrc/bootstrap.hip): a percentile bootstrap over recording units (channels or
+ * meetings).  Not in the reference, which writes point figures only.  The text below IS the specification
+ * (tests/_bootstrap_model.py is a second implementation of it, in Python integers and fractions).  Integers only: the device
+ * never rounds, and the host divides once per reported number.
+ *
+ * Units and replicates.  G units (1..lad_bootstrap_max_units()), B replicates (1..lad_bootstrap_max_replicates()).  Replicate b
+ * is G draws with replacement; weights[b][g] is how often unit g was drawn, so every row sums to G.
+ *
+ * Random words.  Draw i of replicate b is word i & 3 of philox4x32_10(counter = (i >> 2, b, 0, 0x424F4F54), key = (seed &
+ * 0xffffffff, seed >> 32)); the unit is mulhi(word, G) = (word * G) >> 32, the rule of lad_sample_segments.  The tag in word 3
+ * ("BOOT") keeps these draws apart from the sampler's 0x53414D50 and from the augmentation's small values.  The weights are a
+ * pure function of (seed, b, G): two evaluations with one seed see the same resamples.
+ *
+ * Sums.  x is int64 [G][M], one row of M integers per unit; sums[b][m] = sum over g of weights[b][g] * x[g][m], in 64-bit
+ * integers.  Contract: 0 <= x < 2^40, weights >= 0 and every weight row sums to at most 4096; every sum is then below 2^52.
+ * Values outside the contract give unspecified sums and never an access outside the buffers.  Integer addition has no order, so
+ * the bytes do not depend on how the product is tiled.
+ *
+ * Figures.  A figure is six int32: (num_col, num_mult, den_col_a, den_col_b, valid_col, empty_is_one); num_mult is 1 or 2,
+ * den_col_b and valid_col may be -1, empty_is_one is 0 or 1.  For replicate b: num = num_mult * sums[b][num_col]; den =
+ * sums[b][den_col_a], plus sums[b][den_col_b] unless den_col_b is -1.  The replicate is invalid when valid_col >= 0 and
+ * sums[b][valid_col] == 0, and when den == 0 and empty_is_one == 0; with den == 0 and empty_is_one == 1 it counts as the fraction
+ * 1 / 1 (the reference's rule: precision is 1 where nothing is predicted).  Both num and den are below 2^54.
+ *
+ * Order and quantiles.  v = the number of valid replicates of the figure.  The valid ones are ordered by the exact value
+ * num / den: num1 * den2 against num2 * den1 as 128-bit products; equal values by the replicate number, ascending.  Quantile
+ * q_num / q_den (0 < q_num < q_den, int32) is the pair (num, den) at rank max(ceil(q_num * v / q_den) - 1, 0) of that order, in
+ * integers; (-1, -1) when v == 0.
+ *
+ * Shared by the three calls: LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for a null
+ * pointer, a size out of range, an output overlapping an input or another output, a bad figure or a bad quantile.  Identical
+ * bytes on every call; no global atomics; nothing beyond the stated extents is written.
+ * ---------------------------------------------------------------------------------------------- */
+/* both 4096; neither needs a GPU */
+int64_t lad_bootstrap_max_units(void);
+int64_t lad_bootstrap_max_replicates(void);
+/* weights: DEVICE int32 [replicates][units].  One launch, one workgroup per replicate: the counts in an LDS histogram. */
+int lad_bootstrap_weights(int32_t units, int32_t replicates, uint64_t seed, int32_t *weights, void *stream);
+/* x: DEVICE int64 [units][columns]; weights: DEVICE int32 [replicates][units]; sums: DEVICE int64 [replicates][columns].
+ * columns 0..2^32; columns == 0 is LAD_OK without a launch (x and sums may be NULL then).  One launch. */
+int lad_bootstrap_sums(const int64_t *x, const int32_t *weights, int32_t units, int64_t columns, int32_t replicates, int64_t *sums,
+                       void *stream);
+/* sums: DEVICE int64 [replicates][columns], columns >= 1; figures: DEVICE int32 [n_figures][6] and figures_host, the same
+ * values on the HOST, checked before anything is launched (columns in range, num_mult 1 or 2, the flag 0 or 1); q_num, q_den:
+ * HOST int32 [n_quantiles], 1 <= n_quantiles <= 16; out: DEVICE int64 [n_figures][n_quantiles][2]; valid: DEVICE int32
+ * [n_figures].  n_figures == 0 is LAD_OK without a launch.  One launch, one workgroup per figure. */
+int lad_bootstrap_quantiles(const int64_t *sums, int64_t columns, int32_t replicates, const int32_t *figures,
+                            const int32_t *figures_host, int64_t n_figures, const int32_t *q_num, const int32_t *q_den,
+                            int32_t n_quantiles, int64_t *out, int32_t *valid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,13 @@ SIGNATURES = {
                                     c_i32, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lad_window_coverage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, ctypes.POINTER(c_i32),
                                     ctypes.POINTER(c_i32), c_i64, c_i32, c_i32, c_void_p, c_void_p]),
+    # bootstrap intervals of the sweep's figures: resample weights, weighted sums, exact quantiles (csrc/bootstrap.hip)
+    "lad_bootstrap_max_units": (c_i64, []),
+    "lad_bootstrap_max_replicates": (c_i64, []),
+    "lad_bootstrap_weights": (c_int, [c_i32, c_i32, ctypes.c_uint64, c_void_p, c_void_p]),
+    "lad_bootstrap_sums": (c_int, [c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p]),
+    "lad_bootstrap_quantiles": (c_int, [c_void_p, c_i64, c_i32, c_void_p, ctypes.POINTER(c_i32), c_i64, ctypes.POINTER(c_i32),
+                                        ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,237 @@
+"""Percentile bootstrap over recording units: resample weights, weighted integer sums, exact quantiles of ratios of sums.
+
+Not in the reference, whose analysis/analyse.py writes point figures only.  The convention stands in include/lad_hip.h above
+lad_bootstrap_weights (the Philox counter of a draw, the contract of the sums, the six integers of a figure, the order of two
+fractions, the rank of a quantile); tests/_bootstrap_model.py is a second implementation of it.
+
+    weights_host / weights_device      int32 (B, G): how often each of G units occurs in replicate b, a pure function of (seed, b, G)
+    sums_host / sums_device            int64 (B, M) = weights @ x for x int64 (G, M), 0 <= x < 2^40
+    select_host / quantiles_device     per figure the (num, den) pairs at the ranks of the quantiles, and the number of valid replicates
+    intervals_host / intervals_device  the three steps for a matrix of cells (a few columns per cell and one shared last column),
+                                       the device form in chunks of cells so that no sums buffer exceeds SUMS_BYTES_CAP
+
+The host forms are numpy and Python integers and never produce a float; the device forms are csrc/bootstrap.hip and have no CPU
+fallback.  Both return the same integers.  sweep_eval.bootstrap_sum_stats_host / _device build the rows from them.
+"""
+import ctypes
+from fractions import Fraction
+
+import numpy as np
+
+TAG = 0x424F4F54               # counter word 3 of a draw ("BOOT")
+MAX_UNITS = 4096               # include/lad_hip.h: lad_bootstrap_max_units()
+MAX_REPLICATES = 4096          # ... lad_bootstrap_max_replicates()
+MAX_VALUE = 1 << 40            # the contract of lad_bootstrap_sums: 0 <= x < 2^40
+SUMS_BYTES_CAP = 1 << 30       # intervals_device: no sums buffer is larger than this
+SHARED = -1                    # in a cell's figure template: the matrix's last column (shared by all cells)
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on uint64 arrays that hold 32-bit words (csrc/lad_philox.h) -> four such arrays."""
+    c0, c1, c2, c3 = (np.asarray(v, np.uint64) & _M32 for v in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(int(k0) & 0xFFFFFFFF), np.uint64(int(k1) & 0xFFFFFFFF)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2           # 32 x 32 -> 64: no overflow
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ k0) & _M32, p1 & _M32, ((p0 >> s32) ^ c3 ^ k1) & _M32, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0, c1, c2, c3
+
+
+def _check_sizes(G, B):
+    if not 1 <= G <= MAX_UNITS or not 1 <= B <= MAX_REPLICATES:
+        raise ValueError(f"units 1..{MAX_UNITS} and replicates 1..{MAX_REPLICATES}, got {G} and {B}")
+
+
+def weights_host(G, B, seed):
+    """int32 (B, G): draw i of replicate b is word i & 3 of philox4x32_10((i >> 2, b, 0, TAG), (seed lo, seed hi)), its unit
+    (word * G) >> 32.  Every row sums to G."""
+    _check_sizes(G, B)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    calls = (G + 3) // 4
+    c0 = np.broadcast_to(np.arange(calls, dtype=np.uint64)[None, :], (B, calls))
+    c1 = np.broadcast_to(np.arange(B, dtype=np.uint64)[:, None], (B, calls))
+    words = np.stack(philox4x32_10(c0, c1, np.zeros((B, calls), np.uint64), np.full((B, calls), TAG, np.uint64),
+                                   seed & 0xFFFFFFFF, seed >> 32), axis=2).reshape(B, 4 * calls)[:, :G]
+    units = ((words * np.uint64(G)) >> np.uint64(32)).astype(np.int64)
+    out = np.zeros((B, G), np.int32)
+    np.add.at(out, (np.repeat(np.arange(B), G), units.ravel()), 1)
+    return out
+
+
+def check_matrix(x):
+    """x as a contiguous int64 (G, M) array inside the contract of lad_bootstrap_sums (ValueError otherwise)."""
+    x = np.ascontiguousarray(x, dtype=np.int64)
+    if x.ndim != 2 or not 1 <= x.shape[0] <= MAX_UNITS:
+        raise ValueError(f"x must be (units, columns) with 1..{MAX_UNITS} units, got {x.shape}")
+    if x.size and (int(x.min()) < 0 or int(x.max()) >= MAX_VALUE):
+        raise ValueError(f"values of x must lie in 0 .. 2^40 - 1, got {int(x.min())} .. {int(x.max())}")
+    return x
+
+
+def sums_host(x, weights):
+    """int64 (B, M) = weights @ x (below 2^52 within the contract: int64 holds every partial sum)."""
+    return np.asarray(weights, np.int64) @ np.asarray(x, np.int64)
+
+
+def quantile_pairs(level):
+    """The two quantiles of a central interval of `level` per cent as exact (num, den) pairs: (100 - level) / 200 and 1 - that,
+    via Fraction(str(level)) (level 95 -> 1/40 and 39/40; "99.9" -> 1/2000 and 1999/2000)."""
+    lo = (100 - Fraction(str(level))) / 200
+    if not 0 < lo < Fraction(1, 2):
+        raise ValueError(f"level must lie strictly between 0 and 100, got {level}")
+    hi = 1 - lo
+    if hi.denominator >= 2 ** 31:
+        raise ValueError(f"level {level} needs a denominator beyond int32")
+    return [(lo.numerator, lo.denominator), (hi.numerator, hi.denominator)]
+
+
+def rank_of(q_num, q_den, v):
+    """max(ceil(q_num * v / q_den) - 1, 0), in integers."""
+    return max(-((-q_num * v) // q_den) - 1, 0)
+
+
+_KEY_SHIFT = 110
+
+
+def _key(num, den):
+    """An integer that orders fractions with 0 < den < 2^54 exactly as their values: floor(num * 2^110 / den).  Two different
+    values differ by at least 1 / (den1 * den2) > 2^-108, so their scaled forms differ by more than 4 and the floors keep the
+    order; equal values have equal floors."""
+    return (num << _KEY_SHIFT) // den
+
+
+def select_host(sums, figures, quantiles):
+    """sums int64 (B, M); figures [(num_col, num_mult, den_col_a, den_col_b, valid_col, empty_is_one)]; quantiles [(num, den)]
+    -> (out int64 (F, Q, 2), valid int32 (F,)).  Python integers throughout."""
+    sums = np.asarray(sums, np.int64)
+    out = np.full((len(figures), len(quantiles), 2), -1, np.int64)
+    valid = np.zeros(len(figures), np.int32)
+    for f, (num_col, mult, den_a, den_b, valid_col, one) in enumerate(figures):
+        num = (sums[:, num_col] * mult).tolist()
+        den = (sums[:, den_a] + (sums[:, den_b] if den_b >= 0 else 0)).tolist()
+        good = (sums[:, valid_col] != 0).tolist() if valid_col >= 0 else [True] * len(num)
+        kept = []
+        for b, (n, d, g) in enumerate(zip(num, den, good)):
+            if d == 0:
+                if not one:
+                    continue
+                n = d = 1
+            if g:
+                if d >= 1 << 54:
+                    raise ValueError(f"figure {f}: a denominator of {d} is beyond the contract (below 2^54)")
+                kept.append((_key(n, d), b, n, d))
+        kept.sort()                                                                # by the exact value, then the replicate
+        valid[f] = len(kept)
+        if kept:
+            for j, (qn, qd) in enumerate(quantiles):
+                out[f, j] = kept[rank_of(qn, qd, len(kept))][2:]
+    return out, valid
+
+
+def weights_device(G, B, seed, device="cuda"):
+    """weights_host on the GPU (lad_bootstrap_weights): int32 (B, G) tensor."""
+    import torch
+
+    import _hip
+    _check_sizes(G, B)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _hip.LadHipError("the bootstrap's device form has no CPU fallback")
+    with torch.cuda.device(device):
+        w = torch.empty((B, G), dtype=torch.int32, device=device)
+        _hip.check(_hip.lib().lad_bootstrap_weights(G, B, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(w), _hip.stream_handle(device)),
+                   "lad_bootstrap_weights")
+    return w
+
+
+def sums_device(x, weights):
+    """x int64 (G, M) and weights int32 (B, G), both GPU tensors -> int64 (B, M) tensor (lad_bootstrap_sums).  The caller has
+    checked the contract (check_matrix) where x was still on the host."""
+    import torch
+
+    import _hip
+    _hip.require_cuda(x, "x", torch.int64)
+    _hip.require_cuda(weights, "weights", torch.int32)
+    (G, M), B = x.shape, weights.shape[0]
+    if weights.shape != (B, G):
+        raise ValueError(f"weights {tuple(weights.shape)} for {G} units")
+    with torch.cuda.device(x.device):
+        sums = torch.empty((B, M), dtype=torch.int64, device=x.device)
+        _hip.check(_hip.lib().lad_bootstrap_sums(_hip.ptr(x), _hip.ptr(weights), G, M, B, _hip.ptr(sums), _hip.stream_handle(x.device)),
+                   "lad_bootstrap_sums")
+    return sums
+
+
+def quantiles_device(sums, figures, quantiles):
+    """select_host for sums in GPU memory (lad_bootstrap_quantiles): only out and valid cross to the host."""
+    import torch
+
+    import _hip
+    _hip.require_cuda(sums, "sums", torch.int64)
+    B, M = sums.shape
+    figures_host = np.ascontiguousarray(np.asarray(figures, np.int32).reshape(-1, 6))
+    F, Q = len(figures_host), len(quantiles)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    with torch.cuda.device(sums.device):
+        fig = torch.from_numpy(figures_host if F else np.zeros((1, 6), np.int32)).to(sums.device)
+        out = torch.empty((max(F, 1), Q, 2), dtype=torch.int64, device=sums.device)
+        valid = torch.empty((max(F, 1),), dtype=torch.int32, device=sums.device)
+        q_num, q_den = ((ctypes.c_int32 * Q)(*[q[i] for q in quantiles]) for i in (0, 1))
+        _hip.check(_hip.lib().lad_bootstrap_quantiles(_hip.ptr(sums), M, B, _hip.ptr(fig), figures_host.ctypes.data_as(i32p), F, q_num, q_den, Q,
+                                                      _hip.ptr(out), _hip.ptr(valid), _hip.stream_handle(sums.device)),
+                   "lad_bootstrap_quantiles")
+        return out[:F].cpu().numpy(), valid[:F].cpu().numpy()
+
+
+def cell_figures(template, cell, per_cell, shared_col):
+    """The figures of one cell from its template: a template column c >= 0 is column cell * per_cell + c, SHARED is shared_col;
+    -1 in den_col_b / valid_col ("none") is written as None in the template."""
+    def col(c):
+        return -1 if c is None else shared_col if c == SHARED else cell * per_cell + c
+    return [(col(n), mult, col(a), col(b), col(v), one) for n, mult, a, b, v, one in template]
+
+
+def _split(x, per_cell):
+    n_cells, rest = divmod(x.shape[1] - 1, per_cell)
+    if rest:
+        raise ValueError(f"{x.shape[1]} columns are not cells of {per_cell} and one shared column")
+    return n_cells
+
+
+def intervals_host(x, per_cell, template, n_boot, seed, quantiles):
+    """x int64 (G, n_cells * per_cell + 1): per cell `per_cell` columns, then one column shared by all cells.  template: the
+    figures of a cell (cell_figures).  -> (out int64 (n_cells, len(template), Q, 2), valid int32 (n_cells, len(template)))."""
+    x = check_matrix(x)
+    n_cells = _split(x, per_cell)
+    sums = sums_host(x, weights_host(x.shape[0], n_boot, seed))
+    figures = [f for cell in range(n_cells) for f in cell_figures(template, cell, per_cell, x.shape[1] - 1)]
+    out, valid = select_host(sums, figures, quantiles)
+    return out.reshape(n_cells, len(template), len(quantiles), 2), valid.reshape(n_cells, len(template))
+
+
+def intervals_device(x, per_cell, template, n_boot, seed, quantiles, device="cuda", cap=None):
+    """intervals_host on the GPU: the matrix is uploaded once, the weights are drawn once, and the cells go through
+    lad_bootstrap_sums + lad_bootstrap_quantiles in chunks whose sums buffer (n_boot rows of the chunk's columns and the shared
+    one, int64) stays within `cap` bytes (default SUMS_BYTES_CAP; at least one cell a chunk).  Equal to intervals_host whatever the
+    chunk size."""
+    import torch
+    x = check_matrix(x)
+    n_cells = _split(x, per_cell)
+    cap = SUMS_BYTES_CAP if cap is None else cap
+    step = max(1, (cap // (8 * n_boot) - 1) // per_cell)
+    weights = weights_device(x.shape[0], n_boot, seed, device)
+    xd = torch.from_numpy(x).to(weights.device)
+    outs, valids = [], []
+    for c0 in range(0, n_cells, step):
+        n = min(step, n_cells - c0)
+        chunk = torch.cat([xd[:, c0 * per_cell:(c0 + n) * per_cell], xd[:, -1:]], dim=1).contiguous()
+        figures = [f for cell in range(n) for f in cell_figures(template, cell, per_cell, n * per_cell)]
+        out, valid = quantiles_device(sums_device(chunk, weights), figures, quantiles)
+        outs.append(out)
+        valids.append(valid)
+    Q = len(quantiles)
+    out = np.concatenate(outs) if outs else np.zeros((0, Q, 2), np.int64)
+    valid = np.concatenate(valids) if valids else np.zeros(0, np.int32)
+    return out.reshape(n_cells, len(template), Q, 2), valid.reshape(n_cells, len(template))

@@ -46,6 +46,13 @@ nested in the threshold.  Without the flag the files are what they were.
 sweep_eval.event_pr_summary), both score arrays from the same component tree (sweep_eval.score_surface_host(..., events=) under
 the host scorer, csrc/surface_events.hip through sweep_eval.score_surface_device(..., events=) under the device scorer).  It
 cannot be combined with --thresholds, --threshold_grid, --events, --offset_drops, --min_gaps or --penalties.
+`--bootstrap B` (default: absent; not in the reference) also writes `sum_stats_ci.csv`: per setting precision, recall and F1 with a
+percentile-bootstrap interval each and the number of valid replicates (sweep_eval.bootstrap_sum_stats_host under the host scorer,
+csrc/bootstrap.hip through sweep_eval.bootstrap_sum_stats_device under the device scorer: the same bytes), from B resamples of the
+recording units (`--bootstrap_unit channel`, the default, or `meeting`), the resamples a pure function of `--bootstrap_seed`
+(default 0), the interval the central `--bootstrap_level` per cent (default 95).  With `--events` or `--event_grid` it also writes
+`event_sum_stats_ci.csv` (event precision and recall; event F1 is not a ratio of sums and has no interval).  It works with every
+decoder family and both grids.  Without the flag the directory holds what it held before.
 """
 import argparse
 import csv
@@ -63,6 +70,7 @@ import laugh_segmenter  # noqa: E402
 import sweep_eval  # noqa: E402
 
 SURFACE_MAX_LEVELS = 4096      # include/lad_hip.h: lad_surface_max_levels() (the host scorer takes the same grids)
+MAX_REPLICATES = 4096          # ... lad_bootstrap_max_replicates()
 
 
 def read_csv(path, columns, numeric):
@@ -143,6 +151,24 @@ def grid_size(text):
     return value
 
 
+def replicates_arg(text):
+    """--bootstrap: as many replicates as one call of lad_bootstrap_quantiles takes (the host form takes the same range)."""
+    value = int(text)
+    if not 1 <= value <= MAX_REPLICATES:
+        raise argparse.ArgumentTypeError(f"an integer in 1..{MAX_REPLICATES}, got {text}")
+    return value
+
+
+def level_arg(text):
+    """--bootstrap_level: a decimal strictly between 0 and 100, kept as text (bootstrap.quantile_pairs reads it exactly)."""
+    try:
+        import bootstrap
+        bootstrap.quantile_pairs(text)
+    except (ValueError, ZeroDivisionError):
+        raise argparse.ArgumentTypeError(f"a decimal strictly between 0 and 100, got {text}")
+    return text
+
+
 def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, median=None, **axes_and_events):
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
@@ -210,6 +236,17 @@ def build_parser():
                              'laughter), and at least 1; default: 1')
     parser.add_argument('--event_min_overlap_pct', type=percent, default=0,
                         help='... and at least this many per cent of it (of its part outside INVALID), 0..100; default: 0')
+    parser.add_argument('--bootstrap', type=replicates_arg, default=None, metavar='B',
+                        help='(not in the reference) also write sum_stats_ci.csv (and event_sum_stats_ci.csv with --events / '
+                             f'--event_grid): percentile-bootstrap intervals from B resamples of the recording units, B in 1..{MAX_REPLICATES}; '
+                             'default: absent')
+    parser.add_argument('--bootstrap_seed', type=non_negative_int, default=0,
+                        help='the resamples are a pure function of this seed and the replicate number; default: 0')
+    parser.add_argument('--bootstrap_level', type=level_arg, default='95', metavar='PERCENT',
+                        help='the central interval reported, read as an exact decimal (95 -> the quantiles 1/40 and 39/40); default: 95')
+    parser.add_argument('--bootstrap_unit', type=str, default='channel', choices=['channel', 'meeting'],
+                        help='what is resampled: the evaluated channels, or the meetings (three meetings have ten distinct '
+                             'resamples); default: channel')
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
 
@@ -289,6 +326,14 @@ def main(argv=None):
         if args.event_grid is not None:
             write_csv(os.path.join(args.out_dir, "event_pr_summary.csv"), sweep_eval.EVENT_PR_COLUMNS,
                       sweep_eval.event_pr_summary(event_stats))
+    if args.bootstrap is not None:
+        resample = sweep_eval.bootstrap_sum_stats_device if args.scorer == "device" else sweep_eval.bootstrap_sum_stats_host
+        ci = resample(scores, channels, thresholds, min_lengths, index, n_boot=args.bootstrap, seed=args.bootstrap_seed,
+                      level=args.bootstrap_level, unit=args.bootstrap_unit, events=events if with_events else None, **extra)
+        if with_events:
+            ci, event_ci = ci
+            write("event_sum_stats_ci.csv", sweep_eval.EVENT_SUM_CI_COLUMNS, event_ci)
+        write("sum_stats_ci.csv", sweep_eval.SUM_CI_COLUMNS, ci)
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

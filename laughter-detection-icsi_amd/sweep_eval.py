@@ -31,6 +31,10 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
                            (scores, events), the second from event_scores_instances / csrc/events.hip
     event_rows             per (meeting, threshold, min_len) event precision, recall, F1, fragmentation and boundary errors
     event_sum_stats        the same figures over all meetings
+    bootstrap_units        the resampling unit (channel or meeting) of every evaluated channel, and each unit's transcribed ms
+    bootstrap_sum_stats_host    percentile-bootstrap intervals of precision, recall and F1 (and of event precision / recall with
+                           events=) over those units: exact quantiles of ratios of integer sums (bootstrap.py)
+    bootstrap_sum_stats_device  the same rows from csrc/bootstrap.hip.  No CPU fallback.
 
 Everything is integer arithmetic plus a few IEEE float64 operations, so host and device agree exactly.
 """
@@ -39,6 +43,7 @@ import operator
 
 import numpy as np
 
+import bootstrap
 import laugh_segmenter as ls
 
 CLASSES = ("invalid", "laugh", "speech", "noise", "silence")          # include/lad_hip.h: enum lad_score_class
@@ -221,6 +226,12 @@ class TranscriptIndex:
 
     def tot_events(self, meeting_id, kind="laugh"):
         return self._tot[meeting_id][kind][1]
+
+    def laugh_ms(self, meeting_id, part_id=None):
+        """The integer milliseconds behind tot_len(meeting_id, "laugh"): the sum of max(hi - lo, 0) over the rows filed under
+        "laugh" (not the length of their union), of the whole meeting or of one participant."""
+        return sum(max(hi - lo, 0) for (m, part), raw in self._raw.items() if m == meeting_id and part_id in (None, part)
+                   for lo, hi in raw["laugh"])
 
     def num_laugh_rows(self, meeting_id):
         """Rows of type laugh in the input table (parse.laugh_only_df of the meeting: analyse.py:163-164)."""
@@ -816,3 +827,132 @@ def event_sum_stats(rows, binarize=False, penalties=None, offset_drops=None, min
         for i, x in enumerate(list(v[:6]) + ms):
             acc[i] += int(x)
     return [[key[1], key[0], *key[2:], *_event_figures(*sums[key])] for key in sorted(sums)]
+
+
+# ---- bootstrap intervals of the summary figures (bootstrap.py; csrc/bootstrap.hip) ---------------------------------------------
+SUM_CI_COLUMNS = ["threshold", "min_len", "precision", "precision_lo", "precision_hi", "recall", "recall_lo", "recall_hi", "f1", "f1_lo",
+                  "f1_hi", "n_boot_valid"]
+EVENT_SUM_CI_COLUMNS = ["threshold", "min_len", "event_precision", "event_precision_lo", "event_precision_hi", "event_recall",
+                        "event_recall_lo", "event_recall_hi", "n_boot_valid"]
+# A cell of the time matrix holds (pred_ms, corr_ms), a cell of the event matrix (n_valid, pred_hit, ref_hit, n_ref); the shared
+# last column of both is the unit's transcribed milliseconds.  The figures of a cell, as bootstrap.cell_figures reads them:
+_S = bootstrap.SHARED
+_TIME_FIGURES = [(1, 1, 0, None, None, 1),          # precision = corr / pred, 1 where nothing is predicted
+                 (1, 1, _S, None, None, 0),         # recall = corr / transcribed, invalid where nothing is transcribed
+                 (1, 2, 0, _S, _S, 0)]              # F1 = 2 corr / (pred + transcribed), invalid where recall is
+_EVENT_FIGURES = [(1, 1, 0, None, None, 1),         # event precision = pred_hit / n_valid, 1 without a valid prediction
+                  (2, 1, 3, None, None, 0)]         # event recall = ref_hit / n_ref, invalid without an event
+
+
+def bootstrap_units(channels, index, unit="channel"):
+    """The resampling unit of every evaluated channel: (unit_of, transc_ms).  unit_of[c] is the unit number of channels[c], -1 for
+    a channel without a participant (left out, as in eval_rows); transc_ms[g] the transcribed laughter of unit g in integer
+    milliseconds (TranscriptIndex.laugh_ms).  unit="channel": every evaluated channel is a unit, in the order given, with its
+    participant's milliseconds; unit="meeting": the meetings with an evaluated channel, ascending, with the meeting's."""
+    if unit not in ("channel", "meeting"):
+        raise ValueError(f"unit is 'channel' or 'meeting', got {unit!r}")
+    evaluated = [(c, m, index.participant(m, chan)) for c, (m, chan) in enumerate(channels)]
+    evaluated = [(c, m, part) for c, m, part in evaluated if part is not None]
+    unit_of = [-1] * len(channels)
+    if unit == "channel":
+        for g, (c, _, _) in enumerate(evaluated):
+            unit_of[c] = g
+        return unit_of, [index.laugh_ms(m, part) for _, m, part in evaluated]
+    meetings = sorted({m for _, m, _ in evaluated})
+    for c, m, _ in evaluated:
+        unit_of[c] = meetings.index(m)
+    return unit_of, [index.laugh_ms(m) for m in meetings]
+
+
+def _unit_matrix(fields, unit_of, transc_ms):
+    """int64 (G, n_cells * F + 1): fields (C, n_cells, F) summed over the channels of every unit, then the shared column."""
+    G = len(transc_ms)
+    per_unit = np.zeros((G,) + fields.shape[1:], np.int64)
+    evaluated = [c for c, g in enumerate(unit_of) if g >= 0]
+    np.add.at(per_unit, [unit_of[c] for c in evaluated], fields[evaluated])
+    return np.concatenate([per_unit.reshape(G, -1), np.asarray(transc_ms, np.int64).reshape(G, 1)], axis=1)
+
+
+def _ratio(num, den):
+    """One IEEE division of two integers (Python's int / int is correctly rounded); NaN for the pair (-1, -1) of an empty order."""
+    return float("nan") if num < 0 else int(num) / int(den)
+
+
+def _bootstrap_sum_stats(intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events, offset_drops,
+                         min_gaps, penalties):
+    scores = np.asarray(scores)
+    axes = ls.decoder_for(offset_drops, min_gaps, penalties)[1]
+    cells = _cells(list(thresholds), list(min_lengths), axes)
+    if scores.shape != _score_shape(len(channels), list(thresholds), list(min_lengths), axes):
+        raise ValueError(f"scores {scores.shape} are not of this sweep")
+    if events is not None and np.asarray(events).shape != scores.shape:
+        raise ValueError(f"scores {scores.shape} and events {np.asarray(events).shape} are not of one sweep")
+    unit_of, transc_ms = bootstrap_units(channels, index, unit)
+    if not transc_ms:
+        raise ValueError("no channel with a participant: nothing to resample")
+    quantiles = bootstrap.quantile_pairs(level)
+    order = sorted(range(len(cells)), key=lambda j: (cells[j][2], cells[j][1], *cells[j][3]))          # calc_sum_stats' order
+    flat = scores.reshape(len(channels), len(cells), len(FIELDS))                  # (_cells runs in the array's own order)
+    nan = float("nan")
+
+    def rows_of(x, per_cell, template, point):
+        out, valid = intervals(x, per_cell, template, n_boot, seed, quantiles)
+        total = [int(v) for v in x.sum(axis=0)]
+        rows = []
+        for j in order:
+            _, thr, min_l, extra = cells[j]
+            row = [thr, min_l, *extra]
+            for f, figure in enumerate(point(total[j * per_cell:(j + 1) * per_cell], total[-1])):
+                row += [figure, _ratio(*out[j, f, 0]), _ratio(*out[j, f, 1])]
+            rows.append(row + [int(valid[j].min())])
+        return rows
+
+    def time_point(cell, transc):
+        pred, corr = cell
+        return (1.0 if pred == 0 else corr / pred, nan if transc == 0 else corr / transc, nan if transc == 0 else 2 * corr / (pred + transc))
+
+    def event_point(cell, _):
+        n_valid, pred_hit, ref_hit, n_ref = cell
+        return (1.0 if n_valid == 0 else pred_hit / n_valid, nan if n_ref == 0 else ref_hit / n_ref)
+
+    time_rows = rows_of(_unit_matrix(flat[:, :, 2:4], unit_of, transc_ms), 2, _TIME_FIGURES, time_point)
+    if events is None:
+        return time_rows
+    ev = np.asarray(events).reshape(flat.shape[0], flat.shape[1], len(EVENT_FIELDS))
+    fields = np.stack([flat[:, :, 1], ev[:, :, 3], ev[:, :, 2], ev[:, :, 0]], axis=2)
+    return time_rows, rows_of(_unit_matrix(fields, unit_of, transc_ms), 4, _EVENT_FIGURES, event_point)
+
+
+def bootstrap_sum_stats_host(scores, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95, unit="channel", events=None,
+                             offset_drops=None, min_gaps=None, penalties=None):
+    """Percentile-bootstrap intervals of calc_sum_stats' figures over recording units (include/lad_hip.h: lad_bootstrap_weights has
+    the convention).  scores: the array of any of the four scorers for `channels`; the decoder's lists as eval_rows takes them.
+    The units (bootstrap_units: channels, or meetings) are resampled with replacement n_boot times, the weights a pure function of
+    (seed, replicate), so two evaluations with one seed see the same resamples; every figure is recomputed on each resample as a
+    ratio of integer sums, the replicates are ordered exactly, and the quantiles (100 - level) / 200 and 1 - that (exact rationals:
+    Fraction(str(level))) are one replicate's pair each, divided once.
+    Returns rows of SUM_CI_COLUMNS (the decoder's axes behind min_len: columns(SUM_CI_COLUMNS, decoder)), in calc_sum_stats' order:
+    threshold, min_len, precision, precision_lo, precision_hi, recall, ..., f1, f1_lo, f1_hi, n_boot_valid.  The point figures come
+    from the plain unit sums: precision = corr_ms / pred_ms (1 at zero predicted time), recall = corr_ms / transcribed ms,
+    f1 = 2 corr_ms / (pred_ms + transcribed ms) (both NaN at zero transcribed time); a replicate with zero transcribed time is
+    invalid for recall and f1, n_boot_valid is the smallest number of valid replicates among the row's three figures, and an
+    interval without a valid replicate is NaN.
+    events: the second array of a scorer called with events= -> (rows, event rows), the second of EVENT_SUM_CI_COLUMNS:
+    event_precision = pred_hit / n_valid (1 without a valid prediction), event_recall = ref_hit / n_ref (valid iff n_ref > 0).
+    Event F1 is not a ratio of sums and has no interval here; nor have average precision or the difference of two systems.
+    This is the parity form: numpy and Python integers, no float before the final division."""
+    return _bootstrap_sum_stats(bootstrap.intervals_host, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events,
+                                offset_drops, min_gaps, penalties)
+
+
+def bootstrap_sum_stats_device(scores, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95, unit="channel", events=None,
+                               offset_drops=None, min_gaps=None, penalties=None, device="cuda"):
+    """bootstrap_sum_stats_host on the GPU (csrc/bootstrap.hip through bootstrap.intervals_device): the per-unit matrix is checked
+    on the host (0 <= x < 2^40) and uploaded once, the cells go through lad_bootstrap_sums and lad_bootstrap_quantiles in chunks
+    whose sums buffer stays within bootstrap.SUMS_BYTES_CAP, and only the selected pairs and the valid counts come back.  Equal
+    rows (NaN matching NaN) whatever the chunk size.  No CPU fallback."""
+
+    def intervals(x, per_cell, template, n_boot, seed, quantiles):
+        return bootstrap.intervals_device(x, per_cell, template, n_boot, seed, quantiles, device=device)
+    return _bootstrap_sum_stats(intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events, offset_drops,
+                                min_gaps, penalties)
