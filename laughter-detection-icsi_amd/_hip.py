@@ -335,3 +335,61 @@ def ptr(t):
 
 def stream_handle(device=None):
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# host-array slots: the numpy dtype a POINTER(...) parameter reads
+_HOST_DTYPES = {ctypes.POINTER(c_double): np.dtype(np.float64), ctypes.POINTER(c_float): np.dtype(np.float32),
+                ctypes.POINTER(c_i32): np.dtype(np.int32), ctypes.POINTER(c_i64): np.dtype(np.int64)}
+_PLAIN = frozenset((int, float, type(None)))     # what most arguments are: passed on without a second look
+
+
+def _marshal(name, args, a, index):
+    """The slow half of launch(): a host array as the pointer its slot takes, or LadHipError for the array or tensor `a` that may
+    not go where it stands (a tensor that launch() did not take: not in GPU memory, or not on the launch device `index`)."""
+    i = next(k for k, x in enumerate(args) if x is a)
+    argtype = SIGNATURES[name][1][i]
+    where = f"{name}: argument {i + 1}"      # (counted from 1, as ctypes counts)
+    if isinstance(a, torch.Tensor):
+        raise LadHipError(f"{where} must be a GPU tensor on device {index}, got one on {a.device} (a host pointer in a kernel argument "
+                          "is a GPU fault, not an exception)")
+    want = _HOST_DTYPES.get(argtype)
+    if want is None:
+        raise LadHipError(f"{where} is a host array, but the parameter is {'a device pointer' if argtype is c_void_p else 'no host array'}")
+    if a.dtype != want or not a.flags.c_contiguous:
+        raise LadHipError(f"{where} must be a C-contiguous {want.name} array, got {a.dtype}{'' if a.flags.c_contiguous else ', not contiguous'}")
+    return a.ctypes.data_as(argtype)
+
+
+def launch(name, *args, stream=None, device=None, tag="", may_decline=False):
+    """Call entry point `name` (one whose last parameter is the stream) with args and then the stream: `stream`, or the current
+    stream of `device`, or of the first tensor argument's device.  A tensor goes in as its data_ptr() and must lie in GPU memory,
+    on the launch device; a numpy array goes in as a pointer to its buffer and must stand in a POINTER(double | float | int32 |
+    int64) slot of SIGNATURES, C-contiguous and of exactly that dtype; None is NULL; everything else (ctypes arrays and pointers,
+    c_void_p values, structures, numbers) passes through.  A wrong argument count, tensor or array, or a value ctypes will not put
+    into its slot (a tensor's address in a host-array slot), raises LadHipError before the library is reached; a non-zero return
+    code raises what check() raises, for "<name> <tag>".  may_decline: LAD_NOT_COVERED is an answer, not an error: False then,
+    True when the kernel was launched.  (One comprehension, no per-call objects: a train step comes through here 150 times.)"""
+    if len(args) + 1 != len(SIGNATURES[name][1]):
+        raise LadHipError(f"{name} takes {len(SIGNATURES[name][1]) - 1} arguments and the stream, got {len(args)}")
+    if device is None:
+        index = next((a.get_device() for a in args if isinstance(a, torch.Tensor)), None)    # (None: no tensor among the arguments)
+        if index == -1:
+            index = -2     # host memory: no tensor's get_device() is -2, so every tensor is refused
+    elif device.type != "cuda":
+        index = -2
+    else:
+        index = device.index if device.index is not None else torch.cuda.current_device()
+    out = [a if a.__class__ in _PLAIN else
+           (a.data_ptr() if a.get_device() == index else _marshal(name, args, a, index)) if isinstance(a, torch.Tensor) else
+           _marshal(name, args, a, index) if isinstance(a, np.ndarray) else a for a in args]
+    if stream is None:
+        stream = torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if index is None else index)
+    try:
+        rc = getattr(lib(), name)(*out, stream)
+    except ctypes.ArgumentError as e:
+        raise LadHipError(f"{name}: {e}") from None
+    if rc != 0:
+        if may_decline and rc == LAD_NOT_COVERED:
+            return False
+        check(rc, name + " " + tag if tag else name)
+    return True

@@ -141,8 +141,7 @@ def weights_device(G, B, seed, device="cuda"):
         raise _hip.LadHipError("the bootstrap's device form has no CPU fallback")
     with torch.cuda.device(device):
         w = torch.empty((B, G), dtype=torch.int32, device=device)
-        _hip.check(_hip.lib().lad_bootstrap_weights(G, B, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(w), _hip.stream_handle(device)),
-                   "lad_bootstrap_weights")
+        _hip.launch("lad_bootstrap_weights", G, B, int(seed) & 0xFFFFFFFFFFFFFFFF, w)
     return w
 
 
@@ -159,8 +158,7 @@ def sums_device(x, weights):
         raise ValueError(f"weights {tuple(weights.shape)} for {G} units")
     with torch.cuda.device(x.device):
         sums = torch.empty((B, M), dtype=torch.int64, device=x.device)
-        _hip.check(_hip.lib().lad_bootstrap_sums(_hip.ptr(x), _hip.ptr(weights), G, M, B, _hip.ptr(sums), _hip.stream_handle(x.device)),
-                   "lad_bootstrap_sums")
+        _hip.launch("lad_bootstrap_sums", x, weights, G, M, B, sums)
     return sums
 
 
@@ -173,15 +171,12 @@ def quantiles_device(sums, figures, quantiles):
     B, M = sums.shape
     figures_host = np.ascontiguousarray(np.asarray(figures, np.int32).reshape(-1, 6))
     F, Q = len(figures_host), len(quantiles)
-    i32p = ctypes.POINTER(ctypes.c_int32)
     with torch.cuda.device(sums.device):
         fig = torch.from_numpy(figures_host if F else np.zeros((1, 6), np.int32)).to(sums.device)
         out = torch.empty((max(F, 1), Q, 2), dtype=torch.int64, device=sums.device)
         valid = torch.empty((max(F, 1),), dtype=torch.int32, device=sums.device)
         q_num, q_den = ((ctypes.c_int32 * Q)(*[q[i] for q in quantiles]) for i in (0, 1))
-        _hip.check(_hip.lib().lad_bootstrap_quantiles(_hip.ptr(sums), M, B, _hip.ptr(fig), figures_host.ctypes.data_as(i32p), F, q_num, q_den, Q,
-                                                      _hip.ptr(out), _hip.ptr(valid), _hip.stream_handle(sums.device)),
-                   "lad_bootstrap_quantiles")
+        _hip.launch("lad_bootstrap_quantiles", sums, M, B, fig, figures_host, F, q_num, q_den, Q, out, valid)
         return out[:F].cpu().numpy(), valid[:F].cpu().numpy()
 
 

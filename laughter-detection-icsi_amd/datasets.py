@@ -67,9 +67,7 @@ def gather_segments(store, chan, first, count, n_frames, pad, out=None):
     F = store.num_filters
     if out is None:
         out = torch.empty((n, n_frames, F), device=store.device, dtype=torch.float32)
-    _hip.check(_hip.lib().lad_gather_segments(_hip.ptr(ptrs), _hip.ptr(frames), _hip.ptr(chan), _hip.ptr(first), _hip.ptr(count), n,
-                                              n_frames, F, float(pad), _hip.ptr(out), _hip.stream_handle(store.device)),
-               "lad_gather_segments")
+    _hip.launch("lad_gather_segments", ptrs, frames, chan, first, count, n, n_frames, F, float(pad), out, device=store.device)
     return out
 
 
@@ -108,12 +106,9 @@ def gather_segments_augmented(store, chan, first, count, n_frames, pad, cfg, epo
     ptrs, frames = store.tables()
     if out is None:
         out = torch.empty((n, n_frames, F), device=store.device, dtype=torch.float32)
-    _hip.check(_hip.lib().lad_gather_segments_aug(_hip.ptr(ptrs), _hip.ptr(frames), _hip.ptr(chan), _hip.ptr(first), _hip.ptr(count), n,
-                                                  n_frames, F, float(pad), ctypes.byref(params),
-                                                  _hip.ptr(noise.index if noise is not None else None), len(noise) if noise is not None else 0,
-                                                  min(noise.frames) if noise is not None else 0, _hip.ptr(out),
-                                                  _hip.stream_handle(store.device)),
-               "lad_gather_segments_aug")
+    _hip.launch("lad_gather_segments_aug", ptrs, frames, chan, first, count, n, n_frames, F, float(pad), ctypes.byref(params),
+                noise.index if noise is not None else None, len(noise) if noise is not None else 0,
+                min(noise.frames) if noise is not None else 0, out, device=store.device)
     return out
 
 

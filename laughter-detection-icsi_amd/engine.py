@@ -15,7 +15,9 @@ step (no allocation inside the step).  Everything derived from the weights -- pa
 BatchNorm folds -- belongs to the model (_ConvParams / _BnParams, one record per layer); the layer table of an input geometry
 (_blocks_for) holds sizes and points at those records.
 """
+import contextlib
 import ctypes
+import functools
 import math
 import struct
 from typing import FrozenSet, NamedTuple, Optional, Tuple
@@ -37,6 +39,13 @@ BASE_WIDTHS = (64, 32, 16, 16)
 # fp16: windows whose level-1 / level-2 frame streams are computed in one go (engine.stream_super): five tensors of 5.8 KB per frame at
 # level 1 -- 10 GB for a 60-minute channel's 360,000 windows, 30 GB at this cap
 STREAM_SUPER_MAX = 1 << 20
+
+
+_NOT_TIMED = contextlib.nullcontext()
+
+
+class _Declined(Exception):
+    """Leaves the body of ResNetEngine._marked without an event pair (_try_launch)."""
 
 
 class _LazyLevels(dict):
@@ -467,7 +476,6 @@ class ResNetEngine:
         self._flat_p = self._flat_g = None
         self._plans = {}
         self._step_count = 0
-        self._lib = None
         self._grad_dirty = False  # flat grad buffer holds a gradient that must be accumulated into
         self._train_forwards = 0
         self._weights_version = 0
@@ -551,9 +559,11 @@ class ResNetEngine:
 
     # ------------------------------------------------------------------------------------ flat storage
     def lib(self):
-        if self._lib is None:
-            self._lib = _hip.lib()
-        return self._lib
+        return _hip.lib()
+
+    # The engine has no library handle of its own: every launch goes through _hip.launch, which calls _hip.lib().  `_lib` stays as
+    # the name under which tests and tools put a counting or wrapping proxy in the library's place, and take it out again.
+    _lib = property(lambda self: _hip._lib, lambda self, value: setattr(_hip, "_lib", value))
 
     def _named_params(self):
         return list(self.model.named_parameters())
@@ -793,8 +803,36 @@ class ResNetEngine:
         return p
 
     # ------------------------------------------------------------------------------------ helpers
-    def _st(self):
-        return _hip.stream_handle(self.device)
+    def _launch(self, name, *args, tag="", stream=None, may_decline=False):
+        """One checked launch on the engine's device: the current stream, or `stream` (the side stream's handle)."""
+        return _hip.launch(name, *args, stream=stream, device=self.device, tag=tag, may_decline=may_decline)
+
+    def _marked(self, label):
+        """Context manager: HIP events on the launch stream (torch's current stream) around the body when bench.py asked for per-kernel
+        timing of `label`; the pair is kept only when the body finished."""
+        if self.kernel_events is None or label not in self.kernel_events:
+            return _NOT_TIMED
+        return self._event_pair(label)
+
+    @contextlib.contextmanager
+    def _event_pair(self, label):
+        stream = torch.cuda.current_stream(self.device)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record(stream)
+        yield
+        end.record(stream)
+        self.kernel_events[label].append((start, end))
+
+    def _try_launch(self, label, name, *args, tag=""):
+        """A try-and-fall-back entry point: False when it answers LAD_NOT_COVERED (nothing was launched, no event pair is kept: the
+        caller falls back), True when the kernel was launched."""
+        try:
+            with self._marked(label):
+                if not self._launch(name, *args, tag=tag, may_decline=True):
+                    raise _Declined
+        except _Declined:
+            return False
+        return True
 
     def notify_weights_changed(self):
         """Parameters or running statistics were written behind the engine's back (a graph replay, a write through
@@ -820,23 +858,21 @@ class ResNetEngine:
         fresh = have is not None and have[0] == ver
         if fresh and have[1] >= need_dgrad and want <= have[2]:
             return
-        lib, st = self.lib(), self._st()
         if not (fresh and have[1] >= need_dgrad):
             table = self._pack_tables.get(need_dgrad)
             if table is None:  # device table of {w, wt, cout, cin, taps, mode} records: pointers never move
                 recs = [struct.pack("<QQiiii", par.w.data_ptr(), (par.wt_f if mode == 0 else par.wt_d).data_ptr(), par.cout, par.cin, par.taps, mode)
                         for par in self._convs.values() for mode in ((0, 1) if need_dgrad else (0,))]
                 table = self._pack_tables[need_dgrad] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
-            _hip.check(lib.lad_conv_pack_weights_multi(_hip.ptr(table[0]), table[1], st), "lad_conv_pack_weights_multi")
+            self._launch("lad_conv_pack_weights_multi", table[0], table[1])
         h2 = []
         for kind, name in sorted(want - have[2] if fresh else want):   # (a training step: both directions of every image)
             par = self._convs[name]
             if kind == "s2b3":   # both images in one launch
-                _hip.check(lib.lad_conv_s2b3_pack_weights_pair(_hip.ptr(par.w), _hip.ptr(par.shortcut.w), _hip.ptr(par.wt3_s2f),
-                                                               _hip.ptr(par.wt3_s2d), st), "lad_conv_s2b3_pack_weights_pair")
+                self._launch("lad_conv_s2b3_pack_weights_pair", par.w, par.shortcut.w, par.wt3_s2f, par.wt3_s2d)
             elif kind == "b3c":
                 for mode, wt in ((0, par.wt3_f), (1, par.wt3_d)):
-                    _hip.check(lib.lad_conv_b3c_pack_weights(_hip.ptr(par.w), mode, _hip.ptr(wt), par.cin, st), "lad_conv_b3c_pack_weights")
+                    self._launch("lad_conv_b3c_pack_weights", par.w, mode, wt, par.cin)
             else:
                 h2.append(par)
         if h2:
@@ -848,7 +884,7 @@ class ResNetEngine:
                 recs = [struct.pack("<QQii", par.w.data_ptr(), wt.data_ptr(), mode, par.cin) for par in h2
                         for mode, wt in ((0, par.wt2_f), (1, par.wt2_d))]
                 htab = self._pack_tables[hkey] = (torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(self.device), len(recs))
-            _hip.check(lib.lad_conv_h2_pack_weights_multi(_hip.ptr(htab[0]), htab[1], 0, st), "lad_conv_h2_pack_weights_multi")
+            self._launch("lad_conv_h2_pack_weights_multi", htab[0], htab[1], 0)
         self._packed = (ver, need_dgrad or have[1], want | have[2]) if fresh else (ver, need_dgrad, want)
 
     def _eval_prepare(self, half):
@@ -858,31 +894,14 @@ class ResNetEngine:
         if not half:
             self._pack_weights(need_dgrad=False)
         tag = self._state_tag()
-        lib, st = self.lib(), self._st()
         if self._folded != tag:
             for bn in (self.stem_bn, *self._bns.values()):
-                _hip.check(lib.lad_bn_fold(_hip.ptr(bn.g), _hip.ptr(bn.b), _hip.ptr(bn.rm), _hip.ptr(bn.rv), _hip.ptr(bn.conv_bias),
-                                           bn.c, _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]), st), "lad_bn_fold " + bn.name)
+                self._launch("lad_bn_fold", bn.g, bn.b, bn.rm, bn.rv, bn.conv_bias, bn.c, *bn.fold, tag=bn.name)
             self._folded = tag
         if half and self._f16_packed != tag:
             for par in self._convs.values():
-                _hip.check(lib.lad_f16_pack_weights(_hip.ptr(par.w), par.cout, par.cin, par.taps, _hip.ptr(par.wt_h), st),
-                           "lad_f16_pack_weights " + par.name)
+                self._launch("lad_f16_pack_weights", par.w, par.cout, par.cin, par.taps, par.wt_h, tag=par.name)
             self._f16_packed = tag
-
-    def _mark(self, label):
-        """HIP event on the launch stream (torch's current stream) when bench.py asked for per-kernel timing."""
-        if self.kernel_events is None or label not in self.kernel_events:
-            return None
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record(torch.cuda.current_stream(self.device))
-        return ev
-
-    def _mark_end(self, label, start):
-        if start is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record(torch.cuda.current_stream(self.device))
-            self.kernel_events[label].append((start, ev))
 
     def _schedule(self, B, H, W):
         """The schedule of a training step under the flags as they are now (built once per batch size, geometry and flag values)."""
@@ -904,58 +923,48 @@ class ResNetEngine:
         bx, bmask, bcoef = bn if bn is not None else (None, None, None)
         fn = conv_s1_entry(arith, cs.cin, in_coef is not None, abits is not None,
                            None if bn is None else "x" if bmask is None else "bits" if bmask.dtype == torch.int64 else "y")
-        P, fwd, h, w = _hip.ptr, direction == "fwd", cs.h_in, cs.w_in
-        wt = P(getattr(cs.par, {"h2": "wt2_", "b3": "wt3_", "f32": "wt_"}[arith] + ("f" if fwd else "d")))
+        fwd, h, w = direction == "fwd", cs.h_in, cs.w_in
+        wt = getattr(cs.par, {"h2": "wt2_", "b3": "wt3_", "f32": "wt_"}[arith] + ("f" if fwd else "d"))
         cio = (cs.cin, cs.cout) if fwd else (cs.cout, cs.cin)
         if fn == "lad_conv_h2":
-            args = (P(x), P(in_coef), wt, P(bias), P(addend), P(abits), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w, cs.cin)
+            args = (x, in_coef, wt, bias, addend, abits, out, partials, bx, bmask, bcoef, B, h, w, cs.cin)
         elif fn == "lad_conv_b3c_fwd_f32":
-            args = (P(x), wt, P(bias), P(addend), P(out), P(partials), B, h, w, cs.cin)
+            args = (x, wt, bias, addend, out, partials, B, h, w, cs.cin)
         elif fn == "lad_conv_b3c_fwd_f32_bnrelu":
-            args = (P(x), P(in_coef), wt, P(bias), P(out), P(partials), B, h, w, cs.cin)
+            args = (x, in_coef, wt, bias, out, partials, B, h, w, cs.cin)
         elif fn == "lad_conv_b3c_dgrad_bnstat":   # ReLU decisions recomputed from the BatchNorm's input (csrc/conv_b3.hip, STAT epilogue)
-            args = (P(x), wt, P(addend), P(out), P(partials), P(bx), P(bcoef), B, h, w, cs.cin)
+            args = (x, wt, addend, out, partials, bx, bcoef, B, h, w, cs.cin)
         elif fn == "lad_conv_b3_fwd_f32_gated":
-            args = (P(x), wt, P(bias), P(addend), P(abits), P(out), P(partials), B, h, w)
+            args = (x, wt, bias, addend, abits, out, partials, B, h, w)
         elif fn == "lad_conv_b3_dgrad_bnstat":    # + the sums of a BatchNorm that kept its own sign bits
-            args = (P(x), wt, P(addend), P(abits), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w)
+            args = (x, wt, addend, abits, out, partials, bx, bmask, bcoef, B, h, w)
         elif fn == "lad_conv_fwd":
-            args = (P(x), wt, P(bias), P(addend), P(out), P(partials), B, h, w, *cio, cs.taps)
+            args = (x, wt, bias, addend, out, partials, B, h, w, *cio, cs.taps)
         else:
-            args = (P(x), wt, P(addend), P(out), P(partials), P(bx), P(bmask), P(bcoef), B, h, w, *cio, cs.taps)
-        t0 = self._mark(label)
-        _hip.check(getattr(self.lib(), fn)(*args, self._st()), f"{fn}({direction}) {cs.name}")
-        self._mark_end(label, t0)
+            args = (x, wt, addend, out, partials, bx, bmask, bcoef, B, h, w, *cio, cs.taps)
+        with self._marked(label):
+            self._launch(fn, *args, tag=f"({direction}) {cs.name}")
 
     def _conv_fwd(self, cs, ch, x, out, partials, B, in_coef=None):
         """Forward convolution with bias; `partials` receives the per-tile sums of the BatchNorm that follows."""
         if cs.stride == 1:
             self._conv_s1(cs, ch.arith, "fwd", x, out, B, ch.label_fwd, in_coef=in_coef, bias=cs.par.b, partials=partials)
             return
-        t0 = self._mark(ch.label_fwd)
-        _hip.check(self.lib().lad_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(cs.par.b), _hip.ptr(out), _hip.ptr(partials),
-                                              B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, self._st()), "lad_conv_s2_fwd " + cs.name)
-        self._mark_end(ch.label_fwd, t0)
+        with self._marked(ch.label_fwd):
+            self._launch("lad_conv_s2_fwd", x, cs.par.wt_f, cs.par.b, out, partials, B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, tag=cs.name)
 
     def _bn_coef(self, bn, coef, partials, B, h, w):
-        lib, st = self.lib(), self._st()
-        n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
-        _hip.check(lib.lad_bn_finalize(_hip.ptr(partials), n_tiles, bn.c, B * h * w, _hip.ptr(bn.g), _hip.ptr(bn.b),
-                                       _hip.ptr(bn.rm), _hip.ptr(bn.rv), 0.1, _hip.ptr(coef), st),
-                   "lad_bn_finalize " + bn.name)
+        n_tiles = int(self.lib().lad_conv_num_tiles(B, h, w))
+        self._launch("lad_bn_finalize", partials, n_tiles, bn.c, B * h * w, bn.g, bn.b, bn.rm, bn.rv, 0.1, coef, tag=bn.name)
 
     def _bn_coef_pair(self, bn_a, coef_a, part_a, bn_b, coef_b, part_b, B, h, w):
         """_bn_coef for a stride-2 block's bn1 and its shortcut BatchNorm (sums of one shape, left by one launch) in one launch."""
-        lib, st = self.lib(), self._st()
-        n_tiles = int(lib.lad_conv_num_tiles(B, h, w))
-        _hip.check(lib.lad_bn_finalize_pair(_hip.ptr(part_a), _hip.ptr(part_b), n_tiles, bn_a.c, B * h * w,
-                                            _hip.ptr(bn_a.g), _hip.ptr(bn_a.b), _hip.ptr(bn_a.rm), _hip.ptr(bn_a.rv), _hip.ptr(coef_a),
-                                            _hip.ptr(bn_b.g), _hip.ptr(bn_b.b), _hip.ptr(bn_b.rm), _hip.ptr(bn_b.rv), _hip.ptr(coef_b),
-                                            0.1, st), "lad_bn_finalize_pair " + bn_a.name)
+        n_tiles = int(self.lib().lad_conv_num_tiles(B, h, w))
+        self._launch("lad_bn_finalize_pair", part_a, part_b, n_tiles, bn_a.c, B * h * w, bn_a.g, bn_a.b, bn_a.rm, bn_a.rv, coef_a,
+                     bn_b.g, bn_b.b, bn_b.rm, bn_b.rv, coef_b, 0.1, tag=bn_a.name)
 
     def _bn_act(self, x, coef, res, rcoef, y, B, h, w, c, relu=1):
-        _hip.check(self.lib().lad_bn_act(_hip.ptr(x), _hip.ptr(coef), _hip.ptr(res), _hip.ptr(rcoef), _hip.ptr(y), B, h, w, c,
-                                         relu, self._st()), "lad_bn_act")
+        self._launch("lad_bn_act", x, coef, res, rcoef, y, B, h, w, c, relu)
 
     # ------------------------------------------------------------------------------------ forward
     def forward(self, x, train, labels=None, drop_masks=None):
@@ -983,7 +992,6 @@ class ResNetEngine:
             # torch: "Expected more than 1 value per channel when training" (BatchNorm1d on (1, F))
             raise ValueError("Expected more than 1 value per channel when training, got input size "
                              f"torch.Size([{B}, {self.model.linear_layer_size}])")
-        lib, st = self.lib(), self._st()
         p = self._plan(B, H, W, True)
         blocks = p["blocks"]
         # the kernel choices of this pass and of its backward, which reads them from the plan (virtual activations that were never
@@ -999,17 +1007,14 @@ class ResNetEngine:
             # ... and its batch statistics need no convolution pass at all: one input channel, so sum x and sum x^2 are combinations of 54
             # moments of the nine taps (csrc/stem.hip, lad_stem_bn_stats: one pass over the 9 MB of features)
             bn = self.stem_bn
-            _hip.check(lib.lad_stem_bn_stats(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(bn.g), _hip.ptr(bn.b), _hip.ptr(bn.rm), _hip.ptr(bn.rv),
-                                             0.1, _hip.ptr(p["stem_coef"]), _hip.ptr(p["stem_mom"]), _hip.ptr(p["stem_mom_ws"]), B, H, W,
-                                             self.stem_cout, st), "lad_stem_bn_stats")
+            self._launch("lad_stem_bn_stats", x, self.stem_w, bn.g, bn.b, bn.rm, bn.rv, 0.1, p["stem_coef"], p["stem_mom"], p["stem_mom_ws"],
+                         B, H, W, self.stem_cout)
         else:
-            _hip.check(lib.lad_stem_fwd(_hip.ptr(x), _hip.ptr(self.stem_w), None, _hip.ptr(part), B, H, W, self.stem_cout, st),
-                       "lad_stem_fwd")
+            self._launch("lad_stem_fwd", x, self.stem_w, None, part, B, H, W, self.stem_cout)
             self._bn_coef(self.stem_bn, p["stem_coef"], part, B, H, W)
         c0 = self.stem_cout
         scale, shift = p["stem_coef"][:c0], p["stem_coef"][c0:2 * c0]
-        _hip.check(lib.lad_stem_fwd_eval(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(scale), _hip.ptr(shift), _hip.ptr(p["stem_a"]),
-                                         B, H, W, c0, H, B * H, st), "lad_stem_fwd_eval (train)")
+        self._launch("lad_stem_fwd_eval", x, self.stem_w, scale, shift, p["stem_a"], B, H, W, c0, H, B * H, tag="(train)")
         cur = p["stem_a"]
         for b, ch, a in zip(blocks, sched.blocks, p["acts"]):
             ho, wo, co = b.conv1.h_out, b.conv1.w_out, b.conv1.cout
@@ -1017,17 +1022,14 @@ class ResNetEngine:
                 self._conv_fwd(b.conv1, ch.conv1, cur, a["c1"], part, B)
                 self._bn_coef(b.bn1, a["coef1"], part, B, ho, wo)
             else:
-                t0 = self._mark(ch.conv1.label_fwd)
-                if ch.entry == "s2b3":   # conv1 and the 1x1 shortcut on the split-operand path (csrc/conv_b3.hip, conv_s2b3_kernel)
-                    _hip.check(lib.lad_conv_s2b3_fwd(_hip.ptr(cur), _hip.ptr(b.conv1.par.wt3_s2f), _hip.ptr(b.conv1.par.b), _hip.ptr(a["c1"]), _hip.ptr(part),
-                                                     _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]), B, b.conv1.h_in, b.conv1.w_in, st),
-                               "lad_conv_s2b3_fwd " + b.conv1.name)
-                else:   # ... in one launch of the exact-f32 kernel (csrc/conv_mfma.hip, conv_s2_kernel<SC>)
-                    _hip.check(lib.lad_conv_s2_fwd_fused(_hip.ptr(cur), _hip.ptr(b.conv1.par.wt_f), _hip.ptr(b.conv1.par.b), _hip.ptr(b.sc_conv.par.wt_f),
-                                                         _hip.ptr(a["c1"]), _hip.ptr(part), _hip.ptr(a["cs"]), _hip.ptr(p["partials_sc"]),
-                                                         B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, b.conv1.cout, st),
-                               "lad_conv_s2_fwd_fused " + b.conv1.name)
-                self._mark_end(ch.conv1.label_fwd, t0)
+                c1, par = b.conv1, b.conv1.par
+                with self._marked(ch.conv1.label_fwd):
+                    if ch.entry == "s2b3":   # conv1 and the 1x1 shortcut on the split-operand path (csrc/conv_b3.hip, conv_s2b3_kernel)
+                        self._launch("lad_conv_s2b3_fwd", cur, par.wt3_s2f, par.b, a["c1"], part, a["cs"], p["partials_sc"], B, c1.h_in, c1.w_in,
+                                     tag=c1.name)
+                    else:   # ... in one launch of the exact-f32 kernel (csrc/conv_mfma.hip, conv_s2_kernel<SC>)
+                        self._launch("lad_conv_s2_fwd_fused", cur, par.wt_f, par.b, b.sc_conv.par.wt_f, a["c1"], part, a["cs"], p["partials_sc"],
+                                     B, c1.h_in, c1.w_in, c1.cin, c1.cout, tag=c1.name)
                 # bn1 and the shortcut's BatchNorm: one launch
                 self._bn_coef_pair(b.bn1, a["coef1"], part, b.sc_bn, a["coefs"], p["partials_sc"], B, ho, wo)
             if ch.a1_virtual:
@@ -1043,14 +1045,13 @@ class ResNetEngine:
                     self._bn_coef(b.sc_bn, a["coefs"], part, B, ho, wo)
                 self._bn_act(a["c2"], a["coef2"], a["cs"], a["coefs"], a["y"], B, ho, wo, co)
             elif ch.bits:
-                _hip.check(lib.lad_bn_act_bits(_hip.ptr(a["c2"]), _hip.ptr(a["coef2"]), _hip.ptr(cur), None, _hip.ptr(a["y"]),
-                                               _hip.ptr(a["ybits"]), B, ho, wo, co, st), "lad_bn_act_bits")
+                self._launch("lad_bn_act_bits", a["c2"], a["coef2"], cur, None, a["y"], a["ybits"], B, ho, wo, co)
             else:
                 self._bn_act(a["c2"], a["coef2"], cur, None, a["y"], B, ho, wo, co)
             a["x"] = cur
             cur = a["y"]
         last = blocks[-1].conv2
-        _hip.check(lib.lad_pool_fwd(_hip.ptr(cur), _hip.ptr(p["pooled"]), B, p["h4"], p["w4"], last.cout, st), "lad_pool_fwd")
+        self._launch("lad_pool_fwd", cur, p["pooled"], B, p["h4"], p["w4"], last.cout)
         m1 = m2 = None
         rng = isinstance(drop_masks, str) and drop_masks == "rng"
         if drop_masks is not None and not rng:
@@ -1076,14 +1077,11 @@ class ResNetEngine:
             if seed != self._rng_seed:       # (torch.manual_seed since the last draw: the sequence starts again)
                 self._rng_seed = seed
                 self._rng_counter.zero_()
-            _hip.check(lib.lad_head_fwd_train_rng(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2), keep,
-                                                  seed, _hip.ptr(self._rng_counter), _hip.ptr(self._nbt), int(self._nbt.numel()),
-                                                  _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]), _hip.ptr(p["probs"]),
-                                                  _hip.ptr(p["metrics"]), st), "lad_head_fwd_train_rng")
+            self._launch("lad_head_fwd_train_rng", self._head_params, p["pooled"], B, p["feat"], m1, m2, keep, seed, self._rng_counter, self._nbt,
+                         int(self._nbt.numel()), labels, 0.1, p["h"], p["hstats"], p["probs"], p["metrics"])
         else:
-            _hip.check(lib.lad_head_fwd_train(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(m1), _hip.ptr(m2),
-                                              _hip.ptr(labels), 0.1, _hip.ptr(p["h"]), _hip.ptr(p["hstats"]),
-                                              _hip.ptr(p["probs"]), _hip.ptr(p["metrics"]), st), "lad_head_fwd_train")
+            self._launch("lad_head_fwd_train", self._head_params, p["pooled"], B, p["feat"], m1, m2, labels, 0.1, p["h"], p["hstats"],
+                         p["probs"], p["metrics"])
         p["saved"] = (x, labels, m1, m2, B, H, W)
         self._last_train_plan = p
         self._train_forwards += 1  # running statistics moved: the eval-mode folds are stale
@@ -1115,50 +1113,33 @@ class ResNetEngine:
         self._plans[key] = p
         return p
 
-    def _conv_eval(self, cs, bn, x, addend, out, B, relu):
-        lib, st = self.lib(), self._st()
-        label = f"conv_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
-        t0 = self._mark(label)
-        if cs.stride == 1:
-            _hip.check(lib.lad_conv_fwd_eval(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                             _hip.ptr(addend), _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
-                       "lad_conv_fwd_eval " + cs.name)
-        else:
-            if addend is not None:
-                raise _hip.LadHipError("stride-2 eval convolution takes no residual")
-            _hip.check(lib.lad_conv_s2_fwd_eval(_hip.ptr(x), _hip.ptr(cs.par.wt_f), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                                _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
-                       "lad_conv_s2_fwd_eval " + cs.name)
-        self._mark_end(label, t0)
+    # eval-mode convolution by precision: (entry point at stride 1, at stride 2, weight image of _ConvParams, label prefix)
+    _CONV_EVAL = {False: ("lad_conv_fwd_eval", "lad_conv_s2_fwd_eval", "wt_f", "conv_s"),
+                  True: ("lad_f16_conv_fwd", "lad_f16_conv_s2_fwd", "wt_h", "conv_f16_s")}
 
-    def _conv_eval_f16(self, cs, bn, x, addend, out, B, relu):
-        lib, st = self.lib(), self._st()
-        label = f"conv_f16_s{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"
-        t0 = self._mark(label)
-        if cs.stride == 1:
-            _hip.check(lib.lad_f16_conv_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                            _hip.ptr(addend), _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
-                       "lad_f16_conv_fwd " + cs.name)
-        else:
-            _hip.check(lib.lad_f16_conv_s2_fwd(_hip.ptr(x), _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1]),
-                                               _hip.ptr(out), B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, st),
-                       "lad_f16_conv_s2_fwd " + cs.name)
-        self._mark_end(label, t0)
+    def _conv_eval(self, half, cs, bn, x, addend, out, B, relu):
+        s1, s2, image, prefix = self._CONV_EVAL[half]
+        wt = getattr(cs.par, image)
+        with self._marked(f"{prefix}{cs.stride}<{cs.cin},{cs.cout},{cs.taps}>"):
+            if cs.stride == 1:
+                self._launch(s1, x, wt, *bn.fold, addend, out, B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, tag=cs.name)
+            else:
+                if addend is not None and not half:
+                    raise _hip.LadHipError("stride-2 eval convolution takes no residual")
+                self._launch(s2, x, wt, *bn.fold, out, B, cs.h_in, cs.w_in, cs.cin, cs.cout, cs.taps, relu, tag=cs.name)
 
     # ---- the eval forward in pieces (shared by the plain and the streaming sliding-window paths) ------------------------------
     def _eval_stem(self, half, fptr, out, out_byte_offset, B, H, W, frame_stride, frames_avail):
-        lib, st = self.lib(), self._st()
         optr = ctypes.c_void_p(out.data_ptr() + out_byte_offset)
-        fn, name = (lib.lad_f16_stem_fwd, "lad_f16_stem_fwd") if half else (lib.lad_stem_fwd_eval, "lad_stem_fwd_eval")
-        _hip.check(fn(fptr, _hip.ptr(self.stem_w), _hip.ptr(self.stem_bn.fold[0]), _hip.ptr(self.stem_bn.fold[1]), optr, B, H, W,
-                      self.stem_cout, frame_stride, max(0, frames_avail), st), name)
+        self._launch("lad_f16_stem_fwd" if half else "lad_stem_fwd_eval", fptr, self.stem_w, *self.stem_bn.fold, optr, B, H, W,
+                     self.stem_cout, frame_stride, max(0, frames_avail))
 
     def _eval_blocks(self, half, p, blocks, cur, B, fused, rides, final_out=None):
         """Residual blocks `blocks` of plan p on the activation `cur` (one of the plan's rotating buffers of its level).
         fused / rides: per block, whether lad_f16_block_fwd is tried and whether a down-sampling block's shortcut rides in conv1's
         launch (the layout's flags for these blocks on B images).  final_out: where the LAST block's output goes instead of a
         rotating buffer (a slice of a caller's tensor)."""
-        conv = self._conv_eval_f16 if half else self._conv_eval
+        conv = functools.partial(self._conv_eval, half)
         lv = p["lv"]
         for bi, b in enumerate(blocks):
             L = lv[(b.conv1.h_out, b.conv1.w_out)]
@@ -1169,18 +1150,13 @@ class ResNetEngine:
             if fused[bi]:
                 # both convolutions + the residual with the image(s) resident in LDS (csrc/conv_f16.hip: block_f16_strip_kernel at 64
                 # channels, block_f16_small_kernel at 16 / 32)
-                label = f"block_f16<{b.conv1.cin}>"
-                t0 = self._mark(label)
-                rc = self.lib().lad_f16_block_fwd(_hip.ptr(cur), *self._f16_args(b.conv1, b.bn1), *self._f16_args(b.conv2, b.bn2), _hip.ptr(y),
-                                                  B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, self._st())
-                if rc != _hip.LAD_NOT_COVERED:      # (this geometry is not covered, nothing was launched -> the two convolutions)
-                    _hip.check(rc, "lad_f16_block_fwd " + b.conv1.name)
-                    self._mark_end(label, t0)
+                if self._try_launch(f"block_f16<{b.conv1.cin}>", "lad_f16_block_fwd", cur, *self._f16_args(b.conv1, b.bn1),
+                                    *self._f16_args(b.conv2, b.bn2), y, B, b.conv1.h_in, b.conv1.w_in, b.conv1.cin, tag=b.conv1.name):
                     cur = y
-                    continue
+                    continue    # (else this geometry is not covered, nothing was launched -> the two convolutions)
             if rides[bi]:
                 cs = free[2]
-                self._s2_plain_f16(b, _hip.ptr(cur), (_hip.ptr(a1), _hip.ptr(cs)), B, b.conv1.h_in, b.conv1.w_in, True)
+                self._s2_plain_f16(b, cur, (a1, cs), B, b.conv1.h_in, b.conv1.w_in, True)
                 conv(b.conv2, b.bn2, a1, cs, y, B, 1)
                 cur = y
                 continue
@@ -1197,35 +1173,28 @@ class ResNetEngine:
     @staticmethod
     def _f16_args(cs, bn):
         """{fp16 weight image, folded scale, folded shift} of one convolution, as the half-precision entry points take them."""
-        return _hip.ptr(cs.par.wt_h), _hip.ptr(bn.fold[0]), _hip.ptr(bn.fold[1])
+        return cs.par.wt_h, bn.fold[0], bn.fold[1]
 
     def _s2_entry_f16(self, b, launch_one, launch_sc, rides):
         """conv1 (-> slot 0) and the 1x1 shortcut (-> slot 1) of the down-sampling block b in half precision: ONE launch
         (launch_sc()) when the shortcut rides, else launch_one(convolution, its BatchNorm, slot, relu) for each; with the event
         marks bench.py keys on."""
         if rides:
-            label = f"conv_f16_s2sc<{b.conv1.cin},{b.conv1.cout}>"
-            t0 = self._mark(label)
-            launch_sc()
-            self._mark_end(label, t0)
+            with self._marked(f"conv_f16_s2sc<{b.conv1.cin},{b.conv1.cout}>"):
+                launch_sc()
             return
         for cs, bn, slot, relu in ((b.conv1, b.bn1, 0, 1), (b.sc_conv, b.sc_bn, 1, 0)):
-            label = f"conv_f16_s2<{cs.cin},{cs.cout},{cs.taps}>"
-            t0 = self._mark(label)
-            launch_one(cs, bn, slot, relu)
-            self._mark_end(label, t0)
+            with self._marked(f"conv_f16_s2<{cs.cin},{cs.cout},{cs.taps}>"):
+                launch_one(cs, bn, slot, relu)
 
     def _s2_plain_f16(self, b, src, dst, B, h, w, rides):
-        """... on B whole images of h x w at the device pointer src; dst: the pointers of the two outputs."""
-        lib, st = self.lib(), self._st()
-
+        """... on B whole images of h x w at src; dst: the two outputs (tensors, or device pointers into one)."""
         def one(cs, bn, slot, relu):
-            _hip.check(lib.lad_f16_conv_s2_fwd(src, *self._f16_args(cs, bn), dst[slot], B, h, w, cs.cin, cs.cout, cs.taps, relu, st),
-                       "lad_f16_conv_s2_fwd " + cs.name)
+            self._launch("lad_f16_conv_s2_fwd", src, *self._f16_args(cs, bn), dst[slot], B, h, w, cs.cin, cs.cout, cs.taps, relu, tag=cs.name)
 
         def both():
-            _hip.check(lib.lad_f16_conv_s2_fwd_sc(src, *self._f16_args(b.conv1, b.bn1), dst[0], *self._f16_args(b.sc_conv, b.sc_bn), dst[1],
-                                                  B, h, w, b.conv1.cin, b.conv1.cout, 1, st), "lad_f16_conv_s2_fwd_sc " + b.conv1.name)
+            self._launch("lad_f16_conv_s2_fwd_sc", src, *self._f16_args(b.conv1, b.bn1), dst[0], *self._f16_args(b.sc_conv, b.sc_bn), dst[1],
+                         B, h, w, b.conv1.cin, b.conv1.cout, 1, tag=b.conv1.name)
         self._s2_entry_f16(b, one, both, rides)
 
     def _s2_mapped_f16(self, b, src, dst, wmap, rides, strips_resident=False):
@@ -1233,34 +1202,25 @@ class ResNetEngine:
         first stream row, phases, rows of a phase image, rows of src, output rows per image or 0 for all), from the tensor src
         ([strips][stream(s)]).  strips_resident: the one-launch form is tried on lad_f16_conv_s2_strips_fwd first (the strips' input
         rows resident in LDS as parity classes instead of gathered per lane: csrc/s2strip_f16.hip, round 6)."""
-        lib, st = self.lib(), self._st()
-
         def one(cs, bn, slot, relu):
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped(_hip.ptr(src), *self._f16_args(cs, bn), _hip.ptr(dst[slot]), *wmap,
-                                                      cs.cin, cs.cout, cs.taps, relu, st), "lad_f16_conv_s2_fwd_mapped " + cs.name)
+            self._launch("lad_f16_conv_s2_fwd_mapped", src, *self._f16_args(cs, bn), dst[slot], *wmap, cs.cin, cs.cout, cs.taps, relu, tag=cs.name)
 
         def both():
-            args = (_hip.ptr(src), *self._f16_args(b.conv1, b.bn1), _hip.ptr(dst[0]), *self._f16_args(b.sc_conv, b.sc_bn), _hip.ptr(dst[1]))
-            if strips_resident:
-                rc = lib.lad_f16_conv_s2_strips_fwd(*args, *wmap[:7], *wmap[9:], st)
-                if rc != _hip.LAD_NOT_COVERED:
-                    _hip.check(rc, "lad_f16_conv_s2_strips_fwd " + b.conv1.name)
-                    return
-            _hip.check(lib.lad_f16_conv_s2_fwd_mapped_sc(*args, *wmap, b.conv1.cin, b.conv1.cout, 1, st),
-                       "lad_f16_conv_s2_fwd_mapped_sc " + b.conv1.name)
+            args = (src, *self._f16_args(b.conv1, b.bn1), dst[0], *self._f16_args(b.sc_conv, b.sc_bn), dst[1])
+            # (no event pair of its own: _s2_entry_f16 times whichever of the two launches runs)
+            if strips_resident and self._launch("lad_f16_conv_s2_strips_fwd", *args, *wmap[:7], *wmap[9:], tag=b.conv1.name, may_decline=True):
+                return
+            self._launch("lad_f16_conv_s2_fwd_mapped_sc", *args, *wmap, b.conv1.cin, b.conv1.cout, 1, tag=b.conv1.name)
         self._s2_entry_f16(b, one, both, rides)
 
     def _eval_tail(self, half, p, cur, B, probs_out=None):
         """Pooling and classifier.  probs_out (predict_windows): the slice of ITS output these windows belong to -- the head writes
         there (no copy per chunk)."""
-        lib, st = self.lib(), self._st()
         last = p["blocks"][-1].conv2
         p["block_out"] = cur
-        pool, name = (lib.lad_f16_pool_fwd, "lad_f16_pool_fwd") if half else (lib.lad_pool_fwd, "lad_pool_fwd")
-        _hip.check(pool(_hip.ptr(cur), _hip.ptr(p["pooled"]), B, p["h4"], p["w4"], last.cout, st), name)
+        self._launch("lad_f16_pool_fwd" if half else "lad_pool_fwd", cur, p["pooled"], B, p["h4"], p["w4"], last.cout)
         probs = probs_out if probs_out is not None else p["probs"]
-        _hip.check(lib.lad_head_fwd_eval(self._head_params, _hip.ptr(p["pooled"]), B, p["feat"], _hip.ptr(probs), st),
-                   "lad_head_fwd_eval")
+        self._launch("lad_head_fwd_eval", self._head_params, p["pooled"], B, p["feat"], probs)
         return probs
 
     def _require_half(self):
@@ -1368,7 +1328,7 @@ class ResNetEngine:
         """The level-1 strips: frames [s, s + 2 band) for every offset s (gather.hip: upper half = top of window s, lower half =
         bottom of window s - (H - 2 band)) through the stem and blocks[:n1], into the head of cat.  Leaves bufs["strips"]."""
         half, W, C, n1, n_strip, Ht = lay.half, lay.W, self.stem_cout, lay.n1, lay.n_strip, lay.Ht
-        lib, st, cat, pt = self.lib(), self._st(), bufs["cat"], plans["pt"]
+        cat, pt = bufs["cat"], plans["pt"]
         out_t = None
         if cat is not None:
             # (the strips' tail rows are the stream's border row: zeros either way -- except behind a run's shorter last group, where
@@ -1384,15 +1344,9 @@ class ResNetEngine:
             # the first block's launch takes them from there and computes the strip's first and last row itself
             # (lad_f16_block_fwd_stem_rows; round 6) -- no stem launch for the strips, no strip-sized stem tensor written or read
             y0 = out_t if n1 == 1 else pt["lv"][(Ht, W)][1]
-            label = f"block_f16<{b0.conv1.cin}>"
-            t0 = self._mark(label)
-            rc = lib.lad_f16_block_fwd_stem_rows(_hip.ptr(bufs["stem"]), lay.stream_rows, d, ctypes.c_void_p(src[0]), max(0, src[1]),
-                                                 _hip.ptr(self.stem_w), _hip.ptr(self.stem_bn.fold[0]), _hip.ptr(self.stem_bn.fold[1]),
-                                                 *self._f16_args(b0.conv1, b0.bn1), *self._f16_args(b0.conv2, b0.bn2), _hip.ptr(y0),
-                                                 n_strip, Ht, W, st)
-            if rc != _hip.LAD_NOT_COVERED:
-                _hip.check(rc, "lad_f16_block_fwd_stem_rows " + b0.conv1.name)
-                self._mark_end(label, t0)
+            if self._try_launch(f"block_f16<{b0.conv1.cin}>", "lad_f16_block_fwd_stem_rows", bufs["stem"], lay.stream_rows, d,
+                                ctypes.c_void_p(src[0]), max(0, src[1]), self.stem_w, *self.stem_bn.fold, *self._f16_args(b0.conv1, b0.bn1),
+                                *self._f16_args(b0.conv2, b0.bn2), y0, n_strip, Ht, W, tag=b0.conv1.name):
                 ct = y0 if n1 == 1 else self._eval_blocks(half, pt, pt["blocks"][1:n1], y0, n_strip, fused[1:], ride[1:], final_out=out_t)
         if ct is None:
             ct = pt["lv"][(Ht, W)][0]
@@ -1458,7 +1412,7 @@ class ResNetEngine:
 
         def rest_of_level(p, b, L, n_img, fused, final_out):
             y = final_out if k3 == n1 + 1 else L[2]
-            self._conv_eval_f16(b.conv2, b.bn2, L[0], L[1], y, n_img, 1)
+            self._conv_eval(True, b.conv2, b.bn2, L[0], L[1], y, n_img, 1)
             if k3 > n1 + 1:
                 self._eval_blocks(True, p, p["blocks"][n1 + 1:k3], y, n_img, fused, lay.rides[n1 + 1:k3], final_out=final_out)
 
@@ -1486,8 +1440,7 @@ class ResNetEngine:
         fused, ride = lay.window_fused, lay.rides
         if lay.mode == "assembled":
             cur = pw["lv"][(H, W)][0]
-            _hip.check(self.lib().lad_assemble_windows(_hip.ptr(bufs["stream"]), _hip.ptr(bufs["strips"]), _hip.ptr(cur), B, H, W, lay.band,
-                                                       self.stem_cout * (2 if half else 4), self._st()), "lad_assemble_windows")
+            self._launch("lad_assemble_windows", bufs["stream"], bufs["strips"], cur, B, H, W, lay.band, self.stem_cout * (2 if half else 4))
             cur = self._eval_blocks(half, pw, blocks[n1:], cur, B, fused[n1:], ride[n1:])
             return self._eval_tail(half, pw, cur, B, probs_out)
         if lay.mode == "direct":
@@ -1499,25 +1452,19 @@ class ResNetEngine:
             wmap = (B, lay.H2, lay.W2, lay.band2, lay.Ht2, lay.shift2, lay.stream2_base + (d // 2) * (lay.W2 + 1), 2, lay.img_s2, lay.rows2, 0)
             if lay.tail_fused:   # in ONE launch where the tail kernel covers the geometry (csrc/tail_f16.hip, round 6)
                 probs = probs_out if probs_out is not None else pw["probs"]
-                label = "tail_f16"
-                t0 = self._mark(label)
-                rc = self.lib().lad_f16_tail_fwd(_hip.ptr(src), *wmap[:-1], self._tail_params(blocks[k:]), self._head_params, pw["feat"],
-                                                 _hip.ptr(probs), self._st())
-                if rc != _hip.LAD_NOT_COVERED:
-                    _hip.check(rc, "lad_f16_tail_fwd")
-                    self._mark_end(label, t0)
+                if self._try_launch("tail_f16", "lad_f16_tail_fwd", src, *wmap[:-1], self._tail_params(blocks[k:]), self._head_params,
+                                    pw["feat"], probs):
                     return probs
         b = blocks[k]
         L = pw["lv"][(b.conv1.h_out, b.conv1.w_out)]
         if lay.mode == "direct" and not ride[k]:   # (two launches: the entry point that needs no map)
             def one(cs, bn, slot, relu):
-                _hip.check(self.lib().lad_f16_conv_s2_fwd_windows(_hip.ptr(src), *self._f16_args(cs, bn), _hip.ptr(L[slot]), B, H, W, lay.band,
-                                                                  cs.cin, cs.cout, cs.taps, relu, self._st()),
-                           "lad_f16_conv_s2_fwd_windows " + cs.name)
+                self._launch("lad_f16_conv_s2_fwd_windows", src, *self._f16_args(cs, bn), L[slot], B, H, W, lay.band, cs.cin, cs.cout, cs.taps,
+                             relu, tag=cs.name)
             self._s2_entry_f16(b, one, None, False)
         else:
             self._s2_mapped_f16(b, src, L, wmap, ride[k])
-        self._conv_eval_f16(b.conv2, b.bn2, L[0], L[1], L[2], B, 1)
+        self._conv_eval(True, b.conv2, b.bn2, L[0], L[1], L[2], B, 1)
         cur = self._eval_blocks(half, pw, blocks[k + 1:], L[2], B, fused[k + 1:], ride[k + 1:])
         return self._eval_tail(half, pw, cur, B, probs_out)
 
@@ -1592,12 +1539,10 @@ class ResNetEngine:
     # ------------------------------------------------------------------------------------ backward
     def _bn_bwd(self, p, bn, dy, y, x, coef, dx, B, h, w, relu, mode=0, aux=None, sbn=None, xs=None, scoef=None, pre=False):
         """pre=True: the launch that produced dy already left this BatchNorm's per-tile sums in p["partials"]."""
-        _hip.check(self.lib().lad_bn_bwd(
-            _hip.ptr(dy), _hip.ptr(y), _hip.ptr(x), _hip.ptr(coef), _hip.ptr(bn.g), _hip.ptr(xs), _hip.ptr(scoef),
-            _hip.ptr(sbn.g) if sbn is not None else None, _hip.ptr(dx), _hip.ptr(aux), _hip.ptr(bn.gg), _hip.ptr(bn.gb),
-            _hip.ptr(sbn.gg) if sbn is not None else None, _hip.ptr(sbn.gb) if sbn is not None else None,
-            _hip.ptr(p["bn_ws"]), _hip.ptr(p["bcoef"]), _hip.ptr(p["partials"]) if pre else None,
-            int(self.lib().lad_conv_num_tiles(B, h, w)) if pre else 0, B, h, w, bn.c, relu, mode, self._st()), "lad_bn_bwd " + bn.name)
+        sg, sgg, sgb = (sbn.g, sbn.gg, sbn.gb) if sbn is not None else (None, None, None)
+        self._launch("lad_bn_bwd", dy, y, x, coef, bn.g, xs, scoef, sg, dx, aux, bn.gg, bn.gb, sgg, sgb, p["bn_ws"], p["bcoef"],
+                     p["partials"] if pre else None, int(self.lib().lad_conv_num_tiles(B, h, w)) if pre else 0, B, h, w, bn.c, relu, mode,
+                     tag=bn.name)
 
     # Weight gradients are off the critical path of backward (nothing needs them before the optimiser), so they CAN run
     # on a side stream next to the data-gradient chain (overlap_wgrad = True): two MFMA kernels sharing the CUs fill each
@@ -1613,10 +1558,10 @@ class ResNetEngine:
         return self._side
 
     def _on_side(self, launch, read_buffer, small=False):
-        """Run launch(stream_handle) on the side stream; remember that it reads `read_buffer`.  small: a 16- / 32-channel layer's
-        launch (overlap_wgrad_small: only these go to the side stream)."""
+        """Run launch(stream handle) on the side stream (None: on the current stream, as _launch takes it); remember that it reads
+        `read_buffer`.  small: a 16- / 32-channel layer's launch (overlap_wgrad_small: only these go to the side stream)."""
         if not (self.overlap_wgrad or (small and self._overlap_small_on())):
-            launch(self._st())
+            launch(None)
             return
         side = self._side_stream()
         side.wait_stream(torch.cuda.current_stream(self.device))
@@ -1654,17 +1599,16 @@ class ResNetEngine:
         bn = (dy, bn_x, bits, coef): the launch first applies the element-wise half of the BatchNorm backward of the layer's own
         output (p["bcoef"], left by lad_bn_bwd*) to dy and WRITES dout for the data-gradient launch: main stream only."""
         fn = conv_wgrad_entry(kind, in_coef is not None, bn is not None)
-        lib, P, h, w, ws = self.lib(), _hip.ptr, cs.h_in, cs.w_in, self._wg_ws(p, cs)
+        h, w, ws, gw, gb = cs.h_in, cs.w_in, self._wg_ws(p, cs), cs.par.gw, cs.par.gb
         if bn is not None:
             dy, bx, bits, coef = bn
-            _hip.check(lib.lad_conv_wgrad_h2_bnbwd(P(x), P(in_coef), P(dy), P(bx), P(bits), P(coef), P(p["bcoef"]), P(dout), P(ws), P(cs.par.gw),
-                                                   P(cs.par.gb), B, h, w, cs.cin, self._st()), f"{fn} {cs.name}")
+            self._launch(fn, x, in_coef, dy, bx, bits, coef, p["bcoef"], dout, ws, gw, gb, B, h, w, cs.cin, tag=cs.name)
         elif kind == "f32":
-            self._on_side(lambda st: _hip.check(lib.lad_conv_wgrad(P(x), P(dout), P(ws), P(cs.par.gw), P(cs.par.gb), B, h, w, cs.cin, cs.cout, cs.taps, st),
-                                                f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
+            self._on_side(lambda st: self._launch(fn, x, dout, ws, gw, gb, B, h, w, cs.cin, cs.cout, cs.taps, tag=cs.name, stream=st),
+                          dout, small=cs.cin <= 32)
         else:   # same split arithmetic as the forward / data-gradient launches of this layer (csrc/wgrad_mfma.hip)
-            self._on_side(lambda st: _hip.check(getattr(lib, fn)(P(x), P(in_coef), P(dout), P(ws), P(cs.par.gw), P(cs.par.gb), B, h, w, cs.cin, st),
-                                                f"{fn} {cs.name}"), dout, small=cs.cin <= 32)
+            self._on_side(lambda st: self._launch(fn, x, in_coef, dout, ws, gw, gb, B, h, w, cs.cin, tag=cs.name, stream=st),
+                          dout, small=cs.cin <= 32)
 
     def backward(self, dprobs=None):
         """Gradient of the last train-mode forward into the flat gradient buffer (overwrites it).
@@ -1687,21 +1631,19 @@ class ResNetEngine:
         x, labels, m1, m2, B, H, W = p["saved"]
         if dprobs is None and labels is None:
             raise _hip.LadHipError("backward() needs dprobs or labels passed to forward()")
-        lib, st = self.lib(), self._st()
+        lib = self.lib()
         blocks, acts, sched = p["blocks"], p["acts"], p["schedule"]
         last = blocks[-1].conv2
         # weight-gradient slab sums: one launch at the end instead of one per layer (not with the side stream: the flush
         # would have to follow launches on two streams)
         self._defer_on = self.defer_wgrad_sums and not self.overlap_wgrad
         if self._defer_on:
-            _hip.check(lib.lad_wgrad_defer_begin(), "lad_wgrad_defer_begin")
-        _hip.check(lib.lad_head_bwd(self._head_params, self._head_grads, _hip.ptr(p["pooled"]), _hip.ptr(p["h"]),
-                                    _hip.ptr(p["hstats"]), _hip.ptr(p["probs"]), _hip.ptr(dprobs), B, p["feat"], _hip.ptr(m1),
-                                    _hip.ptr(m2), _hip.ptr(labels), _hip.ptr(p["head_ws"]), _hip.ptr(p["dpooled"]), st),
-                   "lad_head_bwd")
+            _hip.check(self.lib().lad_wgrad_defer_begin(), "lad_wgrad_defer_begin")
+        self._launch("lad_head_bwd", self._head_params, self._head_grads, p["pooled"], p["h"], p["hstats"], p["probs"], dprobs, B, p["feat"],
+                     m1, m2, labels, p["head_ws"], p["dpooled"])
         g_out = p["g"][(last.h_out, last.w_out)]
         dy = g_out[0]
-        _hip.check(lib.lad_pool_bwd(_hip.ptr(p["dpooled"]), _hip.ptr(dy), B, p["h4"], p["w4"], last.cout, st), "lad_pool_bwd")
+        self._launch("lad_pool_bwd", p["dpooled"], dy, B, p["h4"], p["w4"], last.cout)
         pre2 = False  # did the producer of `dy` already reduce for this block's bn2?
         pre2_tiles = 0  # ... into how many partials, if not one per 128-row tile (the stride-2 data gradient)
         for bi in range(len(blocks) - 1, -1, -1):
@@ -1722,11 +1664,9 @@ class ResNetEngine:
             fuse1 = ch.conv1.wgrad_bn and not self.overlap_wgrad
             if ch.bits:
                 # dc2 only; the shortcut's share dy * [y > 0] is formed from dy and the bits in conv1's data gradient below
-                _hip.check(lib.lad_bn_bwd_bits(_hip.ptr(dy), _hip.ptr(bits), _hip.ptr(a["c2"]), _hip.ptr(a["coef2"]), _hip.ptr(b.bn2.g),
-                                               None if fuse2 else _hip.ptr(dc2), _hip.ptr(b.bn2.gg), _hip.ptr(b.bn2.gb), _hip.ptr(p["bn_ws"]),
-                                               _hip.ptr(p["bcoef"]), _hip.ptr(p["partials"]) if pre2 else None,
-                                               (pre2_tiles or int(lib.lad_conv_num_tiles(B, ho, wo))) if pre2 else 0, B, ho, wo, co, st),
-                           "lad_bn_bwd_bits " + b.bn2.name)
+                self._launch("lad_bn_bwd_bits", dy, bits, a["c2"], a["coef2"], b.bn2.g, None if fuse2 else dc2, b.bn2.gg, b.bn2.gb, p["bn_ws"],
+                             p["bcoef"], p["partials"] if pre2 else None,
+                             (pre2_tiles or int(lib.lad_conv_num_tiles(B, ho, wo))) if pre2 else 0, B, ho, wo, co, tag=b.bn2.name)
             elif b.sc_conv is None:
                 self._bn_bwd(p, b.bn2, dy, a["y"], a["c2"], a["coef2"], dc2, B, ho, wo, 1, mode=1, aux=aux, pre=pre2)
             else:
@@ -1766,14 +1706,13 @@ class ResNetEngine:
                 sc = b.sc_conv
 
                 def s2_wgrad(cs, dout, xin=a["x"]):   # one convolution's weight gradient in a launch of its own
-                    self._on_side(lambda sst: _hip.check(lib.lad_conv_s2_wgrad(
-                        _hip.ptr(xin), _hip.ptr(dout), _hip.ptr(self._wg_ws(p, cs)), _hip.ptr(cs.par.gw), _hip.ptr(cs.par.gb), B, hi, wi, cs.cin, cs.cout,
-                        cs.taps, sst), "lad_conv_s2_wgrad " + cs.name), dout, small=cs.cin <= 32)
+                    self._on_side(lambda sst: self._launch("lad_conv_s2_wgrad", xin, dout, self._wg_ws(p, cs), cs.par.gw, cs.par.gb, B, hi, wi,
+                                                           cs.cin, cs.cout, cs.taps, tag=cs.name, stream=sst), dout, small=cs.cin <= 32)
 
                 if ch.sc_wgrad_fused:   # conv1's and the shortcut's weight gradients in one launch (same input rows; csrc/conv_s2_bwd.hip)
-                    self._on_side(lambda sst, c1s=c1s, sc=sc, dc1=dc1, aux=aux, xin=a["x"]: _hip.check(lib.lad_conv_s2_wgrad_fused(
-                        _hip.ptr(xin), _hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(self._wg_ws(p, c1s)), _hip.ptr(c1s.par.gw), _hip.ptr(c1s.par.gb),
-                        _hip.ptr(sc.par.gw), B, hi, wi, c1s.cin, c1s.cout, sst), "lad_conv_s2_wgrad_fused " + c1s.name), dc1, small=c1s.cin <= 32)
+                    self._on_side(lambda sst, c1s=c1s, sc=sc, dc1=dc1, aux=aux, xin=a["x"]: self._launch(
+                        "lad_conv_s2_wgrad_fused", xin, dc1, aux, self._wg_ws(p, c1s), c1s.par.gw, c1s.par.gb, sc.par.gw, B, hi, wi, c1s.cin, c1s.cout,
+                        tag=c1s.name, stream=sst), dc1, small=c1s.cin <= 32)
                     if dc1.data_ptr() in self._side_readers:   # (it ran on the side stream) the launch reads aux as well
                         self._side_readers[aux.data_ptr()] = self._side_readers[dc1.data_ptr()]
                 else:
@@ -1785,28 +1724,22 @@ class ResNetEngine:
                     # both data gradients on the split-operand path, parity class by parity class (dgrad_s2b3_kernel)
                     n_part = int(lib.lad_conv_s2b3_dgrad_partials(B, hi, wi))
                     assert not ch.dgrad1_bn or n_part * 2 * 64 <= p["partials"].numel()
-                    _hip.check(lib.lad_conv_s2b3_dgrad(_hip.ptr(dc1), _hip.ptr(aux), _hip.ptr(c1s.par.wt3_s2d), _hip.ptr(dx),
-                                                       _hip.ptr(p["partials"]) if ch.dgrad1_bn else None, _hip.ptr(stat[0]), _hip.ptr(stat[1]),
-                                                       _hip.ptr(stat[2]), B, hi, wi, st), "lad_conv_s2b3_dgrad " + c1s.name)
+                    self._launch("lad_conv_s2b3_dgrad", dc1, aux, c1s.par.wt3_s2d, dx, p["partials"] if ch.dgrad1_bn else None, *stat, B, hi, wi,
+                                 tag=c1s.name)
                 elif ch.entry == "s2_fused" and ch.dgrad1_bn:
                     n_part = int(lib.lad_conv_s2_dgrad_partials(B, hi, wi))
                     assert n_part * 2 * 64 <= p["partials"].numel()
-                    _hip.check(lib.lad_conv_s2_dgrad_fused_bnstat(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx),
-                                                                  _hip.ptr(p["partials"]), _hip.ptr(stat[0]), _hip.ptr(stat[1]),
-                                                                  _hip.ptr(stat[2]), B, hi, wi, c1s.cin, c1s.cout, st),
-                               "lad_conv_s2_dgrad_fused_bnstat " + c1s.name)
+                    self._launch("lad_conv_s2_dgrad_fused_bnstat", dc1, c1s.par.wt_d, aux, sc.par.wt_d, dx, p["partials"], *stat, B, hi, wi,
+                                 c1s.cin, c1s.cout, tag=c1s.name)
                 elif ch.entry == "s2_fused":   # both data gradients in one launch, dx written once
-                    _hip.check(lib.lad_conv_s2_dgrad_fused(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx),
-                                                           B, hi, wi, c1s.cin, c1s.cout, st), "lad_conv_s2_dgrad_fused " + c1s.name)
+                    self._launch("lad_conv_s2_dgrad_fused", dc1, c1s.par.wt_d, aux, sc.par.wt_d, dx, B, hi, wi, c1s.cin, c1s.cout, tag=c1s.name)
                 else:
-                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(dc1), _hip.ptr(c1s.par.wt_d), _hip.ptr(dx), B, hi, wi, c1s.cin, c1s.cout, 9, 0,
-                                                     st), "lad_conv_s2_dgrad " + c1s.name)
+                    self._launch("lad_conv_s2_dgrad", dc1, c1s.par.wt_d, dx, B, hi, wi, c1s.cin, c1s.cout, 9, 0, tag=c1s.name)
                 pre2, pre2_tiles = ch.dgrad1_bn is not None, n_part
                 if not ch.sc_wgrad_fused:
                     s2_wgrad(sc, aux)
                 if ch.entry == "plain":
-                    _hip.check(lib.lad_conv_s2_dgrad(_hip.ptr(aux), _hip.ptr(sc.par.wt_d), _hip.ptr(dx), B, hi, wi, sc.cin, sc.cout, 1, 1, st),
-                               "lad_conv_s2_dgrad " + sc.name)
+                    self._launch("lad_conv_s2_dgrad", aux, sc.par.wt_d, dx, B, hi, wi, sc.cin, sc.cout, 1, 1, tag=sc.name)
             dy = dx
         # stem: bn1 + conv1 weight gradient.  The input needs no gradient and the convolution is recomputed from the features:
         # sums (x recomputed) -> lad_bn_bwd finalises them into dgamma / dbeta / bcoef (dx = None: nothing to apply) ->
@@ -1814,25 +1747,20 @@ class ResNetEngine:
         if sched.stem_onepass:
             # ONE pass over dy (the BatchNorm's sums and the centred tap products together), the rest from the forward's moments
             bn = self.stem_bn
-            _hip.check(lib.lad_stem_bwd_onepass(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(dy), _hip.ptr(p["stem_coef"]), _hip.ptr(bn.g),
-                                                _hip.ptr(p["stem_mom"]), _hip.ptr(p["stem_bwd_ws"]), _hip.ptr(self.stem_gw), _hip.ptr(bn.gg),
-                                                _hip.ptr(bn.gb), B, H, W, self.stem_cout, st), "lad_stem_bwd_onepass")
+            self._launch("lad_stem_bwd_onepass", x, self.stem_w, dy, p["stem_coef"], bn.g, p["stem_mom"], p["stem_bwd_ws"], self.stem_gw, bn.gg,
+                         bn.gb, B, H, W, self.stem_cout)
         else:
             groups = int(lib.lad_stem_bn_bwd_groups(B, H, W))
-            _hip.check(lib.lad_stem_bn_bwd_sums(_hip.ptr(x), _hip.ptr(self.stem_w), _hip.ptr(dy), _hip.ptr(p["stem_coef"]),
-                                                _hip.ptr(p["partials"]), B, H, W, self.stem_cout, st), "lad_stem_bn_bwd_sums")
+            self._launch("lad_stem_bn_bwd_sums", x, self.stem_w, dy, p["stem_coef"], p["partials"], B, H, W, self.stem_cout)
             bn = self.stem_bn
-            _hip.check(lib.lad_bn_bwd(_hip.ptr(dy), None, None, _hip.ptr(p["stem_coef"]), _hip.ptr(bn.g), None, None, None, None,
-                                      None, _hip.ptr(bn.gg), _hip.ptr(bn.gb), None, None, _hip.ptr(p["bn_ws"]), _hip.ptr(p["bcoef"]),
-                                      _hip.ptr(p["partials"]), groups, B, H, W, bn.c, 2, 0, st), "lad_bn_bwd " + bn.name)
-            self._on_side(lambda sst: _hip.check(lib.lad_stem_wgrad_bn(_hip.ptr(x), _hip.ptr(dy), None, _hip.ptr(self.stem_w),
-                                                                       _hip.ptr(p["stem_coef"]), _hip.ptr(p["bcoef"]),
-                                                                       _hip.ptr(p["wgrad_ws"]), _hip.ptr(self.stem_gw), B, H, W,
-                                                                       self.stem_cout, sst), "lad_stem_wgrad_bn"), dy)
+            self._launch("lad_bn_bwd", dy, None, None, p["stem_coef"], bn.g, None, None, None, None, None, bn.gg, bn.gb, None, None,
+                         p["bn_ws"], p["bcoef"], p["partials"], groups, B, H, W, bn.c, 2, 0, tag=bn.name)
+            self._on_side(lambda sst: self._launch("lad_stem_wgrad_bn", x, dy, None, self.stem_w, p["stem_coef"], p["bcoef"], p["wgrad_ws"],
+                                                   self.stem_gw, B, H, W, self.stem_cout, stream=sst), dy)
         if self._defer_on:
             self._defer_on = False
             self._join_side()   # (the one launch that sums every layer's slabs follows the weight-gradient launches of both streams)
-            _hip.check(lib.lad_wgrad_defer_flush(st), "lad_wgrad_defer_flush")
+            self._launch("lad_wgrad_defer_flush")
         self._join_side()
         self._grad_dirty = True
 
@@ -1904,8 +1832,7 @@ class ResNetEngine:
         """accumulated_grad() += scale * flat_grad(): `(loss / gradient_accumulation_steps).backward()` of train.py:287-289
         (the engine's backward overwrites the flat gradient, so the running sum lives in a buffer of its own)."""
         acc = self.accumulated_grad()
-        _hip.check(self.lib().lad_grad_accumulate(_hip.ptr(acc), _hip.ptr(self._flat_g), self._n_flat, float(scale), self._st()),
-                   "lad_grad_accumulate")
+        self._launch("lad_grad_accumulate", acc, self._flat_g, self._n_flat, float(scale))
         return acc
 
     def clip_and_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, grad_scale=1.0, zero_grad=True, grad=None):
@@ -1913,18 +1840,14 @@ class ResNetEngine:
         grad_scale multiplies the gradient first (1/world_size after a sum all-reduce).  grad: the gradient buffer to step
         with (default: the flat gradient; the accumulation buffer under gradient accumulation)."""
         self.ensure_flat()
-        lib, st = self.lib(), self._st()
         g = self._flat_g if grad is None else grad
         if g.numel() != self._n_flat or g.dtype != torch.float32 or not g.is_cuda:
             raise _hip.LadHipError("clip_and_step: grad must be a float32 GPU buffer of the flat parameter size")
         self._step_count += 1  # host mirror; the kernels use the device-side counter (hipGraph replays)
-        _hip.check(lib.lad_grad_sumsq(_hip.ptr(g), self._n_flat, _hip.ptr(self._norm_partials), _hip.ptr(self._step_dev), st),
-                   "lad_grad_sumsq")
-        _hip.check(lib.lad_adam_step(_hip.ptr(self._flat_p), _hip.ptr(g), _hip.ptr(self._exp_avg),
-                                     _hip.ptr(self._exp_avg_sq), self._n_flat, _hip.ptr(self._norm_partials), float(grad_scale),
-                                     float(max_norm if max_norm is not None else 0.0), float(lr), float(betas[0]), float(betas[1]),
-                                     float(eps), self._step_count, _hip.ptr(self._step_dev), 1 if zero_grad else 0,
-                                     _hip.ptr(self._norm_out), st), "lad_adam_step")
+        self._launch("lad_grad_sumsq", g, self._n_flat, self._norm_partials, self._step_dev)
+        self._launch("lad_adam_step", self._flat_p, g, self._exp_avg, self._exp_avg_sq, self._n_flat, self._norm_partials, float(grad_scale),
+                     float(max_norm if max_norm is not None else 0.0), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                     self._step_count, self._step_dev, 1 if zero_grad else 0, self._norm_out)
         self.notify_weights_changed()
         if zero_grad:
             self._grad_dirty = False
@@ -1941,8 +1864,7 @@ class ResNetEngine:
         _hip.require_cuda(labels, "labels", torch.int32)
         if out is None:
             out = torch.zeros(8, device=probs.device)
-        _hip.check(self.lib().lad_bce_metrics(_hip.ptr(probs), _hip.ptr(labels), probs.numel(), _hip.ptr(out), self._st()),
-                   "lad_bce_metrics")
+        self._launch("lad_bce_metrics", probs, labels, probs.numel(), out)
         return out
 
     def metrics(self):

@@ -226,8 +226,7 @@ class HipFbank:
             _hip.require_cuda(out, "out", torch.float32)
             if tuple(out.shape) != (b, t, self._n_out):
                 raise ValueError(f"out must be {(b, t, self._n_out)}")
-        _hip.check(_hip.lib().lad_fbank_forward(self._plan, _hip.ptr(pcm), b, n, _hip.ptr(out),
-                                                _hip.stream_handle(pcm.device)), "lad_fbank_forward")
+        _hip.launch("lad_fbank_forward", self._plan, pcm, b, n, out)
         return out
 
     def extract_long(self, pcm, out=None):
@@ -239,8 +238,7 @@ class HipFbank:
         t = self.num_frames(n)
         if out is None:
             out = torch.empty((t, self._n_out), device=pcm.device, dtype=torch.float32)
-        _hip.check(_hip.lib().lad_fbank_forward_long(self._plan, _hip.ptr(pcm), n, _hip.ptr(out),
-                                                     _hip.stream_handle(pcm.device)), "lad_fbank_forward_long")
+        _hip.launch("lad_fbank_forward_long", self._plan, pcm, n, out)
         return out
 
 

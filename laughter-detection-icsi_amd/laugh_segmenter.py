@@ -33,8 +33,6 @@ from typing import Callable, NamedTuple
 
 import numpy as np
 
-_I32P, _F64P = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-
 
 def frame_span_to_time_span(frame_span, fps=100.):
     return (frame_span[0] / fps, frame_span[1] / fps)
@@ -215,8 +213,8 @@ class Decoder(NamedTuple):
     keys: Callable              # (thresholds, axis_values, ctx) -> ([(threshold, *axis values)], [setting]), thresholds-major; validates
     host_spans: Callable        # (probs, settings, fps, ctx) -> [int64 (n, 2) per setting]
     round_size: Callable        # (lib, n_settings) -> settings per device call
-    count: Callable             # (lib, track, chunk, ws, stream, ctx): lad_*_count of the settings `chunk`
-    fill: Callable              # (lib, track, chunk, ws, counts, total, stream, ctx) -> (the table the scorers read, its counts)
+    count: Callable             # (track, chunk, ws, ctx): lad_*_count of the settings `chunk`
+    fill: Callable              # (track, chunk, ws, counts, total, ctx) -> (the table the scorers read, its counts)
     dir_suffix: Callable        # key -> the directories segment_laughter.py adds below t_<thr>/l_<min_len>
     found_line: Callable        # (n, key) -> what segment_laughter.py prints per setting
 
@@ -289,16 +287,15 @@ def _runs_spans_host(probs, settings, fps, ctx):
     return [run_spans(p > thr) for thr in settings]
 
 
-def _runs_count(lib, track, chunk, ws, stream, ctx):
+def _runs_count(track, chunk, ws, ctx):
     import _hip
-    _hip.check(lib.lad_runs_count(*track, _doubles(chunk), len(chunk), _hip.ptr(ws), stream), "lad_runs_count")
+    _hip.launch("lad_runs_count", *track, _doubles(chunk), len(chunk), ws)
 
 
-def _runs_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+def _runs_fill(track, chunk, ws, counts, total, ctx):
     import _hip
     table = _table(total, ws.device)
-    _hip.check(lib.lad_runs_fill(*track, _doubles(chunk), len(chunk), _hip.ptr(ws), counts.ctypes.data_as(_I32P), _hip.ptr(table), total,
-                                 stream), "lad_runs_fill")
+    _hip.launch("lad_runs_fill", *track, _doubles(chunk), len(chunk), ws, counts, table, total)
     return table[:total], counts
 
 
@@ -367,18 +364,17 @@ def _binarize_spans_host(probs, settings, fps, ctx):
     return spans_list
 
 
-def _binarize_count(lib, track, chunk, ws, stream, ctx):
+def _binarize_count(track, chunk, ws, ctx):
     import _hip
     onset, offset, _ = zip(*chunk)
-    _hip.check(lib.lad_binarize_count(*track, _doubles(onset), _doubles(offset), len(chunk), _hip.ptr(ws), stream), "lad_binarize_count")
+    _hip.launch("lad_binarize_count", *track, _doubles(onset), _doubles(offset), len(chunk), ws)
 
 
-def _binarize_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+def _binarize_fill(track, chunk, ws, counts, total, ctx):
     import _hip
     tables = _table(total, ws.device, 2)    # the hysteresis runs go to tables[0], the merged ones to tables[1] and their counts over the raw ones
-    _hip.check(lib.lad_binarize_fill(*track, *[_doubles(col) for col in zip(*chunk)], len(chunk), _hip.ptr(on_device(ctx, "fps_host", ws.device)),
-                                     ctx["fps_host"].ctypes.data_as(_F64P), _hip.ptr(ws), counts.ctypes.data_as(_I32P), _hip.ptr(tables[0]),
-                                     _hip.ptr(tables[1]), total, stream), "lad_binarize_fill")
+    _hip.launch("lad_binarize_fill", *track, *[_doubles(col) for col in zip(*chunk)], len(chunk), on_device(ctx, "fps_host", ws.device),
+                ctx["fps_host"], ws, counts, tables[0], tables[1], total)
     counts = _read_counts(ws, len(counts))
     return tables[1][:int(counts.sum(dtype=np.int64))], counts
 
@@ -473,18 +469,16 @@ def _viterbi_spans_host(probs, settings, table):
     return [run_spans(on[:, k]) for k in range(K)]
 
 
-def _viterbi_count(lib, track, chunk, ws, stream, ctx):
+def _viterbi_count(track, chunk, ws, ctx):
     import _hip
     bias, penalty = ((ctypes.c_int32 * len(chunk))(*col) for col in zip(*chunk))
-    _hip.check(lib.lad_viterbi_count(*track, _hip.ptr(on_device(ctx, "table", ws.device)), ctx["table"].ctypes.data_as(_I32P), bias, penalty,
-                                     len(chunk), _hip.ptr(ws), _hip.ptr(ctx.get("best")), stream), "lad_viterbi_count")
+    _hip.launch("lad_viterbi_count", *track, on_device(ctx, "table", ws.device), ctx["table"], bias, penalty, len(chunk), ws, ctx.get("best"))
 
 
-def _viterbi_fill(lib, track, chunk, ws, counts, total, stream, ctx):
+def _viterbi_fill(track, chunk, ws, counts, total, ctx):
     import _hip
     runs = _table(total, ws.device)
-    _hip.check(lib.lad_viterbi_fill(_hip.ptr(ws), counts.ctypes.data_as(_I32P), *track[2:], len(chunk), _hip.ptr(runs), total, stream),
-               "lad_viterbi_fill")
+    _hip.launch("lad_viterbi_fill", ws, counts, *track[2:], len(chunk), runs, total)
     return runs[:total], counts
 
 
@@ -521,17 +515,15 @@ def _device_tables(decoder, probs, dtype, chunk, ctx, want_best=False):
     import torch
 
     import _hip
-    lib = _hip.lib()
     C, T = probs.shape
     K = len(chunk)
     ws = _hip.workspace(decoder.lib + "_workspace_bytes", C, T, K, device=probs.device)
     with torch.cuda.device(probs.device):
-        stream = _hip.stream_handle(probs.device)
         ctx["best"] = best = torch.empty(C * K, dtype=torch.int64, device=probs.device) if want_best else None
-        track = (_hip.ptr(probs), dtype, C, T)
-        decoder.count(lib, track, chunk, ws, stream, ctx)
+        track = (probs, dtype, C, T)
+        decoder.count(track, chunk, ws, ctx)
         counts = _read_counts(ws, C * K)
-        table, counts = decoder.fill(lib, track, chunk, ws, counts, int(counts.sum(dtype=np.int64)), stream, ctx)
+        table, counts = decoder.fill(track, chunk, ws, counts, int(counts.sum(dtype=np.int64)), ctx)
         return ws, table, counts, best
 
 

@@ -9,7 +9,6 @@ section 5).
 The filter is designed here in float64 from the closed form of the bilinear transform (no scipy); the kernel runs the
 recurrence as a scan of affine maps.  There is no CPU fallback.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -66,17 +65,12 @@ def filtfilt_device(probs, b, a, lengths=None, out=None):
     out2 = _hip.out_track(out, p2, single, torch.float64)
     if C == 0:
         return out2[0] if single else out2
-    lib = _hip.lib()
-    f64p = ctypes.POINTER(ctypes.c_double)
     bb = np.ascontiguousarray(b, dtype=np.float64)
     aa = np.ascontiguousarray(a, dtype=np.float64)
     zi = zi2(bb, aa)
-    lptr = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if lengths is not None else None
     with torch.cuda.device(p2.device):
         ws = _hip.workspace("lad_lowpass_workspace_bytes", C, T, device=p2.device)
-        _hip.check(lib.lad_lowpass(_hip.ptr(p2), dtype, C, T, lptr, bb.ctypes.data_as(f64p), aa.ctypes.data_as(f64p),
-                                   zi.ctypes.data_as(f64p), _hip.ptr(out2), _hip.ptr(ws), _hip.stream_handle(p2.device)),
-                   "lad_lowpass")
+        _hip.launch("lad_lowpass", p2, dtype, C, T, lengths, bb, aa, zi, out2, ws)
     return out2[0] if single else out2
 
 

@@ -6,7 +6,6 @@ every frame with the track's ends replicated (scipy.ndimage's mode='nearest'), s
 rank = (window - 1) / 2, the minimum rank 0, the maximum rank window - 1.  The result is one of the track's own values, so the
 device form equals the host form (laugh_segmenter.rank_filter) bit for bit.  There is no CPU fallback.
 """
-import ctypes
 
 MAX_WINDOW = 1023      # lad_rank_filter_max_window()
 
@@ -43,11 +42,9 @@ def rank_filter_device(probs, window, rank, lengths=None, out=None):
     out2 = _hip.out_track(out, p2, single, p2.dtype)
     if C == 0 or T == 0:
         return out2[0] if single else out2
-    lptr = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if lengths is not None else None
     with torch.cuda.device(p2.device):
         ws = _hip.workspace("lad_rank_filter_workspace_bytes", C, T, window, device=p2.device)
-        _hip.check(_hip.lib().lad_rank_filter(_hip.ptr(p2), dtype, C, T, lptr, window, rank, _hip.ptr(out2), _hip.ptr(ws),
-                                              _hip.stream_handle(p2.device)), "lad_rank_filter")
+        _hip.launch("lad_rank_filter", p2, dtype, C, T, lengths, window, rank, out2, ws)
     return out2[0] if single else out2
 
 

@@ -119,8 +119,7 @@ class Resampler:
         y = torch.empty(b - a, dtype=torch.float32, device=pcm.device)
         dtype = LAD_RESAMPLE_I16 if pcm.dtype == torch.int16 else LAD_RESAMPLE_F32
         with torch.cuda.device(pcm.device):
-            _hip.check(_hip.lib().lad_resample(_hip.ptr(pcm), dtype, pcm.numel(), _hip.ptr(self.table), self.up, self.down, self.K,
-                                               a, b - a, _hip.ptr(y), _hip.stream_handle(pcm.device)), "lad_resample")
+            _hip.launch("lad_resample", pcm, dtype, pcm.numel(), self.table, self.up, self.down, self.K, a, b - a, y)
         return y
 
 

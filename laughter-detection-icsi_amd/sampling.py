@@ -15,7 +15,6 @@ redrawn on the device before every epoch (csrc/sample.hip), one launch for the w
 The convention (frames and milliseconds, regions, pools, kinds, the Philox counter) is written out in include/lad_hip.h next to
 lad_sample_segments.  The host side here is integer bookkeeping; every draw happens on the device.  No CPU fallback.
 """
-import ctypes
 import math
 from dataclasses import dataclass
 
@@ -182,10 +181,6 @@ class SegmentPools:
                     np.asarray([r[2] for r in rows], np.int32), [r[3] for r in rows])
 
 
-def _i32p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-
-
 class DrawTable:
     """What lad_sample_segments reads, on the device, with the host copies its entry point checks.  The arrays are checked here
     once (ValueError, before anything is uploaded), so a draw hands the library only the small pool tables to check."""
@@ -253,13 +248,10 @@ class DrawTable:
         reg = torch.empty(n, dtype=torch.int32, device=self.device) if region else None
         if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(epoch) < 2 ** 32:
             raise ValueError("seed is 64 bits, epoch 32 bits, neither negative")
-        i64p = ctypes.POINTER(ctypes.c_int64)
         with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().lad_sample_segments(
-                _hip.ptr(self.d_kind), _hip.ptr(self.d_src), n, _hip.ptr(self.d_row_id), _hip.ptr(self.d_regions), len(self.regions),
-                _hip.ptr(self.d_pool_off), _hip.ptr(self.d_pool_cum), len(self.pool_off) - 1, None, None, _i32p(self.pool_off),
-                self.pool_total.ctypes.data_as(i64p), self.T, int(seed), int(epoch), _hip.ptr(chan), _hip.ptr(first), _hip.ptr(count),
-                _hip.ptr(reg), _hip.stream_handle(self.device)), "lad_sample_segments")
+            _hip.launch("lad_sample_segments", self.d_kind, self.d_src, n, self.d_row_id, self.d_regions, len(self.regions), self.d_pool_off,
+                        self.d_pool_cum, len(self.pool_off) - 1, None, None, self.pool_off, self.pool_total, self.T, int(seed), int(epoch),
+                        chan, first, count, reg)
         return (chan, first, count, reg) if region else (chan, first, count)
 
 
@@ -359,8 +351,6 @@ def window_coverage(index_or_sets, channels, chan, first, count, fps):
     dix = sweep_eval.DeviceIndex(channels, bounds, offsets, chan.device)
     out = torch.empty((n, S), dtype=torch.int32, device=chan.device)
     with torch.cuda.device(chan.device):
-        _hip.check(_hip.lib().lad_window_coverage(_hip.ptr(chan), _hip.ptr(first), _hip.ptr(count), n, int(fps), _hip.ptr(dix.bounds),
-                                                  _hip.ptr(dix.offsets), _i32p(dix.bounds_host), _i32p(dix.offsets_host), dix.n_intervals,
-                                                  len(channels), S, _hip.ptr(out), _hip.stream_handle(chan.device)),
-                   "lad_window_coverage")
+        _hip.launch("lad_window_coverage", chan, first, count, n, int(fps), dix.bounds, dix.offsets, dix.bounds_host, dix.offsets_host,
+                    dix.n_intervals, len(channels), S, out)
     return out

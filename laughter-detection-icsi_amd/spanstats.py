@@ -5,11 +5,8 @@ the frame value of every decoder, 0.0 for a NaN frame; the sum of rint(w * 2^32)
 largest, and w there.  Integers and float64 compares only, so the device form equals the host form (laugh_segmenter.span_stats)
 bit for bit; the mean and the peak's time are derived on the host (laugh_segmenter.confidences).  There is no CPU fallback.
 """
-import ctypes
 
 import numpy as np
-
-_I32P = ctypes.POINTER(ctypes.c_int32)
 
 
 def prepare_device(probs, dtype):
@@ -18,12 +15,10 @@ def prepare_device(probs, dtype):
     import torch
 
     import _hip
-    lib = _hip.lib()
     C, T = probs.shape
     ws = _hip.workspace("lad_span_stats_workspace_bytes", C, T, device=probs.device)
     with torch.cuda.device(probs.device):
-        _hip.check(lib.lad_span_stats_prepare(_hip.ptr(probs), dtype, C, T, _hip.ptr(ws), _hip.stream_handle(probs.device)),
-                   "lad_span_stats_prepare")
+        _hip.launch("lad_span_stats_prepare", probs, dtype, C, T, ws)
     return ws
 
 
@@ -33,7 +28,6 @@ def stats_device(probs, dtype, ws, table, counts):
     import torch
 
     import _hip
-    lib = _hip.lib()
     C, T = probs.shape
     counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
     if counts.size == 0 or counts.size % C:
@@ -47,9 +41,7 @@ def stats_device(probs, dtype, ws, table, counts):
         sums = torch.empty(max(total, 1), dtype=torch.int64, device=probs.device)
         peaks = torch.empty(max(total, 1), dtype=torch.int32, device=probs.device)
         values = torch.empty(max(total, 1), dtype=torch.float64, device=probs.device)
-        _hip.check(lib.lad_span_stats(_hip.ptr(probs), dtype, C, T, _hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(_I32P),
-                                      counts.size // C, _hip.ptr(sums), _hip.ptr(peaks), _hip.ptr(values),
-                                      _hip.stream_handle(probs.device)), "lad_span_stats")
+        _hip.launch("lad_span_stats", probs, dtype, C, T, ws, table, counts, counts.size // C, sums, peaks, values)
     return sums[:total], peaks[:total], values[:total]
 
 

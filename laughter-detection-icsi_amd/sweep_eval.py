@@ -432,11 +432,8 @@ def _device_head(probs, what, channels, behind, fps, index, lowpass, median, len
 def _index_and_lengths(dix, ctx, min_lengths):
     """The ten arguments every scoring entry point ends its inputs with: the index on the device and on the host, fps
     (ctx["fps_host"]) on the device and on the host, the min_lengths and their number."""
-    import _hip
-    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    return (_hip.ptr(dix.bounds), _hip.ptr(dix.offsets), dix.bounds_host.ctypes.data_as(i32p), dix.offsets_host.ctypes.data_as(i32p),
-            dix.n_intervals, _hip.ptr(ls.on_device(ctx, "fps_host", dix.device)), ctx["fps_host"].ctypes.data_as(f64p),
-            (ctypes.c_double * len(min_lengths))(*[float(m) for m in min_lengths]), len(min_lengths))
+    return (dix.bounds, dix.offsets, dix.bounds_host, dix.offsets_host, dix.n_intervals, ls.on_device(ctx, "fps_host", dix.device),
+            ctx["fps_host"], (ctypes.c_double * len(min_lengths))(*[float(m) for m in min_lengths]), len(min_lengths))
 
 
 def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, lowpass=None, lengths=None, offset_drops=None,
@@ -478,15 +475,14 @@ def score_sweep_device(probs, channels, thresholds, min_lengths, fps, index, low
         sws = _hip.workspace("lad_score_workspace_bytes", C, dix.n_intervals, n, L, device=probs.device)
         ws, table, counts, _ = ls._device_tables(decoder, probs, dtype, chunk, ctx)
         with torch.cuda.device(probs.device):
-            stream = _hip.stream_handle(probs.device)
             # what the two scorers are given alike: the tables, the index, fps and min_lengths
-            scored = (_hip.ptr(ws), _hip.ptr(table), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), C, T, n, *index_and_lengths)
+            scored = (ws, table, counts, C, T, n, *index_and_lengths)
             scores = torch.empty((C, n, L, len(FIELDS)), dtype=torch.int64, device=probs.device)
-            _hip.check(lib.lad_score_runs(*scored, _hip.ptr(sws), _hip.ptr(scores), stream), "lad_score_runs")
+            _hip.launch("lad_score_runs", *scored, sws, scores)
             if criteria is not None:
                 ews = _hip.workspace("lad_score_events_workspace_bytes", C, dix.n_intervals, n, L, len(table), device=probs.device)
                 ev = torch.empty((C, n, L, len(EVENT_FIELDS)), dtype=torch.int64, device=probs.device)
-                _hip.check(lib.lad_score_events(*scored, *criteria, _hip.ptr(ews), _hip.ptr(ev), stream), "lad_score_events")
+                _hip.launch("lad_score_events", *scored, *criteria, ews, ev)
                 ev_parts.append(ev.cpu().numpy())
         parts.append(scores.cpu().numpy())
     scores = np.concatenate(parts, axis=1).reshape(out_shape)
@@ -640,21 +636,17 @@ def score_surface_device(probs, channels, levels, min_lengths, fps, index, lowpa
         return empty
     probs, dtype, dix, fps_host, criteria = head
     C, T = probs.shape
-    lib = _hip.lib()
     size_query = "lad_surface_workspace_bytes" if criteria is None else "lad_surface_events_workspace_bytes"
     with torch.cuda.device(probs.device):
         ws = _hip.workspace(size_query, C, T, dix.n_intervals, K, L, device=probs.device)
         scores = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
         ctx = {"fps_host": fps_host}
-        track_and_index = (_hip.ptr(probs), dtype, C, T, lv.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), K,
-                           *_index_and_lengths(dix, ctx, min_lengths))
-        stream = _hip.stream_handle(probs.device)
+        track_and_index = (probs, dtype, C, T, lv, K, *_index_and_lengths(dix, ctx, min_lengths))
         if criteria is None:
-            _hip.check(lib.lad_score_surface(*track_and_index, _hip.ptr(ws), _hip.ptr(scores), stream), "lad_score_surface")
+            _hip.launch("lad_score_surface", *track_and_index, ws, scores)
             return scores.cpu().numpy()
         ev = torch.empty(out_shape, dtype=torch.int64, device=probs.device)
-        _hip.check(lib.lad_score_surface_events(*track_and_index, *criteria, _hip.ptr(ws), _hip.ptr(scores), _hip.ptr(ev), stream),
-                   "lad_score_surface_events")
+        _hip.launch("lad_score_surface_events", *track_and_index, *criteria, ws, scores, ev)
         return scores.cpu().numpy(), ev.cpu().numpy()
 
 
