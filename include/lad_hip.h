@@ -1202,6 +1202,34 @@ int lad_bootstrap_quantiles(const int64_t *sums, int64_t columns, int32_t replic
                             const int32_t *figures_host, int64_t n_figures, const int32_t *q_num, const int32_t *q_den,
                             int32_t n_quantiles, int64_t *out, int32_t *valid, void *stream);
 
+/* Pairs of figures: the difference of two systems, and the harmonic mean of two figures of one (event F1), under the same
+ * resamples.  A pair is 13 int32: (op, figure1[6], figure2[6]); both figures are six-integer figures as above, over columns of
+ * the one sums matrix.  For replicate b each figure gives (n, d) and a validity by the rule above, the substitution of 1 / 1
+ * included; the pair is valid for b iff both figures are.  n1, d1, n2, d2 are below 2^54.
+ *
+ * The value of a valid replicate is N / D:
+ *   op 0, difference:     N = n1 * d2 - n2 * d1 (signed), D = d1 * d2;
+ *   op 1, harmonic mean:  N = 2 * n1 * n2, D = n1 * d2 + n2 * d1, and the value 0 / 1 where D is 0 (both numerators are 0 then:
+ *                         event_f1's rule "0 where precision + recall is 0").
+ * |N| and D are below 2^109.  No other op is accepted.
+ *
+ * Order.  The valid replicates are ordered by the exact value N / D: by the sign of N first, then |N_i| * D_j against |N_j| * D_i as
+ * 256-bit products (built from 64-bit halves; of two negative values the larger magnitude comes first); equal values by the
+ * replicate number, ascending.  v = the number of valid replicates; quantile q_num / q_den is the replicate at rank
+ * max(ceil(q_num * v / q_den) - 1, 0) of that order.
+ *
+ * sums, q_num, q_den, n_quantiles: as for lad_bootstrap_quantiles.  pairs: DEVICE int32 [n_pairs][13] and pairs_host, the same
+ * values on the HOST, checked before anything is launched (op 0 or 1, columns in range, num_mult 1 or 2, the flag 0 or 1).
+ * out: DEVICE int64 [n_pairs][n_quantiles][4], the (n1, d1, n2, d2) of that replicate after the substitution, all -1 when v == 0:
+ * the host forms N / D from them and divides once.  valid: DEVICE int32 [n_pairs].  signs: DEVICE int32 [n_pairs][3], how many
+ * valid replicates have N < 0, N == 0 and N > 0.
+ * The family's refusals hold (a bad op is a bad figure; each of the three outputs against the sums, the pairs and one another).
+ * n_pairs == 0 is LAD_OK without a launch.  One launch, one workgroup per pair; the whole order in LDS, 36 bytes a replicate
+ * (padded to a power of two): 144 KiB at 4096.  No global atomics; identical bytes on every call. */
+int lad_bootstrap_pair_quantiles(const int64_t *sums, int64_t columns, int32_t replicates, const int32_t *pairs,
+                                 const int32_t *pairs_host, int64_t n_pairs, const int32_t *q_num, const int32_t *q_den,
+                                 int32_t n_quantiles, int64_t *out, int32_t *valid, int32_t *signs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

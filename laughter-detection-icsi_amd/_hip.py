@@ -244,6 +244,8 @@ SIGNATURES = {
     "lad_bootstrap_sums": (c_int, [c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p]),
     "lad_bootstrap_quantiles": (c_int, [c_void_p, c_i64, c_i32, c_void_p, ctypes.POINTER(c_i32), c_i64, ctypes.POINTER(c_i32),
                                         ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p]),
+    "lad_bootstrap_pair_quantiles": (c_int, [c_void_p, c_i64, c_i32, c_void_p, ctypes.POINTER(c_i32), c_i64, ctypes.POINTER(c_i32),
+                                             ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -9,6 +9,9 @@ fractions, the rank of a quantile); tests/_bootstrap_model.py is a second implem
     select_host / quantiles_device     per figure the (num, den) pairs at the ranks of the quantiles, and the number of valid replicates
     intervals_host / intervals_device  the three steps for a matrix of cells (a few columns per cell and one shared last column),
                                        the device form in chunks of cells so that no sums buffer exceeds SUMS_BYTES_CAP
+    pair_select_host / pair_quantiles_device    per pair of figures (their difference, or their harmonic mean) the (n1, d1, n2, d2) at
+                                       the ranks of the quantiles, the valid replicates and how many lie below, at and above 0
+    pair_intervals_host / pair_intervals_device the same three steps for the cells of two systems under one set of resamples
 
 The host forms are numpy and Python integers and never produce a float; the device forms are csrc/bootstrap.hip and have no CPU
 fallback.  Both return the same integers.  sweep_eval.bootstrap_sum_stats_host / _device build the rows from them.
@@ -230,3 +233,162 @@ def intervals_device(x, per_cell, template, n_boot, seed, quantiles, device="cud
     out = np.concatenate(outs) if outs else np.zeros((0, Q, 2), np.int64)
     valid = np.concatenate(valids) if valids else np.zeros(0, np.int32)
     return out.reshape(n_cells, len(template), Q, 2), valid.reshape(n_cells, len(template))
+
+
+# ---- pairs of figures: the difference of two systems and the harmonic mean of two figures (lad_bootstrap_pair_quantiles) --------------
+DIFFERENCE, HARMONIC = 0, 1    # the op of a pair
+_PAIR_KEY_SHIFT = 220
+
+
+def pair_fraction(op, n1, d1, n2, d2):
+    """The value of a pair as Python integers (N, D), D > 0: op 0 n1 / d1 - n2 / d2 = (n1 d2 - n2 d1) / (d1 d2); op 1 the harmonic
+    mean 2 n1 n2 / (n1 d2 + n2 d1), 0 / 1 where that denominator is 0."""
+    n1, d1, n2, d2 = int(n1), int(d1), int(n2), int(d2)
+    if op == DIFFERENCE:
+        return n1 * d2 - n2 * d1, d1 * d2
+    if op != HARMONIC:
+        raise ValueError(f"op is {DIFFERENCE} (difference) or {HARMONIC} (harmonic mean), got {op}")
+    den = n1 * d2 + n2 * d1
+    return (2 * n1 * n2, den) if den else (0, 1)
+
+
+def pair_value(op, entry):
+    """The reported number of one entry (n1, d1, n2, d2) of pair_select_host / pair_quantiles_device: one correctly rounded
+    conversion of the exact fraction (Python's int / int); NaN for the all -1 entry of an empty order."""
+    if int(entry[1]) < 0:
+        return float("nan")
+    num, den = pair_fraction(op, *entry)
+    return num / den
+
+
+def _replicate_fractions(sums, figure, f):
+    """Per replicate the (n, d) of a six-integer figure after the substitution, None where the replicate is invalid."""
+    num_col, mult, den_a, den_b, valid_col, one = figure
+    num = (sums[:, num_col] * mult).tolist()
+    den = (sums[:, den_a] + (sums[:, den_b] if den_b >= 0 else 0)).tolist()
+    good = (sums[:, valid_col] != 0).tolist() if valid_col >= 0 else [True] * len(num)
+    out = []
+    for n, d, g in zip(num, den, good):
+        if d == 0:
+            n, d, g = (1, 1, g) if one else (0, 0, False)
+        if g and d >= 1 << 54:
+            raise ValueError(f"pair {f}: a denominator of {d} is beyond the contract (below 2^54)")
+        out.append((n, d) if g else None)
+    return out
+
+
+def pair_select_host(sums, pairs, quantiles):
+    """sums int64 (B, M); pairs [(op, figure1, figure2)] or 13 integers each, the figures as select_host takes them; quantiles
+    [(num, den)] -> (out int64 (P, Q, 4) of (n1, d1, n2, d2), valid int32 (P,), signs int32 (P, 3)).  Python integers throughout:
+    the order is that of floor(N * 2^220 / D), which is the order of the values (two different ones, with D below 2^109, differ by
+    more than 2^-218) and equal for equal values; then the replicate number."""
+    sums = np.asarray(sums, np.int64)
+    pairs = np.asarray([_flat_pair(p) for p in pairs], np.int64).reshape(-1, 13).tolist()
+    out = np.full((len(pairs), len(quantiles), 4), -1, np.int64)
+    valid = np.zeros(len(pairs), np.int32)
+    signs = np.zeros((len(pairs), 3), np.int32)
+    for f, pair in enumerate(pairs):
+        op = pair[0]
+        kept = []
+        for b, (one, two) in enumerate(zip(_replicate_fractions(sums, pair[1:7], f), _replicate_fractions(sums, pair[7:13], f))):
+            if one is not None and two is not None:
+                num, den = pair_fraction(op, *one, *two)
+                kept.append(((num << _PAIR_KEY_SHIFT) // den, b, one + two))
+                signs[f, 1 + (num > 0) - (num < 0)] += 1
+        kept.sort()
+        valid[f] = len(kept)
+        if kept:
+            for j, (qn, qd) in enumerate(quantiles):
+                out[f, j] = kept[rank_of(qn, qd, len(kept))][2]
+    return out, valid, signs
+
+
+def _flat_pair(pair):
+    """(op, figure1, figure2) or the 13 integers themselves -> the 13 integers."""
+    pair = list(pair)
+    return [pair[0], *pair[1], *pair[2]] if len(pair) == 3 else pair
+
+
+def pair_quantiles_device(sums, pairs, quantiles):
+    """pair_select_host for sums in GPU memory (lad_bootstrap_pair_quantiles): only out, valid and signs cross to the host."""
+    import torch
+
+    import _hip
+    _hip.require_cuda(sums, "sums", torch.int64)
+    B, M = sums.shape
+    pairs_host = np.ascontiguousarray(np.asarray([_flat_pair(p) for p in pairs], np.int32).reshape(-1, 13))
+    P, Q = len(pairs_host), len(quantiles)
+    with torch.cuda.device(sums.device):
+        pd = torch.from_numpy(pairs_host if P else np.zeros((1, 13), np.int32)).to(sums.device)
+        out = torch.empty((max(P, 1), Q, 4), dtype=torch.int64, device=sums.device)
+        valid = torch.empty((max(P, 1),), dtype=torch.int32, device=sums.device)
+        signs = torch.empty((max(P, 1), 3), dtype=torch.int32, device=sums.device)
+        q_num, q_den = ((ctypes.c_int32 * Q)(*[q[i] for q in quantiles]) for i in (0, 1))
+        _hip.launch("lad_bootstrap_pair_quantiles", sums, M, B, pd, pairs_host, P, q_num, q_den, Q, out, valid, signs)
+        return out[:P].cpu().numpy(), valid[:P].cpu().numpy(), signs[:P].cpu().numpy()
+
+
+def pair_cell_figures(template, cell, per_cell, n_cells, shared_col):
+    """The pairs of one cell from its template [(op, figure1, figure2)]: a figure is (system, num_col, num_mult, den_col_a,
+    den_col_b, valid_col, empty_is_one), system 0 (A) or 1 (B), its columns as cell_figures reads them within that system's cell:
+    column c >= 0 is (system * n_cells + cell) * per_cell + c."""
+    def figure(fg):
+        system, (n, mult, a, b, v, one) = fg[0], fg[1:]
+
+        def col(c):
+            return -1 if c is None else shared_col if c == SHARED else (system * n_cells + cell) * per_cell + c
+        return (col(n), mult, col(a), col(b), col(v), one)
+    return [(op, figure(one), figure(two)) for op, one, two in template]
+
+
+def _pair_split(x, per_cell, systems, template):
+    n_cells, rest = divmod(x.shape[1] - 1, per_cell * systems)
+    if systems not in (1, 2) or rest:
+        raise ValueError(f"{x.shape[1]} columns are not the cells of {systems} system(s), {per_cell} columns each, and one shared column")
+    if any(fg[0] not in range(systems) for _, one, two in template for fg in (one, two)):
+        raise ValueError(f"a figure of the template reads a system outside 0..{systems - 1}")
+    return n_cells
+
+
+def pair_intervals_host(x, per_cell, template, n_boot, seed, quantiles, systems=2):
+    """x int64 (G, systems * n_cells * per_cell + 1): the cells of system A, then the same cells of system B, then one column shared
+    by all (systems=1: one system's cells and the shared column, for pairs of its own figures).  template: the pairs of a cell
+    (pair_cell_figures).  The weights are those of intervals_host for this seed: the two systems, and a separate evaluation of
+    either, see the same resamples.  -> (out int64 (n_cells, len(template), Q, 4), valid int32 (n_cells, len(template)), signs
+    int32 (n_cells, len(template), 3))."""
+    x = check_matrix(x)
+    n_cells = _pair_split(x, per_cell, systems, template)
+    sums = sums_host(x, weights_host(x.shape[0], n_boot, seed))
+    pairs = [p for cell in range(n_cells) for p in pair_cell_figures(template, cell, per_cell, n_cells, x.shape[1] - 1)]
+    out, valid, signs = pair_select_host(sums, pairs, quantiles)
+    T = len(template)
+    return out.reshape(n_cells, T, len(quantiles), 4), valid.reshape(n_cells, T), signs.reshape(n_cells, T, 3)
+
+
+def pair_intervals_device(x, per_cell, template, n_boot, seed, quantiles, systems=2, device="cuda", cap=None):
+    """pair_intervals_host on the GPU: the matrix is uploaded once, the weights are drawn once and shared by both systems (that is
+    the pairing), and the cells go through lad_bootstrap_sums + lad_bootstrap_pair_quantiles in chunks.  A chunk holds the same
+    cells of every system and the shared column, and its sums buffer stays within `cap` bytes (default SUMS_BYTES_CAP; at least
+    one cell a chunk).  Equal to pair_intervals_host whatever the chunk size."""
+    import torch
+    x = check_matrix(x)
+    n_cells = _pair_split(x, per_cell, systems, template)
+    cap = SUMS_BYTES_CAP if cap is None else cap
+    step = max(1, (cap // (8 * n_boot) - 1) // (per_cell * systems))
+    weights = weights_device(x.shape[0], n_boot, seed, device)
+    xd = torch.from_numpy(x).to(weights.device)
+    outs, valids, signs = [], [], []
+    for c0 in range(0, n_cells, step):
+        n = min(step, n_cells - c0)
+        parts = [xd[:, (s * n_cells + c0) * per_cell:(s * n_cells + c0 + n) * per_cell] for s in range(systems)]
+        chunk = torch.cat(parts + [xd[:, -1:]], dim=1).contiguous()
+        pairs = [p for cell in range(n) for p in pair_cell_figures(template, cell, per_cell, n, systems * n * per_cell)]
+        out, valid, sign = pair_quantiles_device(sums_device(chunk, weights), pairs, quantiles)
+        outs.append(out)
+        valids.append(valid)
+        signs.append(sign)
+    Q, T = len(quantiles), len(template)
+    out = np.concatenate(outs) if outs else np.zeros((0, Q, 4), np.int64)
+    valid = np.concatenate(valids) if valids else np.zeros(0, np.int32)
+    sign = np.concatenate(signs) if signs else np.zeros((0, 3), np.int32)
+    return out.reshape(n_cells, T, Q, 4), valid.reshape(n_cells, T), sign.reshape(n_cells, T, 3)

@@ -51,8 +51,15 @@ percentile-bootstrap interval each and the number of valid replicates (sweep_eva
 csrc/bootstrap.hip through sweep_eval.bootstrap_sum_stats_device under the device scorer: the same bytes), from B resamples of the
 recording units (`--bootstrap_unit channel`, the default, or `meeting`), the resamples a pure function of `--bootstrap_seed`
 (default 0), the interval the central `--bootstrap_level` per cent (default 95).  With `--events` or `--event_grid` it also writes
-`event_sum_stats_ci.csv` (event precision and recall; event F1 is not a ratio of sums and has no interval).  It works with every
-decoder family and both grids.  Without the flag the directory holds what it held before.
+`event_sum_stats_ci.csv` (event precision and recall; with `--bootstrap_event_f1` also event_f1, event_f1_lo and event_f1_hi in
+front of n_boot_valid: event F1 is not a ratio of sums, its replicates are exact harmonic means ordered by
+lad_bootstrap_pair_quantiles).  It works with every decoder family and both grids.  Without the flag the directory holds what it
+held before.
+`--compare_probs_dir DIR` (needs `--bootstrap`; default: absent) is a second system B for the same channels: its tracks go through
+the same smoother, decoder and scorer as those of `--probs_dir` (system A), and `sum_stats_diff.csv` has per setting both systems'
+precision, recall and F1, the exact difference A - B, its interval under the same resamples and the share of resamples in which A
+is strictly greater (sweep_eval.bootstrap_diff_sum_stats_host / _device: the same bytes under either scorer); with `--events` /
+`--event_grid` also `event_sum_stats_diff.csv`, for event precision and recall.  Every other file is that of `--probs_dir` alone.
 """
 import argparse
 import csv
@@ -247,12 +254,22 @@ def build_parser():
     parser.add_argument('--bootstrap_unit', type=str, default='channel', choices=['channel', 'meeting'],
                         help='what is resampled: the evaluated channels, or the meetings (three meetings have ten distinct '
                              'resamples); default: channel')
+    parser.add_argument('--bootstrap_event_f1', action='store_true',
+                        help='with --bootstrap and --events / --event_grid: event_sum_stats_ci.csv also has event_f1 with its interval')
+    parser.add_argument('--compare_probs_dir', type=str, default=None, metavar='DIR',
+                        help='(needs --bootstrap) a second system for the same channels, <meeting>/<chan>.npy as --probs_dir: also write '
+                             'sum_stats_diff.csv (and event_sum_stats_diff.csv with --events / --event_grid), the difference --probs_dir '
+                             'minus DIR of every figure with its interval under the same resamples; default: absent')
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.compare_probs_dir is not None and args.bootstrap is None:
+        raise SystemExit("--compare_probs_dir needs --bootstrap: the comparison is an interval of the difference")
+    if args.bootstrap_event_f1 and (args.bootstrap is None or not (args.events or args.event_grid is not None)):
+        raise SystemExit("--bootstrap_event_f1 needs --bootstrap and --events or --event_grid")
     if args.median is not None and args.lowpass is not None:
         raise SystemExit("--median cannot be combined with --lowpass: they are two smoothers for the same place")
     grid = args.threshold_grid
@@ -276,10 +293,16 @@ def main(argv=None):
     chans = read_csv(args.channels, sweep_eval.CHANNEL_COLUMNS, ("length",))
     index = sweep_eval.TranscriptIndex(rows, chans)
     channels, tracks = load_tracks(args.probs_dir, index)
+    systems = [tracks]
+    if args.compare_probs_dir is not None:
+        channels_b, tracks_b = load_tracks(args.compare_probs_dir, index)
+        if channels_b != channels:
+            raise SystemExit(f"--compare_probs_dir holds {len(channels_b)} channels, --probs_dir {len(channels)}: they must be the same "
+                             f"(differing: {sorted(set(channels) ^ set(channels_b))[:4]})")
+        systems.append(tracks_b)
     length = {(c["meeting_id"], c["chan"]): c["length"] for c in chans}
-    fps = [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
     if args.lowpass is not None:
-        for (meeting, chan), t in zip(channels, tracks):
+        for (meeting, chan), t in [ct for system in systems for ct in zip(channels, system)]:
             if len(t) <= 9:
                 raise ValueError(f"--lowpass: the track of {meeting}/{chan} has {len(t)} frames, the filter needs more than 9")
     extra = dict(offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties)
@@ -289,23 +312,23 @@ def main(argv=None):
         raise SystemExit("--penalties cannot be combined with --offset_drops / --min_gaps")
     with_events = args.events or args.event_grid is not None
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if with_events else {}
-    if grid is not None:
+
+    def score(tracks):
+        fps = [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
         if args.scorer == "device":
-            scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True, median=args.median, **criteria)
-        else:
-            if args.lowpass is not None:
-                tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
-            elif args.median is not None:
-                tracks = [laugh_segmenter.median_filter(t, args.median) for t in tracks]
-            scores = sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index, **criteria)
-    elif args.scorer == "device":
-        scores = score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, median=args.median, **extra, **criteria)
-    else:
+            if grid is not None:
+                return score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True,
+                                    median=args.median, **criteria)
+            return score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, median=args.median, **extra,
+                                **criteria)
         if args.lowpass is not None:
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
         elif args.median is not None:
             tracks = [laugh_segmenter.median_filter(t, args.median) for t in tracks]
-        scores = sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
+        if grid is not None:
+            return sweep_eval.score_surface_host(tracks, channels, thresholds, min_lengths, fps, index, **criteria)
+        return sweep_eval.score_sweep_host(tracks, channels, thresholds, min_lengths, fps, index, **extra, **criteria)
+    scores = score(tracks)
     if with_events:
         scores, events = scores
     per_meeting = sweep_eval.eval_rows(scores, channels, thresholds, min_lengths, index, **extra)
@@ -329,11 +352,24 @@ def main(argv=None):
     if args.bootstrap is not None:
         resample = sweep_eval.bootstrap_sum_stats_device if args.scorer == "device" else sweep_eval.bootstrap_sum_stats_host
         ci = resample(scores, channels, thresholds, min_lengths, index, n_boot=args.bootstrap, seed=args.bootstrap_seed,
-                      level=args.bootstrap_level, unit=args.bootstrap_unit, events=events if with_events else None, **extra)
+                      level=args.bootstrap_level, unit=args.bootstrap_unit, events=events if with_events else None, **extra,
+                      **({"event_f1": True} if args.bootstrap_event_f1 else {}))
         if with_events:
             ci, event_ci = ci
-            write("event_sum_stats_ci.csv", sweep_eval.EVENT_SUM_CI_COLUMNS, event_ci)
+            write("event_sum_stats_ci.csv", sweep_eval.EVENT_SUM_CI_F1_COLUMNS if args.bootstrap_event_f1 else sweep_eval.EVENT_SUM_CI_COLUMNS,
+                  event_ci)
         write("sum_stats_ci.csv", sweep_eval.SUM_CI_COLUMNS, ci)
+    if args.compare_probs_dir is not None:
+        scores_b = score(systems[1])
+        scores_b, events_b = scores_b if with_events else (scores_b, None)
+        compare = sweep_eval.bootstrap_diff_sum_stats_device if args.scorer == "device" else sweep_eval.bootstrap_diff_sum_stats_host
+        diff = compare(scores, scores_b, channels, thresholds, min_lengths, index, n_boot=args.bootstrap, seed=args.bootstrap_seed,
+                       level=args.bootstrap_level, unit=args.bootstrap_unit, events_a=events if with_events else None, events_b=events_b,
+                       **extra)
+        if with_events:
+            diff, event_diff = diff
+            write("event_sum_stats_diff.csv", sweep_eval.EVENT_SUM_DIFF_COLUMNS, event_diff)
+        write("sum_stats_diff.csv", sweep_eval.SUM_DIFF_COLUMNS, diff)
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

@@ -35,6 +35,8 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
     bootstrap_sum_stats_host    percentile-bootstrap intervals of precision, recall and F1 (and of event precision / recall with
                            events=) over those units: exact quantiles of ratios of integer sums (bootstrap.py)
     bootstrap_sum_stats_device  the same rows from csrc/bootstrap.hip.  No CPU fallback.
+    bootstrap_diff_sum_stats_host / _device   two systems scored on the same channels: their point figures, the exact difference A - B
+                           with its interval under the same resamples, and the share of resamples in which A is strictly better
 
 Everything is integer arithmetic plus a few IEEE float64 operations, so host and device agree exactly.
 """
@@ -870,8 +872,26 @@ def _ratio(num, den):
     return float("nan") if num < 0 else int(num) / int(den)
 
 
-def _bootstrap_sum_stats(intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events, offset_drops,
-                         min_gaps, penalties):
+def _number(fraction):
+    """One IEEE division for a fraction (num, den) of Python integers; NaN for None (a figure that does not exist)."""
+    return float("nan") if fraction is None else fraction[0] / fraction[1]
+
+
+def _time_fractions(cell, transc):
+    """Precision, recall and F1 of a cell (pred_ms, corr_ms) as (num, den), None where the figure is NaN."""
+    pred, corr = cell
+    return ((corr, pred) if pred else (1, 1), (corr, transc) if transc else None, (2 * corr, pred + transc) if transc else None)
+
+
+def _event_fractions(cell, _):
+    """Event precision and recall of a cell (n_valid, pred_hit, ref_hit, n_ref) as (num, den), None where the figure is NaN."""
+    n_valid, pred_hit, ref_hit, n_ref = cell
+    return ((pred_hit, n_valid) if n_valid else (1, 1), (ref_hit, n_ref) if n_ref else None)
+
+
+def _sweep_cells(scores, channels, thresholds, min_lengths, events, offset_drops, min_gaps, penalties):
+    """What both bootstraps ask of a score array: (scores, its cells -- _cells runs in the array's own order --, their order in
+    calc_sum_stats' rows)."""
     scores = np.asarray(scores)
     axes = ls.decoder_for(offset_drops, min_gaps, penalties)[1]
     cells = _cells(list(thresholds), list(min_lengths), axes)
@@ -879,44 +899,56 @@ def _bootstrap_sum_stats(intervals, scores, channels, thresholds, min_lengths, i
         raise ValueError(f"scores {scores.shape} are not of this sweep")
     if events is not None and np.asarray(events).shape != scores.shape:
         raise ValueError(f"scores {scores.shape} and events {np.asarray(events).shape} are not of one sweep")
+    return scores, cells, sorted(range(len(cells)), key=lambda j: (cells[j][2], cells[j][1], *cells[j][3]))
+
+
+def _event_fields(flat, events):
+    """(C, n_cells, 4): a cell of the event matrix, (n_valid, pred_hit, ref_hit, n_ref)."""
+    ev = np.asarray(events).reshape(flat.shape[0], flat.shape[1], len(EVENT_FIELDS))
+    return np.stack([flat[:, :, 1], ev[:, :, 3], ev[:, :, 2], ev[:, :, 0]], axis=2)
+
+
+def _bootstrap_sum_stats(intervals, pair_intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events,
+                         offset_drops, min_gaps, penalties, event_f1):
+    if event_f1 and events is None:
+        raise ValueError("event_f1=True needs events=")
+    scores, cells, order = _sweep_cells(scores, channels, thresholds, min_lengths, events, offset_drops, min_gaps, penalties)
     unit_of, transc_ms = bootstrap_units(channels, index, unit)
     if not transc_ms:
         raise ValueError("no channel with a participant: nothing to resample")
     quantiles = bootstrap.quantile_pairs(level)
-    order = sorted(range(len(cells)), key=lambda j: (cells[j][2], cells[j][1], *cells[j][3]))          # calc_sum_stats' order
-    flat = scores.reshape(len(channels), len(cells), len(FIELDS))                  # (_cells runs in the array's own order)
-    nan = float("nan")
+    flat = scores.reshape(len(channels), len(cells), len(FIELDS))
 
-    def rows_of(x, per_cell, template, point):
+    def rows_of(x, per_cell, template, fractions):
         out, valid = intervals(x, per_cell, template, n_boot, seed, quantiles)
         total = [int(v) for v in x.sum(axis=0)]
         rows = []
         for j in order:
             _, thr, min_l, extra = cells[j]
             row = [thr, min_l, *extra]
-            for f, figure in enumerate(point(total[j * per_cell:(j + 1) * per_cell], total[-1])):
-                row += [figure, _ratio(*out[j, f, 0]), _ratio(*out[j, f, 1])]
+            for f, figure in enumerate(fractions(total[j * per_cell:(j + 1) * per_cell], total[-1])):
+                row += [_number(figure), _ratio(*out[j, f, 0]), _ratio(*out[j, f, 1])]
             rows.append(row + [int(valid[j].min())])
         return rows
 
-    def time_point(cell, transc):
-        pred, corr = cell
-        return (1.0 if pred == 0 else corr / pred, nan if transc == 0 else corr / transc, nan if transc == 0 else 2 * corr / (pred + transc))
-
-    def event_point(cell, _):
-        n_valid, pred_hit, ref_hit, n_ref = cell
-        return (1.0 if n_valid == 0 else pred_hit / n_valid, nan if n_ref == 0 else ref_hit / n_ref)
-
-    time_rows = rows_of(_unit_matrix(flat[:, :, 2:4], unit_of, transc_ms), 2, _TIME_FIGURES, time_point)
+    time_rows = rows_of(_unit_matrix(flat[:, :, 2:4], unit_of, transc_ms), 2, _TIME_FIGURES, _time_fractions)
     if events is None:
         return time_rows
-    ev = np.asarray(events).reshape(flat.shape[0], flat.shape[1], len(EVENT_FIELDS))
-    fields = np.stack([flat[:, :, 1], ev[:, :, 3], ev[:, :, 2], ev[:, :, 0]], axis=2)
-    return time_rows, rows_of(_unit_matrix(fields, unit_of, transc_ms), 4, _EVENT_FIGURES, event_point)
+    x = _unit_matrix(_event_fields(flat, events), unit_of, transc_ms)
+    event_rows_ = rows_of(x, 4, _EVENT_FIGURES, _event_fractions)
+    if event_f1:
+        # the harmonic mean of the cell's own precision and recall (valid where both are: where recall is, so n_boot_valid stands)
+        out, _, _ = pair_intervals(x, 4, _EVENT_F1_PAIR, n_boot, seed, quantiles, systems=1)
+        total = [int(v) for v in x.sum(axis=0)]
+        for row, j in zip(event_rows_, order):
+            n_valid, pred_hit, ref_hit, n_ref = total[4 * j:4 * j + 4]
+            point = _event_figures(n_ref, 0, ref_hit, n_valid, pred_hit, 0, 0, 0)[2]           # (event_sum_stats' own arithmetic)
+            row[-1:-1] = [float(point), *(bootstrap.pair_value(bootstrap.HARMONIC, out[j, 0, k]) for k in (0, 1))]
+    return time_rows, event_rows_
 
 
 def bootstrap_sum_stats_host(scores, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95, unit="channel", events=None,
-                             offset_drops=None, min_gaps=None, penalties=None):
+                             offset_drops=None, min_gaps=None, penalties=None, event_f1=False):
     """Percentile-bootstrap intervals of calc_sum_stats' figures over recording units (include/lad_hip.h: lad_bootstrap_weights has
     the convention).  scores: the array of any of the four scorers for `channels`; the decoder's lists as eval_rows takes them.
     The units (bootstrap_units: channels, or meetings) are resampled with replacement n_boot times, the weights a pure function of
@@ -931,20 +963,118 @@ def bootstrap_sum_stats_host(scores, channels, thresholds, min_lengths, index, n
     interval without a valid replicate is NaN.
     events: the second array of a scorer called with events= -> (rows, event rows), the second of EVENT_SUM_CI_COLUMNS:
     event_precision = pred_hit / n_valid (1 without a valid prediction), event_recall = ref_hit / n_ref (valid iff n_ref > 0).
-    Event F1 is not a ratio of sums and has no interval here; nor have average precision or the difference of two systems.
+    event_f1=True (with events=): the event rows carry event_f1, event_f1_lo, event_f1_hi in front of n_boot_valid
+    (EVENT_SUM_CI_F1_COLUMNS).  Event F1 is not a ratio of sums: a replicate's value is the exact harmonic mean of its event
+    precision and recall (bootstrap.HARMONIC: 0 where both are 0), the replicates are ordered by 256-bit cross products, and the
+    two ends are one conversion of an exact fraction each; the point figure is event_sum_stats' event_f1, by its own arithmetic.
+    The difference of two systems is bootstrap_diff_sum_stats_host; event F1 of two systems is not differenced (a difference of
+    two harmonic means is four figures and 512-bit products), and average precision has no interval.
     This is the parity form: numpy and Python integers, no float before the final division."""
-    return _bootstrap_sum_stats(bootstrap.intervals_host, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events,
-                                offset_drops, min_gaps, penalties)
+    return _bootstrap_sum_stats(bootstrap.intervals_host, bootstrap.pair_intervals_host, scores, channels, thresholds, min_lengths, index,
+                                n_boot, seed, level, unit, events, offset_drops, min_gaps, penalties, event_f1)
 
 
 def bootstrap_sum_stats_device(scores, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95, unit="channel", events=None,
-                               offset_drops=None, min_gaps=None, penalties=None, device="cuda"):
+                               offset_drops=None, min_gaps=None, penalties=None, event_f1=False, device="cuda"):
     """bootstrap_sum_stats_host on the GPU (csrc/bootstrap.hip through bootstrap.intervals_device): the per-unit matrix is checked
     on the host (0 <= x < 2^40) and uploaded once, the cells go through lad_bootstrap_sums and lad_bootstrap_quantiles in chunks
     whose sums buffer stays within bootstrap.SUMS_BYTES_CAP, and only the selected pairs and the valid counts come back.  Equal
-    rows (NaN matching NaN) whatever the chunk size.  No CPU fallback."""
+    rows (NaN matching NaN) whatever the chunk size; event_f1=True through lad_bootstrap_pair_quantiles.  No CPU fallback."""
 
     def intervals(x, per_cell, template, n_boot, seed, quantiles):
         return bootstrap.intervals_device(x, per_cell, template, n_boot, seed, quantiles, device=device)
-    return _bootstrap_sum_stats(intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events, offset_drops,
-                                min_gaps, penalties)
+
+    def pair_intervals(x, per_cell, template, n_boot, seed, quantiles, systems=2):
+        return bootstrap.pair_intervals_device(x, per_cell, template, n_boot, seed, quantiles, systems=systems, device=device)
+    return _bootstrap_sum_stats(intervals, pair_intervals, scores, channels, thresholds, min_lengths, index, n_boot, seed, level, unit, events,
+                                offset_drops, min_gaps, penalties, event_f1)
+
+
+# ---- the difference of two systems under the same resamples (bootstrap.pair_intervals_*; lad_bootstrap_pair_quantiles) ----------------
+def _diff_columns(figures):
+    return ["threshold", "min_len", *(f + s for f in figures for s in ("_a", "_b", "_diff", "_diff_lo", "_diff_hi", "_gt")), "n_boot_valid"]
+
+
+SUM_DIFF_COLUMNS = _diff_columns(("precision", "recall", "f1"))
+EVENT_SUM_DIFF_COLUMNS = _diff_columns(("event_precision", "event_recall"))
+EVENT_SUM_CI_F1_COLUMNS = EVENT_SUM_CI_COLUMNS[:-1] + ["event_f1", "event_f1_lo", "event_f1_hi", "n_boot_valid"]
+_A, _B = 0, 1                  # the system a figure of a pair template reads (bootstrap.pair_cell_figures)
+_TIME_DIFFS = [(bootstrap.DIFFERENCE, (_A, *f), (_B, *f)) for f in _TIME_FIGURES]
+_EVENT_DIFFS = [(bootstrap.DIFFERENCE, (_A, *f), (_B, *f)) for f in _EVENT_FIGURES]
+_EVENT_F1_PAIR = [(bootstrap.HARMONIC, (_A, *_EVENT_FIGURES[0]), (_A, *_EVENT_FIGURES[1]))]
+
+
+def _bootstrap_diff_sum_stats(pair_intervals, scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot, seed, level, unit,
+                              events_a, events_b, offset_drops, min_gaps, penalties):
+    if (events_a is None) != (events_b is None):
+        raise ValueError("events_a and events_b go together")
+    scores_a, cells, order = _sweep_cells(scores_a, channels, thresholds, min_lengths, events_a, offset_drops, min_gaps, penalties)
+    scores_b = np.asarray(scores_b)
+    if scores_b.shape != scores_a.shape:
+        raise ValueError(f"scores_a {scores_a.shape} and scores_b {scores_b.shape} are not of one sweep and the same channels")
+    if events_b is not None and np.asarray(events_b).shape != scores_b.shape:
+        raise ValueError(f"scores {scores_b.shape} and events_b {np.asarray(events_b).shape} are not of one sweep")
+    unit_of, transc_ms = bootstrap_units(channels, index, unit)
+    if not transc_ms:
+        raise ValueError("no channel with a participant: nothing to resample")
+    quantiles = bootstrap.quantile_pairs(level)
+    flat_a, flat_b = (s.reshape(len(channels), len(cells), len(FIELDS)) for s in (scores_a, scores_b))
+    nan = float("nan")
+
+    def rows_of(fields_a, fields_b, per_cell, template, fractions):
+        xa, xb = (_unit_matrix(f, unit_of, transc_ms) for f in (fields_a, fields_b))
+        x = np.concatenate([xa[:, :-1], xb], axis=1)                               # A's cells, B's cells, the shared column
+        out, valid, signs = pair_intervals(x, per_cell, template, n_boot, seed, quantiles)
+        total_a, total_b = ([int(v) for v in m.sum(axis=0)] for m in (xa, xb))
+        rows = []
+        for j in order:
+            _, thr, min_l, extra = cells[j]
+            row = [thr, min_l, *extra]
+            both = (fractions(t[j * per_cell:(j + 1) * per_cell], t[-1]) for t in (total_a, total_b))
+            for f, (a, b) in enumerate(zip(*both)):
+                diff = nan if a is None or b is None else bootstrap.pair_value(bootstrap.DIFFERENCE, (*a, *b))
+                v = int(valid[j, f])
+                row += [_number(a), _number(b), diff, *(bootstrap.pair_value(bootstrap.DIFFERENCE, out[j, f, k]) for k in (0, 1)),
+                        int(signs[j, f, 2]) / v if v else nan]
+            rows.append(row + [int(valid[j].min())])
+        return rows
+
+    time_rows = rows_of(flat_a[:, :, 2:4], flat_b[:, :, 2:4], 2, _TIME_DIFFS, _time_fractions)
+    if events_a is None:
+        return time_rows
+    return time_rows, rows_of(_event_fields(flat_a, events_a), _event_fields(flat_b, events_b), 4, _EVENT_DIFFS, _event_fractions)
+
+
+def bootstrap_diff_sum_stats_host(scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95, unit="channel",
+                                  events_a=None, events_b=None, offset_drops=None, min_gaps=None, penalties=None):
+    """Two systems A and B, scored by one sweep on the same channels (score arrays of one shape: ValueError otherwise): is A better
+    than B?  Both are resampled with the same weights -- those of bootstrap_sum_stats_host for this seed --, every figure of both is
+    recomputed on each resample, and the replicates are ordered by the exact difference A - B (include/lad_hip.h:
+    lad_bootstrap_pair_quantiles).  The errors of two systems on the same channels are correlated, so this interval is as a rule
+    much narrower than either system's own.
+    Returns rows of SUM_DIFF_COLUMNS (the decoder's axes behind min_len: columns(SUM_DIFF_COLUMNS, decoder)), in calc_sum_stats'
+    order: threshold, min_len, then for each of precision, recall and f1 six columns -- <f>_a and <f>_b, the point figures of
+    bootstrap_sum_stats_host; <f>_diff, the exact A - B of the plain unit sums converted once (NaN where either is NaN);
+    <f>_diff_lo and <f>_diff_hi, the quantiles (100 - level) / 200 and 1 - that of the replicates' differences, each
+    float(Fraction(n1, d1) - Fraction(n2, d2)) of one replicate; <f>_gt, the share of valid replicates in which A is strictly
+    greater (NaN without one) -- and n_boot_valid, the smallest number of valid replicates among the row's figures (a replicate is
+    valid for a difference where it is for both systems' figures).
+    events_a, events_b (both): -> (rows, event rows), the second of EVENT_SUM_DIFF_COLUMNS, for event_precision and event_recall.
+    Event F1 of two systems is not differenced: a difference of two harmonic means is four figures, and ordering it exactly takes
+    512-bit products.  Nor is average precision.
+    This is the parity form: numpy and Python integers, no float before the final conversion."""
+    return _bootstrap_diff_sum_stats(bootstrap.pair_intervals_host, scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot, seed,
+                                     level, unit, events_a, events_b, offset_drops, min_gaps, penalties)
+
+
+def bootstrap_diff_sum_stats_device(scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot=2000, seed=0, level=95,
+                                    unit="channel", events_a=None, events_b=None, offset_drops=None, min_gaps=None, penalties=None,
+                                    device="cuda"):
+    """bootstrap_diff_sum_stats_host on the GPU (csrc/bootstrap.hip through bootstrap.pair_intervals_device): one matrix of both
+    systems' cells, one draw of the weights, lad_bootstrap_sums and lad_bootstrap_pair_quantiles in chunks within
+    bootstrap.SUMS_BYTES_CAP.  Equal rows (NaN matching NaN) whatever the chunk size.  No CPU fallback."""
+
+    def pair_intervals(x, per_cell, template, n_boot, seed, quantiles):
+        return bootstrap.pair_intervals_device(x, per_cell, template, n_boot, seed, quantiles, device=device)
+    return _bootstrap_diff_sum_stats(pair_intervals, scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot, seed, level, unit,
+                                     events_a, events_b, offset_drops, min_gaps, penalties)
