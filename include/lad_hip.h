@@ -1230,6 +1230,66 @@ int lad_bootstrap_pair_quantiles(const int64_t *sums, int64_t columns, int32_t r
                                  const int32_t *pairs_host, int64_t n_pairs, const int32_t *q_num, const int32_t *q_den,
                                  int32_t n_quantiles, int64_t *out, int32_t *valid, int32_t *signs, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Calibration of the probability track against the transcript (csrc/calibration.hip): the label histogram of a track, and a
+ * 65537-entry map applied to a track.  Not in the reference, which treats the network's output as a probability and never checks
+ * it.  The text below IS the specification (tests/_calibration_model.py is a second implementation of it, with per-millisecond
+ * sets and a Python loop over the frames).  The device only adds integers; every figure (Brier, NLL, ECE, ROC AUC, the
+ * reliability table) and every fit (Platt, temperature, isotonic) follows on the host from the 5 x 65538 integers of a row
+ * (calibration.py).
+ *
+ * Frames.  v[i] is the fixed probability exactly as in lad_runs_count: p > 1 becomes 1, p <= 0 becomes 1e-7, NaN is kept, and a
+ * float32 sample is widened exactly.  The bucket of a frame is u[i] = (int)floor(v[i] * 65536.0), in 0..65536, as in
+ * lad_viterbi_count.  A NaN frame goes to slot 65537, so a histogram row has lad_label_histogram_slots() = 65538 slots.
+ * Time.  For channel c with n_c frames (lengths_host[c], or `frames` when lengths_host is NULL), m_j = rint((double)j / fps[c] *
+ * 1000) for j = 0..n_c: IEEE division, no reciprocal, contraction off, the expression of lad_score_runs for a run's ends.  Frame i
+ * (0 <= i < n_c) owns the millisecond interval (m_i, m_{i+1}].  A run first..last of the scorers is (m_first, m_last], the
+ * frames first..last-1: the convention the scorers already use.  Frames at or beyond n_c are not read.
+ * Weights.  w_k(i) = F_k(m_{i+1}) - F_k(m_i) for the five segments k of the index (enum lad_score_class; LAUGH, SPEECH, NOISE and
+ * SILENCE come with INVALID already subtracted), F the coverage function of lad_score_runs: the milliseconds of class k in
+ * (0, x].  Milliseconds in none of the five sets (beyond the channel's length) belong to nobody.
+ * Output.  hist[g][k][slot], int64, n_groups x 5 x 65538 entries: the sum of w_k(i) over the frames i of every channel c with
+ * group[c] == g whose slot is `slot`.  group_host: HOST int32[channels] with values in -1..n_groups-1; -1 leaves the channel out;
+ * NULL puts channel c into group c, and n_groups must equal channels then.  The entry point zeroes hist itself.
+ * Consequences.  For every channel and class the sum over all 65538 slots equals F_k(m_{n_c}).  A channel without a participant
+ * (five empty sets) adds nothing.  All sums stay below 2^47: a channel holds fewer than 2^31 ms (lad_score_runs' millisecond-
+ * overflow check, here on m_{n_c}) and there are at most 65535 channels.
+ * Arithmetic.  Integer sums only, accumulated with vector global atomics on int64: identical bytes on every call.
+ *
+ * Launches: one memset of hist, one copy each of the lengths and the groups where they are given, and two launches whatever the
+ * sizes: the running lengths of the index (one workgroup per (channel, class)), then one workgroup per (channel,
+ * lad_label_histogram_tile_frames() frames).  A workgroup sorts its frames by slot in LDS, sums the weights of equal slots there,
+ * and issues at most one atomic per distinct (class, slot) it met, none for a sum of zero: a constant track costs at most five
+ * atomics a workgroup.  An index without any interval returns after the memset.
+ * ---------------------------------------------------------------------------------------------- */
+/* slots of a histogram row (65538: buckets 0..65536, then the NaN frames) */
+int32_t lad_label_histogram_slots(void);
+/* frames per workgroup (the tests place their edges from it) */
+int32_t lad_label_histogram_tile_frames(void);
+/* bytes of workspace for lad_label_histogram; needs no GPU.  -1 and lad_last_error() for channels outside 1..65535, frames
+ * outside 1..2^30 or n_intervals outside 0..2^30. */
+int64_t lad_label_histogram_workspace_bytes(int64_t channels, int64_t frames, int64_t n_intervals);
+/* probs: DEVICE float32 or float64 [channels][frames], contiguous (dtype: lad_runs_dtype), only read.  lengths_host: HOST
+ * int64[channels], each 1..frames, or NULL.  bounds, offsets, fps: DEVICE, the index and the frame rates as lad_score_runs takes
+ * them; bounds_host, offsets_host, fps_host: HOST copies of the same values, checked before anything is launched.  workspace:
+ * DEVICE, lad_label_histogram_workspace_bytes.  hist: DEVICE int64[n_groups][5][65538].  The host arrays have been copied when
+ * the call returns.
+ * LAD_ERR_INVALID with lad_last_error() set, nothing launched and nothing written, for everything lad_score_runs refuses of the
+ * index and fps (offsets that do not ascend from 0 to n_intervals, intervals that are empty, unsorted or overlapping, an fps that
+ * is not positive and finite, millisecond overflow of m_{n_c}), sizes out of range, an unknown dtype, a null pointer, a length
+ * outside 1..frames, a group outside -1..n_groups-1, n_groups outside 1..channels (or not channels when group_host is NULL), or
+ * hist, probs and the workspace overlapping one another. */
+int lad_label_histogram(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const int64_t *lengths_host,
+                        const int32_t *bounds, const int32_t *offsets, const int32_t *bounds_host, const int32_t *offsets_host,
+                        int64_t n_intervals, const double *fps, const double *fps_host, const int32_t *group_host,
+                        int32_t n_groups, void *workspace, int64_t *hist, void *stream);
+/* out[c][i] = table[u[i]] with u the bucket above; a NaN frame gives NaN.  table: DEVICE double[65537], read as it is (the caller
+ * keeps it in [0, 1]); out: DEVICE double[channels][frames].  One launch, one lane per frame, the table read through the cache;
+ * every decoder, smoother and scorer takes the result as a float64 track.  LAD_ERR_INVALID with lad_last_error() set, nothing
+ * launched and nothing written, for sizes out of range, an unknown dtype, a null pointer, or out overlapping probs or the table. */
+int lad_track_remap(const void *probs, int32_t dtype, int64_t channels, int64_t frames, const double *table, double *out,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,14 @@ SIGNATURES = {
                                         ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p]),
     "lad_bootstrap_pair_quantiles": (c_int, [c_void_p, c_i64, c_i32, c_void_p, ctypes.POINTER(c_i32), c_i64, ctypes.POINTER(c_i32),
                                              ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # calibration of the track: label histogram against the transcript, a 65537-entry map applied to a track (csrc/calibration.hip)
+    "lad_label_histogram_slots": (c_i32, []),
+    "lad_label_histogram_tile_frames": (c_i32, []),
+    "lad_label_histogram_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "lad_label_histogram": (c_int, [c_void_p, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64), c_void_p, c_void_p, ctypes.POINTER(c_i32),
+                                    ctypes.POINTER(c_i32), c_i64, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_i32), c_i32,
+                                    c_void_p, c_void_p, c_void_p]),
+    "lad_track_remap": (c_int, [c_void_p, c_i32, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,6 +6,8 @@
 // point's name and in what it calls its K axis ("thresholds" / "settings"): among them everything lad_score_runs and
 // lad_score_events ask before they launch (check_scorer) and the largest number of events of one channel (most_events_of).
 // lad_score_runs and lad_score_events read the workspace the other two wrote, so there is one definition of each.
+// calibration.hip (the label histogram of a track) takes from here the fixed load, the index scan, the coverage look-up and the
+// index's half of the host checks (check_index_intervals).
 #pragma once
 #include <cmath>
 
@@ -288,18 +290,10 @@ inline int load_min_lengths(const char *who, const double *min_lengths, int L, M
     return LAD_OK;
 }
 
-// what a scorer asks of the time base and the interval index before it launches anything: millisecond values are int32
-// (to_frames(frames / fps) < 2^31 for every channel); offsets ascend from 0 to n_intervals; within a (channel, class) intervals are
-// non-empty, sorted and disjoint
-inline int check_index(const char *who, int64_t channels, int64_t frames, const double *fps_host, const int32_t *offsets_host,
-                       const int32_t *bounds_host, int64_t n_intervals) {
-    if (int rc = check_fps(who, fps_host, channels)) return rc;
-    for (int64_t c = 0; c < channels; ++c) {
-        const double f = fps_host[c];
-        const double ms = std::nearbyint((double)frames / f * MS);
-        LAD_REQUIRE(ms < 2147483648.0, "%s: millisecond overflow: %lld frames at fps[%lld] = %g end at %.0f ms, int32 holds 2^31 - 1", who,
-                    (long long)frames, (long long)c, f, ms);
-    }
+// what the scorers and lad_label_histogram ask of the interval index before they launch anything: offsets ascend from 0 to
+// n_intervals; within a (channel, class) intervals are non-empty, sorted and disjoint
+inline int check_index_intervals(const char *who, int64_t channels, const int32_t *offsets_host, const int32_t *bounds_host,
+                                 int64_t n_intervals) {
     LAD_REQUIRE(offsets_host[0] == 0 && offsets_host[channels * CLASSES] == n_intervals,
                 "%s: index offsets run from %d to %d, expected 0 to %lld", who, offsets_host[0], offsets_host[channels * CLASSES],
                 (long long)n_intervals);
@@ -317,6 +311,21 @@ inline int check_index(const char *who, int64_t channels, int64_t frames, const 
         }
     }
     return LAD_OK;
+}
+
+// what a scorer asks of the time base and the interval index before it launches anything: millisecond values are int32
+// (to_frames(frames / fps) < 2^31 for every channel), then check_index_intervals (lad_label_histogram checks the time base per
+// channel length instead and then asks the same of the index)
+inline int check_index(const char *who, int64_t channels, int64_t frames, const double *fps_host, const int32_t *offsets_host,
+                       const int32_t *bounds_host, int64_t n_intervals) {
+    if (int rc = check_fps(who, fps_host, channels)) return rc;
+    for (int64_t c = 0; c < channels; ++c) {
+        const double f = fps_host[c];
+        const double ms = std::nearbyint((double)frames / f * MS);
+        LAD_REQUIRE(ms < 2147483648.0, "%s: millisecond overflow: %lld frames at fps[%lld] = %g end at %.0f ms, int32 holds 2^31 - 1", who,
+                    (long long)frames, (long long)c, f, ms);
+    }
+    return check_index_intervals(who, channels, offsets_host, bounds_host, n_intervals);
 }
 
 inline int check_dtype(const char *who, int32_t dtype) {

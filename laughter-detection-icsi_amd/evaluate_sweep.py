@@ -60,6 +60,20 @@ the same smoother, decoder and scorer as those of `--probs_dir` (system A), and 
 precision, recall and F1, the exact difference A - B, its interval under the same resamples and the share of resamples in which A
 is strictly greater (sweep_eval.bootstrap_diff_sum_stats_host / _device: the same bytes under either scorer); with `--events` /
 `--event_grid` also `event_sum_stats_diff.csv`, for event precision and recall.  Every other file is that of `--probs_dir` alone.
+`--calibration_report` (default: off; not in the reference) also writes `calibration.csv` -- per meeting and for `all` the
+threshold-free, frame-level figures of the tracks as they are evaluated (behind `--calibration`, `--lowpass` / `--median`): laugh
+and non-laugh milliseconds, Brier score, NLL, ECE / MCE over `--calibration_bins` bins (default 15), ROC AUC and average precision
+(calibration.calibration_figures) -- and `reliability.csv`, the reliability table of all meetings together.  Both come from one
+label histogram grouped by meeting (calibration.label_histogram_host under the host scorer, csrc/calibration.hip through
+calibration.label_histogram_device under the device scorer: the same integers, so the same bytes -- except behind `--lowpass`, where
+the device filter equals scipy's only within the rounding of float64 and a smoothed value next to a bucket's edge may fall on
+either side; behind `--median` and without a smoother the two routes see the same values bit for bit).
+`--fit_calibration {platt,temperature,isotonic}` (default: absent) fits a calibration map on the tracks as loaded, before any
+smoothing, and writes `calibration_table.npz` (the 65537-entry table, the method, its parameters, the figures before and after).
+`--calibration FILE` (default: absent) applies such a table to every track first, before `--lowpass` / `--median` and every
+decoder (calibration.apply_calibration, or lad_track_remap under the device scorer): fit on the dev split, apply on the test split.
+With `--compare_probs_dir` the one table is applied to both systems, as the smoother and the decoder are; two systems that need a
+table each are calibrated beforehand.  Not together with `--fit_calibration`.  Without the three flags the directory holds what it held before.
 """
 import argparse
 import csv
@@ -73,6 +87,7 @@ for _p in (os.path.join(_PKG, "utils"), _PKG):
 
 import numpy as np  # noqa: E402
 
+import calibration  # noqa: E402
 import laugh_segmenter  # noqa: E402
 import sweep_eval  # noqa: E402
 
@@ -176,15 +191,31 @@ def level_arg(text):
     return text
 
 
-def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, median=None, **axes_and_events):
+def bins_arg(text):
+    """--calibration_bins: the equal-width bins of ECE, MCE and the reliability table."""
+    value = int(text)
+    if not 1 <= value <= 65537:
+        raise argparse.ArgumentTypeError(f"an integer in 1..65537, got {text}")
+    return value
+
+
+def upload(tracks, table=None):
+    """All tracks as one NaN-padded (C, T) GPU tensor: float32 if every track is float16 / float32, else float64.  table: a
+    calibration table, applied on the device first (the result is float64; the padding stays NaN)."""
     import torch
     dtype = np.float32 if all(t.dtype in (np.float16, np.float32) for t in tracks) else np.float64
     padded = np.full((len(tracks), max(len(t) for t in tracks)), np.nan, dtype)
     for c, t in enumerate(tracks):
         padded[c, :len(t)] = t
+    probs = torch.from_numpy(padded).cuda()
+    return probs if table is None else laugh_segmenter.apply_calibration_device(probs, table)
+
+
+def score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=None, surface=False, median=None, table=None,
+                 **axes_and_events):
     lengths = [len(t) for t in tracks] if lowpass is not None or median is not None else None
     score = sweep_eval.score_surface_device if surface else sweep_eval.score_sweep_device
-    return score(torch.from_numpy(padded).cuda(), channels, thresholds, min_lengths, fps, index, lowpass=lowpass, lengths=lengths,
+    return score(upload(tracks, table), channels, thresholds, min_lengths, fps, index, lowpass=lowpass, lengths=lengths,
                  **({} if median is None else {"median": median}), **axes_and_events)
 
 
@@ -260,8 +291,41 @@ def build_parser():
                         help='(needs --bootstrap) a second system for the same channels, <meeting>/<chan>.npy as --probs_dir: also write '
                              'sum_stats_diff.csv (and event_sum_stats_diff.csv with --events / --event_grid), the difference --probs_dir '
                              'minus DIR of every figure with its interval under the same resamples; default: absent')
+    parser.add_argument('--calibration_report', action='store_true',
+                        help='(not in the reference) also write calibration.csv (per meeting and for all: Brier score, NLL, ECE, MCE, '
+                             'ROC AUC, average precision of the tracks as they are evaluated) and reliability.csv; the same bytes under '
+                             'either --scorer except behind --lowpass (the two filters agree within float64 rounding); default: off')
+    parser.add_argument('--calibration_bins', type=bins_arg, default=15, metavar='N',
+                        help='the equal-width bins of ECE, MCE and the reliability table, 1..65537; default: 15')
+    parser.add_argument('--fit_calibration', type=str, default=None, choices=list(calibration.METHODS),
+                        help='(not in the reference) fit a calibration map on the tracks as loaded (Platt scaling, temperature scaling '
+                             'or isotonic regression on the label histogram) and write calibration_table.npz; not with --calibration; '
+                             'default: absent')
+    parser.add_argument('--calibration', type=str, default=None, metavar='FILE',
+                        help='(not in the reference) a calibration_table.npz: its table is applied to every track first, before '
+                             '--lowpass / --median and every decoder (with --compare_probs_dir: to the tracks of both systems); '
+                             'default: absent')
     parser.add_argument('--out_dir', required=True, type=str)
     return parser
+
+
+def calibration_histogram(tracks, channels, fps, index, groups, scorer, table=None, lowpass=None, median=None):
+    """The label histogram (G, 5, 65538) of the tracks behind the table and the smoother, on the host or on the device as `scorer`
+    says: the tracks as they are evaluated, or with neither the tracks as loaded."""
+    if scorer == "device":
+        probs, lengths = upload(tracks, table), [len(t) for t in tracks]
+        if lowpass is not None:
+            probs = laugh_segmenter.lowpass_device(probs, cutoff=lowpass, lengths=lengths)
+        elif median is not None:
+            probs = laugh_segmenter.median_filter_device(probs, median, lengths=lengths)
+        return calibration.label_histogram_device(probs, channels, fps, index, lengths=lengths, groups=groups)
+    if table is not None:
+        tracks = [laugh_segmenter.apply_calibration(t, table) for t in tracks]
+    if lowpass is not None:
+        tracks = [laugh_segmenter.lowpass(t, cutoff=lowpass) for t in tracks]
+    elif median is not None:
+        tracks = [laugh_segmenter.median_filter(t, median) for t in tracks]
+    return calibration.label_histogram_host(tracks, channels, fps, index, groups=groups)
 
 
 def main(argv=None):
@@ -272,6 +336,9 @@ def main(argv=None):
         raise SystemExit("--bootstrap_event_f1 needs --bootstrap and --events or --event_grid")
     if args.median is not None and args.lowpass is not None:
         raise SystemExit("--median cannot be combined with --lowpass: they are two smoothers for the same place")
+    if args.fit_calibration is not None and args.calibration is not None:
+        raise SystemExit("--fit_calibration cannot be combined with --calibration: the fit is made on the tracks as loaded")
+    table = None if args.calibration is None else calibration.load_table(args.calibration)
     grid = args.threshold_grid
     if args.event_grid is not None:
         for flag in ("thresholds", "threshold_grid", "events", "offset_drops", "min_gaps", "penalties"):
@@ -313,14 +380,21 @@ def main(argv=None):
     with_events = args.events or args.event_grid is not None
     criteria = dict(events=(args.event_min_overlap_ms, args.event_min_overlap_pct)) if with_events else {}
 
+    calibrated = {} if table is None else {"table": table}
+
+    def frame_rates(tracks):
+        return [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
+
     def score(tracks):
-        fps = [args.fps if args.fps is not None else len(t) / length[mc] for mc, t in zip(channels, tracks)]
+        fps = frame_rates(tracks)
         if args.scorer == "device":
             if grid is not None:
                 return score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, surface=True,
-                                    median=args.median, **criteria)
-            return score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, median=args.median, **extra,
-                                **criteria)
+                                    median=args.median, **calibrated, **criteria)
+            return score_device(tracks, channels, thresholds, min_lengths, fps, index, lowpass=args.lowpass, median=args.median, **calibrated,
+                                **extra, **criteria)
+        if table is not None:
+            tracks = [laugh_segmenter.apply_calibration(t, table) for t in tracks]
         if args.lowpass is not None:
             tracks = [laugh_segmenter.lowpass(t, cutoff=args.lowpass) for t in tracks]
         elif args.median is not None:
@@ -370,6 +444,20 @@ def main(argv=None):
             diff, event_diff = diff
             write("event_sum_stats_diff.csv", sweep_eval.EVENT_SUM_DIFF_COLUMNS, event_diff)
         write("sum_stats_diff.csv", sweep_eval.SUM_DIFF_COLUMNS, diff)
+    if args.calibration_report:
+        meetings = sorted({m for m, _ in channels})
+        hist = calibration_histogram(tracks, channels, frame_rates(tracks), index, [meetings.index(m) for m, _ in channels], args.scorer,
+                                     table=table, lowpass=args.lowpass, median=args.median)
+        figures = [calibration.calibration_figures(h, n_bins=args.calibration_bins) for h in (*hist, hist.sum(axis=0))]
+        write_csv(os.path.join(args.out_dir, "calibration.csv"), calibration.CALIBRATION_COLUMNS,
+                  [calibration.figure_row(name, f) for name, f in zip(meetings + ["all"], figures)])
+        write_csv(os.path.join(args.out_dir, "reliability.csv"), calibration.RELIABILITY_COLUMNS, calibration.reliability_rows(figures[-1]))
+    if args.fit_calibration is not None:
+        row = calibration_histogram(tracks, channels, frame_rates(tracks), index, [0] * len(channels), args.scorer)[0]
+        fitted, parameters = calibration.fit(row, args.fit_calibration)
+        calibration.save_table(os.path.join(args.out_dir, "calibration_table.npz"), fitted, args.fit_calibration, parameters,
+                               calibration.calibration_figures(row, n_bins=args.calibration_bins),
+                               calibration.calibration_figures(calibration.remap_histogram(row, fitted), n_bins=args.calibration_bins))
     print(f"{len(channels)} channels, {int(np.prod(scores.shape[1:-1]))} settings ({args.scorer} scorer): "
           f"{len(per_meeting)} rows -> {args.out_dir}")
 

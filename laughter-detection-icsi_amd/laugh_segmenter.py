@@ -114,6 +114,21 @@ def median_filter_device(probs, window, lengths=None, out=None):
     return rankfilt.median_filter_device(probs, window, lengths=lengths, out=out)
 
 
+def apply_calibration(track, table):
+    """A fitted calibration table (float64 (65537,), one value per bucket of the Viterbi decoder: calibration.fit_platt /
+    fit_isotonic) applied to a host track: table[floor(v * 65536)] of the fixed probability v, NaN kept, float64.  Not in the
+    reference.  It stands in front of the smoothers and every decoder."""
+    import calibration
+    return calibration.apply_calibration(track, table)
+
+
+def apply_calibration_device(probs, table, out=None):
+    """`apply_calibration` for a (T,) or (C, T) track in GPU memory (csrc/calibration.hip through calibration.py): a float64 tensor
+    of the same shape that stays on the device, bit for bit what the host form returns.  No CPU fallback."""
+    import calibration
+    return calibration.apply_calibration_device(probs, table, out=out)
+
+
 def fix_over_underflow(prob):
     """p > 1 -> 1; p <= 0 -> 1e-7 (so that threshold 0 still accepts the frame); else p."""
     if prob > 1:

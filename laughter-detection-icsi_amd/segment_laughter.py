@@ -43,6 +43,12 @@ instance, `start,end,mean_prob,peak_time,peak_prob` (laugh_segmenter.span_stats 
 below X before anything is printed, cut or written.  Both work with either segmenter and every decoder; with `--lowpass` or
 `--median` the figures are those of the smoothed track, the one the instances were cut from.  Without the two flags paths and bytes
 are what they were; the TextGrid format never changes.
+
+`--calibration FILE` (default: absent; not in the reference) applies the table of a `calibration_table.npz` that
+`evaluate_sweep.py --fit_calibration` wrote to the track first, before `--lowpass` / `--median` and every decoder
+(laugh_segmenter.apply_calibration under `--segmenter host`, csrc/calibration.hip under `--segmenter device`: the same values bit
+for bit).  Thresholds, penalties in nats and `--confidence` then speak of calibrated probabilities; `--save_probs` keeps writing
+the raw track.
 """
 import argparse
 import os
@@ -138,6 +144,16 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
                   precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
                   save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None, median=None, confidence=False,
                   min_confidence=None):
+    """segment_laughter.py:79-122: load_and_pred_calibrated without a calibration table (its docstring has the arguments)."""
+    return load_and_pred_calibrated(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid, rank, world, precision,
+                                    save_to_audio_files, verbose, save_probs, segmenter, resample, save_audio_rate, lowpass, offset_drops,
+                                    min_gaps, penalties, median, confidence, min_confidence)
+
+
+def load_and_pred_calibrated(model, audio_path, thresholds, min_lengths, output_dir, save_to_textgrid=True, rank=0, world=1,
+                             precision="fp32", save_to_audio_files=False, verbose=True, save_probs=None, segmenter="host", resample=False,
+                             save_audio_rate=None, lowpass=None, offset_drops=None, min_gaps=None, penalties=None, median=None,
+                             confidence=False, min_confidence=None, *, calibration=None):
     """segment_laughter.py:79-122.  Returns (seconds taken by everything below, {(thr, min_len): [(start, end), ...]}).
     segmenter "device": the track stays on the GPU and rank 0 cuts it there (the other ranks return an empty dictionary).
     resample: accept a file at another rate than 16 kHz (converted on the GPU).  save_audio_rate: rate of the laugh_<i>.wav cuts
@@ -148,7 +164,9 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
     penalties: the Viterbi decoder; the dictionary's keys are (thr, penalty, min_len).  Not together with the two above.
     confidence: also write <file>.confidence.csv next to every TextGrid (start,end,mean_prob,peak_time,peak_prob per instance, of
     the track the instances were cut from: the smoothed one under lowpass / median).  min_confidence: instances whose mean
-    probability lies below it are dropped from the dictionary and from everything printed, cut or written."""
+    probability lies below it are dropped from the dictionary and from everything printed, cut or written.
+    calibration: None, or a calibration table (float64 (65537,): calibration.load_table): applied to the track first, in front of the
+    smoother and the decoder, on the host or on the device like the sweep; save_probs still gets the raw track."""
     if segmenter not in ("host", "device"):
         raise ValueError(f"segmenter must be 'host' or 'device', got {segmenter!r}")
     if lowpass is not None and median is not None:
@@ -165,6 +183,9 @@ def load_and_pred(model, audio_path, thresholds, min_lengths, output_dir, save_t
         # (not in the reference: the per-frame track, e.g. to compare a sharded run with a single-rank one)
         np.save(save_probs, probs.cpu().numpy() if segmenter == "device" else probs)
     fps = len(probs) / float(file_length)
+    if calibration is not None and (segmenter == "host" or rank == 0):
+        probs = laugh_segmenter.apply_calibration(probs, calibration) if segmenter == "host" else \
+            laugh_segmenter.apply_calibration_device(probs, calibration)
     if lowpass is not None and (segmenter == "host" or rank == 0):
         probs = laugh_segmenter.lowpass(probs, cutoff=lowpass) if segmenter == "host" else \
             laugh_segmenter.lowpass_device(probs, cutoff=lowpass)
@@ -254,6 +275,9 @@ def build_parser():
     parser.add_argument('--min_confidence', type=float, default=None, metavar='X',
                         help="(not in the reference) drop the instances whose mean probability is below X before anything is printed, cut "
                              "or written (of the smoothed track under --lowpass or --median); default: absent")
+    parser.add_argument('--calibration', type=str, default=None, metavar='FILE',
+                        help="(not in the reference) a calibration_table.npz of evaluate_sweep.py --fit_calibration: its table is "
+                             "applied to the track first, before --lowpass / --median and every decoder; default: absent")
     parser.add_argument('--resample', type=str, default='False',
                         help="(not in the reference) 'True': an input file at another sampling rate than 16 kHz is converted on the GPU "
                              "(polyphase FIR, scipy.signal.resample_poly's convention) instead of refused")
@@ -272,6 +296,10 @@ def main(argv=None):
                                               timeout=None))
     thresholds = [float(t) for t in args.thresholds.split(',')]
     min_lengths = [float(l) for l in args.min_lengths.split(',')]
+    table = None
+    if args.calibration is not None:
+        import calibration
+        table = calibration.load_table(args.calibration)
     rank, world, local = parallel.init_from_env()
     if args.gpus is not None and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the launcher environment says WORLD_SIZE={world}")
@@ -281,12 +309,13 @@ def main(argv=None):
     torch.cuda.set_device(device)
     model = build_model(args.config, args.model_path, device)
     truthy = ('true', '1', 'yes')
-    load_and_pred(model, args.input_audio_file, thresholds, min_lengths, args.output_dir,
-                  save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world,
-                  precision=args.precision, save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
-                  segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
-                  lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties,
-                  median=args.median, confidence=args.confidence.lower() in truthy, min_confidence=args.min_confidence)
+    load_and_pred_calibrated(model, args.input_audio_file, thresholds, min_lengths, args.output_dir,
+                             save_to_textgrid=args.save_to_textgrid.lower() in truthy, rank=rank, world=world, precision=args.precision,
+                             save_to_audio_files=args.save_to_audio_files.lower() in truthy, save_probs=args.save_probs,
+                             segmenter=args.segmenter, resample=args.resample.lower() in truthy, save_audio_rate=args.save_audio_rate,
+                             lowpass=args.lowpass, offset_drops=args.offset_drops, min_gaps=args.min_gaps, penalties=args.penalties,
+                             median=args.median, confidence=args.confidence.lower() in truthy, min_confidence=args.min_confidence,
+                             calibration=table)
 
 
 if __name__ == '__main__':

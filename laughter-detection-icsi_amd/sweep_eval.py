@@ -37,6 +37,9 @@ here a set is a sorted (n, 2) array of (lo, hi] end points and an overlap is a d
     bootstrap_sum_stats_device  the same rows from csrc/bootstrap.hip.  No CPU fallback.
     bootstrap_diff_sum_stats_host / _device   two systems scored on the same channels: their point figures, the exact difference A - B
                            with its interval under the same resamples, and the share of resamples in which A is strictly better
+    label_histogram_host / _device, calibration_figures   the frame-level, threshold-free view of the track (calibration.py; csrc/
+                           calibration.hip): per bucket of the track's value the milliseconds of every class, and from them Brier
+                           score, NLL, ECE, ROC AUC and the reliability table
 
 Everything is integer arithmetic plus a few IEEE float64 operations, so host and device agree exactly.
 """
@@ -1078,3 +1081,24 @@ def bootstrap_diff_sum_stats_device(scores_a, scores_b, channels, thresholds, mi
         return bootstrap.pair_intervals_device(x, per_cell, template, n_boot, seed, quantiles, device=device)
     return _bootstrap_diff_sum_stats(pair_intervals, scores_a, scores_b, channels, thresholds, min_lengths, index, n_boot, seed, level, unit,
                                      events_a, events_b, offset_drops, min_gaps, penalties)
+
+
+def label_histogram_host(tracks, channels, fps, index, lengths=None, groups=None):
+    """calibration.label_histogram_host: per bucket of the track's value the milliseconds of every transcript class that the frames
+    in the bucket own, int64 (G, 5, 65538) (include/lad_hip.h: lad_label_histogram has the convention).  The one frame-level,
+    threshold-free view of the track: calibration.calibration_figures reads Brier, NLL, ECE, ROC AUC and the reliability table
+    from a row of it."""
+    import calibration
+    return calibration.label_histogram_host(tracks, channels, fps, index, lengths=lengths, groups=groups)
+
+
+def label_histogram_device(probs, channels, fps, index, lengths=None, groups=None):
+    """calibration.label_histogram_device: the same array for tracks in GPU memory (csrc/calibration.hip).  No CPU fallback."""
+    import calibration
+    return calibration.label_histogram_device(probs, channels, fps, index, lengths=lengths, groups=groups)
+
+
+def calibration_figures(hist_row, n_bins=15):
+    """calibration.calibration_figures of one histogram row."""
+    import calibration
+    return calibration.calibration_figures(hist_row, n_bins=n_bins)
